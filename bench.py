@@ -5,11 +5,19 @@ tokens), one process per GPU, RCCL gradient all-reduce once per optimiser step.
 
 A "step" = one gradient-accumulation window of --window slides per rank pushed through the model as
 one ragged batch (loss = ces, models/loss.py:5-28), gradients all-reduced, Adam step.  Prints ONE
-JSON line (rank 0) with the contract fields plus `roofline` (the model's long-bag cross-attention
+JSON line (rank 0) with the contract fields.  A plain run sets up, warms up, times --steps steps and
+prints; everything else is measured only with --full: `roofline` (the model's long-bag cross-attention
 kernel timed by HIP events on its own stream against algorithmic bytes), `cpu_baseline` (the CPU
-oracle timed on this box's host cores on a bounded sample, N=1 only) and `extra`: the same
-measurement for the other BASELINE configs (cfg 3 NaCAGaT 15k, cfg 4 ragged 2k-30k windows, cfg 5
-100k-patch fp32 bags), each with its own roofline.
+oracle timed on the host's cores on a bounded sample, N=1 only), `extra` (the same
+measurement for the other BASELINE configs: cfg 3 NaCAGaT 15k, cfg 4 ragged 2k-30k windows, cfg 5
+100k-patch fp32 bags, each with its own roofline) and config.ms_per_step_without_setup_replays.
+
+The training state is rewound to its value after set-up before the timed steps and every REWIND_EVERY steps, outside
+the timed region: trained on the same windows much longer, the model reaches the ces loss's NaN (see REWIND_EVERY).
+
+--dump-outputs DIR writes what the last timed step handed back (per-slide loss and risk, and the flat
+parameter and gradient buffers after it; see dump_outputs) as DIR/<name>.npy.  Inputs and weights are
+seeded, so two builds run with the same arguments can be compared output for output.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself
 (torch.distributed.run, 127.0.0.1) BEFORE this process touches the GPU, relays their output and exits
@@ -30,6 +38,12 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 BASE_SEED = 1234               # synthetic inputs from seed 1234 + config index / rank
 SETTLE_STEPS = 40            # default of --settle: untimed replays after graph capture and before the W warmup steps (setup; see run_config)
+# The step trains on the same resident windows over and over, and the model memorises them: a censored slide's survival
+# S[y] rounds to 1.0 and the reference's ces loss computes 0 * log(1 - S[y]) = NaN (models/loss.py:5-28, kept by the loss
+# kernel), after which every step computes NaN.  First non-finite step from initialisation, measured: 179 (the headline
+# config), 114 (--n-windows 1), 121 (--model-size big), 209-1228 (other configs).  So the training state is rewound to its
+# value after set-up every REWIND_EVERY steps and before the timed steps, outside the timed region (see run_config).
+REWIND_EVERY = 48
 
 
 def parse(argv=None):
@@ -62,6 +76,11 @@ def parse(argv=None):
                          "config.setup_replays_before_warmup; 0 = the bare W-warmup / K-timed contract)")
     ap.add_argument("--no-extras", action="store_true", help="headline configuration only")
     ap.add_argument("--no-graph", action="store_true", help="run the step eagerly instead of replaying a captured HIP graph")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the bare-contract pass, the roofline kernel, "
+                         "the other BASELINE configs (unless --no-extras) and the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
     return ap.parse_args(argv)
 
 
@@ -296,6 +315,23 @@ def cpu_baseline_leg(kind, patches, budget_s=15.0):
             "sample": f"{n} slides of {patches}x1024 fp32, {kind} medium, fwd+ces+bwd, one slide per call"}
 
 
+DUMP_MAX_ELEMS = 6 * 2 ** 20      # per flat buffer (24 MB of float32): two buffers + the per-slide vectors stay under 64 MB
+
+
+def dump_outputs(path, loss, risk, bucket, opt):
+    """The last timed step's outputs as float32 .npy files: what train_window hands back (per-slide loss and risk) and
+    the flat parameter / gradient buffers the step leaves behind.  A buffer longer than DUMP_MAX_ELEMS is written as a
+    fixed sample (seed 0, ascending indices), the same for every run of a given model."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"per_slide_loss": loss, "risk": risk, "params": opt.flat_p, "grads": bucket.flat}
+    for name, t in arrays.items():
+        x = t.detach().float().reshape(-1).cpu().numpy()
+        if x.size > DUMP_MAX_ELEMS:
+            x = x[np.sort(np.random.default_rng(0).permutation(x.size)[:DUMP_MAX_ELEMS])]
+        np.save(os.path.join(path, name + ".npy"), x)
+
+
 def _all_ranks_ok(ok: bool, dev, world) -> bool:
     """Collective agreement on a per-rank outcome: True only if EVERY rank reports ok (MIN all-reduce; identity at N = 1)."""
     if world == 1:
@@ -350,11 +386,13 @@ def ge_cpu_baseline_leg(patches=15000, timeout_s=180, need_gib=64):
     return json.loads(r.stdout.strip().splitlines()[-1])
 
 
-def run_config(a, dev, rank, world, steps, warmup, with_roofline=True):
+def run_config(a, dev, rank, world, steps, warmup, with_roofline=True, bare_pass=True, dump=None):
     """Build the model and its resident windows, time `steps` window steps (barrier + synchronize on both sides, max over
-    ranks) and return the contract dict (rank 0; None elsewhere)."""
+    ranks) and return the contract dict (rank 0; None elsewhere).  dump: directory for rank 0's dump_outputs() of the last
+    timed step."""
     import torch
     import torch.distributed as dist
+    from multimodal_path_omic_amd import ops as _ops
     from multimodal_path_omic_amd.dp import FlatAdam, FlatGradBucket
     from multimodal_path_omic_amd.harness import GraphedWindowStep, train_window
     bag_dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float32
@@ -369,10 +407,11 @@ def run_config(a, dev, rank, world, steps, warmup, with_roofline=True):
     def eager_step(i):
         bags, omics, labels, cens = windows[i % len(windows)]
         bucket.begin()
-        train_window(model, bags, omics, labels, cens, a.window)
+        out = train_window(model, bags, omics, labels, cens, a.window)
         bucket.finish()
         bucket.all_reduce_mean()
         opt.step()
+        return out
 
     graphed, graph_note = None, "eager"
     if not a.no_graph:
@@ -393,11 +432,11 @@ def run_config(a, dev, rank, world, steps, warmup, with_roofline=True):
         # against one): the choice must be the same on every rank, or the ranks hang in mismatched collectives.
         if not _all_ranks_ok(graphed is not None, dev, world) and graphed is not None:
             graphed, graph_note = None, "eager (graph capture failed on another rank)"
-    def step(i):
+    def window_step(i):
         if graphed is None:
             return eager_step(i)
         gs = graphed[i % len(graphed)]
-        gs()
+        out = gs()
         if world > 1:
             # the one exchange step of the path, split so that most of it hides behind the patch layer's weight-gradient
             # GEMM: everything but that gradient is ready after the main graph
@@ -409,38 +448,71 @@ def run_config(a, dev, rank, world, steps, warmup, with_roofline=True):
                 if h is not None:
                     h.wait()
             opt.step()
+        return out
+
+    # The whole training state -- parameters, Adam moments and step count, gradients, dropout counters -- as set-up left it
+    # (GraphedWindowStep puts back what its warm-up and priming replays touched).  Rewinding to it keeps every step inside
+    # the finite range (REWIND_EVERY); the work of a step does not depend on the values.
+    state = [opt.flat_p, opt.exp_avg, opt.exp_avg_sq, opt.t_dev, bucket.flat]
+    if _ops._rng_epoch_tensor is not None:
+        state.append(_ops._rng_epoch_tensor)
+    saved, saved_calls = [t.clone() for t in state], _ops._rng_calls
+    since_rewind = [0]
+
+    def rewind():
+        for t, v in zip(state, saved):
+            t.copy_(v)
+        _ops._rng_calls = saved_calls
+        since_rewind[0] = 0
+
+    def step(i):
+        if since_rewind[0] >= REWIND_EVERY:
+            rewind()
+        since_rewind[0] += 1
+        return window_step(i)
+
+    def timed_steps(first, n):
+        """n steps from window index `first`; returns (seconds, last step's output), rewinds excluded from the seconds."""
+        last, paused = None, 0.0
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for i in range(n):
+            if since_rewind[0] >= REWIND_EVERY:
+                torch.cuda.synchronize(dev)
+                tp = time.perf_counter()
+                rewind()
+                torch.cuda.synchronize(dev)
+                paused += time.perf_counter() - tp
+            last = step(first + i)
+        torch.cuda.synchronize(dev)
+        return time.perf_counter() - t0 - paused, last
 
     # Setup, not measurement: a few dozen replays so that the first timed steps do not pay for the card leaving its idle
     # state or for the first touch of the second resident window (the timed region of the driver's K = 20 is 22 ms long: one
     # 5 ms hiccup is a quarter of it -- seen once in round 3, 1.37 ms per step with every kernel at its usual time under
     # rocprofv3 minutes later).  Then the contract: W untimed warmup steps, exactly K timed ones.
     bare_ms = None
-    if world == 1 and a.settle > 0:
+    if bare_pass and world == 1 and a.settle > 0:
         # the bare contract first, for the record (config.ms_per_step_without_setup_replays): W warmup steps and K timed ones
         # straight after graph capture, beside the headline figure below
         for i in range(warmup):
             step(i)
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        for i in range(steps):
-            step(warmup + i)
-        torch.cuda.synchronize(dev)
-        bare_ms = (time.perf_counter() - t0) / steps * 1e3
+        bare_ms = timed_steps(warmup, steps)[0] / steps * 1e3
     for i in range(a.settle):
         step(i)
     torch.cuda.synchronize(dev)
     for i in range(warmup):
         step(i)
+    rewind()                                                      # the timed steps start from the state after set-up
     if world > 1:
         dist.barrier()
-    torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    for i in range(steps):
-        step(warmup + i)
-    torch.cuda.synchronize(dev)
+    dt, last = timed_steps(warmup, steps)
     if world > 1:
+        t0 = time.perf_counter()
         dist.barrier()
-    dt = time.perf_counter() - t0
+        dt += time.perf_counter() - t0
+    if dump is not None and rank == 0 and steps > 0:
+        dump_outputs(dump, *last, bucket, opt)
     if world > 1:
         t = torch.tensor([dt], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -459,6 +531,7 @@ def run_config(a, dev, rank, world, steps, warmup, with_roofline=True):
                        "patches_per_slide": "uniform[2000,30000] (fixed multiset)" if a.ragged else a.patches,
                        "parallelism": f"dp{world}", "resident_windows": a.n_windows, "launch": graph_note,
                        "setup_replays_before_warmup": a.settle,
+                       "training_state_rewound_every": REWIND_EVERY,
                        "ms_per_step_without_setup_replays": None if bare_ms is None else round(bare_ms, 3)},
         }
     if rank == 0 and with_roofline:
@@ -588,14 +661,14 @@ def main():
             sys.exit(f"--strong: the global window of {a.window} slides does not divide over {world} ranks")
         a.global_window = a.window
         a.window //= world                                        # per rank; the loss scale 1 / window x the mean over ranks = 1 / global window
-    out = run_config(a, dev, rank, world, a.steps, a.warmup)
-    if not a.no_extras and not a.ragged and a.model == "mcat" and a.patches == 15000 and a.dtype == "bf16":
+    out = run_config(a, dev, rank, world, a.steps, a.warmup, with_roofline=a.full, bare_pass=a.full, dump=a.dump_outputs)
+    if a.full and not a.no_extras and not a.ragged and a.model == "mcat" and a.patches == 15000 and a.dtype == "bf16":
         ex = extras(a, dev, rank, world)
         if rank == 0:
             out["extra"] = ex
     # the CPU leg comes LAST: ~20 s of 64 busy host threads right before a GPU leg left that leg's first seconds slow
     # (measured: the ragged extra at 1.92 ms per step after it, 1.47 ms before it)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_leg(a.model, a.patches)
         f3 = out.get("extra", {}).get("f3_ge_nacagat_15k")
         if isinstance(f3, dict) and "error" not in f3:

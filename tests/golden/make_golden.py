@@ -358,8 +358,29 @@ def gen_cohort():
     save("cohort", out)
 
 
+# ----------------------------------------------------------------------------- INTEGRATION.md section 3
+def gen_state_dicts():
+    """The reference models' state_dict listings (names in order + shapes) at the widths test_reference_swap.py checks the
+    drop-in slots against: MCAT / NaCAGaT x every fusion, and the gene-expression model at every size.  Names and shapes
+    only: shapes are padded with -1 to rank 3."""
+    sizes = [100, 200, 300, 400, 500, 600]
+    models = {}
+    for fusion in ("concat", "bilinear", "gated_concat"):
+        models[f"mcat/{fusion}"] = MultimodalCoAttentionTransformer(omic_sizes=sizes, fusion=fusion)
+        models[f"nacagat/{fusion}"] = NarrowContextualAttentionGateTransformer(omic_sizes=sizes, fusion=fusion)
+    for size in ("small", "medium", "big"):
+        models[f"ge_nacagat/{size}"] = GeneExprNarrowContextualAttentionGateTransformer(model_size=size)
+    out = {}
+    for key, model in models.items():
+        sd = model.state_dict()
+        assert all(v.dim() <= 3 for v in sd.values())
+        out[f"{key}/names"] = np.array(list(sd))
+        out[f"{key}/shapes"] = np.array([list(v.shape) + [-1] * (3 - v.dim()) for v in sd.values()], dtype=np.int64)
+    save("state_dicts", out)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["coattn_mcat", "coattn_nacagat", "cag", "encoder", "pool", "fusion",
-                             "models", "loss", "cohort", "fusion_next", "ge_models"]
+                             "models", "loss", "cohort", "fusion_next", "ge_models", "state_dicts"]
     for w in which:
         globals()["gen_" + w]()

@@ -144,6 +144,32 @@ def test_bench_gpus_n_starts_its_own_ranks(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_dump_outputs(tmp_path):
+    """A plain bench run measures the headline only (--full adds the rest); --dump-outputs writes float32 arrays, a flat
+    buffer above the size cap as the same seeded sample every time."""
+    import importlib.util
+    import types
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse(["--steps", "3"])
+    assert a.steps == 3 and not a.full and a.dump_outputs is None
+    assert bench.parse(["--full", "--dump-outputs", str(tmp_path)]).full
+    n = bench.DUMP_MAX_ELEMS + 1000
+    bucket = types.SimpleNamespace(flat=torch.arange(n, dtype=torch.float32))
+    opt = types.SimpleNamespace(flat_p=torch.ones(17))
+    loss, risk = torch.rand(32), torch.rand(32, dtype=torch.float64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), loss, risk, bucket, opt)
+    out = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(out) == ["grads.npy", "params.npy", "per_slide_loss.npy", "risk.npy"]
+    assert all(x.dtype == np.float32 for x in out.values())
+    assert np.array_equal(out["per_slide_loss.npy"], loss.numpy()) and np.array_equal(out["params.npy"], np.ones(17, np.float32))
+    g = out["grads.npy"]
+    assert g.size == bench.DUMP_MAX_ELEMS and np.all(np.diff(g) > 0) and g[-1] < n
+    assert np.array_equal(g, np.load(tmp_path / "b" / "grads.npy"))
+
+
 def test_empty_slides_are_refused():
     import torch
     from multimodal_path_omic_amd.ops import BagBatch
