@@ -167,13 +167,15 @@ int mpo_coattn_mcat_backward(const void* bag, int bag_dtype, const int32_t* cu_r
  * bf16 product [rows, cols], and its derivative g = dy * (h > 0 ? 1/(1-p) : 0).  (The forward half dates from r01, when the
  * product X W^T was a library call; mpo_patch_fc_forward has covered every model width since ABI v13 and the Python host no
  * longer calls it.)  Backward: n = rows * cols elements; d_bias (nullable, [cols]) receives the column
- * sums of g -- the layer's bias gradient -- from the same pass (workspace of *_workspace_bytes then required). */
+ * sums of g -- the layer's bias gradient -- from the same pass (workspace of *_workspace_bytes then required).
+ * The bf16 operands (and the forward's bias) are moved in 16-byte vectors: a pointer that is not 16-byte aligned is an error. */
 int mpo_patch_epilogue_forward(void* h_bf16, const float* bias, int64_t rows, int cols, float drop_p, uint64_t seed,
                                uint64_t offset, const uint64_t* rng_epoch, mpo_stream_t stream);
 size_t mpo_patch_epilogue_backward_workspace_bytes(int64_t n, int cols);
 int mpo_patch_epilogue_backward(const void* h_bf16, const void* dy_bf16, void* g_bf16, int64_t n, int cols, float drop_p,
                                 float* d_bias /* nullable */, void* workspace, size_t workspace_bytes, mpo_stream_t stream);
-/* out[c] = sum_r x[r][c] for a bf16 [rows, cols] tensor: the bias gradient of self.H (torch's reduce: 142 us) */
+/* out[c] = sum_r x[r][c] for a bf16 [rows, cols] tensor, cols = 8 * a divisor of 256, x 16-byte aligned: the bias gradient
+ * of self.H (torch's reduce: 142 us) */
 int mpo_colsum_bf16(const void* x_bf16, float* out, int64_t rows, int cols, mpo_stream_t stream);
 
 /* ---- weight gradient of self.H (models/mcat/mcat.py:24-29: Linear(1024, 256)): d_weight [embed, patch_dim] fp32 =

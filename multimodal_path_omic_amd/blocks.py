@@ -162,9 +162,11 @@ class PreGatingContextualAttention(nn.Module):
             total = ops.contextual_gate(q2, q_proj, self.CAG, residual=out)
             return total.view(n_slides, n_q, e), bags.split_map(amap, n_q)
         q_proj, out, amap, q_on = ops.coattn_nacagat(q2, bags, self.in_proj_weight, self.in_proj_bias, self.out_proj.weight,
-                                                     self.out_proj.bias, drop, bag_relu_gate, hand_on=True)
+                                                     self.out_proj.bias, drop, bag_relu_gate, hand_on=True,
+                                                     _qpass_owned=True)
+        # (the handed-on query's gradient is the pair's own slice: the encoder's fresh input gradient, read by nothing else)
         total, q_on = ops.contextual_gate(q_on, q_proj, self.CAG, residual=out, dest=(pair, 0),
-                                          hand_on=True)
+                                          hand_on=True, _qpass_owned=True)
         return total.view(n_slides, n_q, e), bags.split_map(amap, n_q), q_on.view(n_slides, n_q, e)
 
     def forward(self, query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, **unused):

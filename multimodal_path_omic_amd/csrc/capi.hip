@@ -674,10 +674,18 @@ int mpo_coattn_bwd_bagpass(const void* bag, int bag_dtype, const int32_t* cu_row
 // ------------------------------------------------------------------------------------------- patch layer epilogue
 int mpo_patch_epilogue_forward(void* h_bf16, const float* bias, int64_t rows, int cols, float drop_p, uint64_t seed,
                                uint64_t offset, const uint64_t* rng_epoch, mpo_stream_t stream) {
+    MPO_CHECK(h_bf16 && bias, "patch epilogue: null operand");
+    MPO_CHECK(rows >= 0, "patch epilogue: %lld rows", (long long)rows);
+    // (the kernel moves h as bf16 x 8 and the bias as fp32 x 4: 16-byte loads)
+    MPO_CHECK(((reinterpret_cast<uintptr_t>(h_bf16) | reinterpret_cast<uintptr_t>(bias)) & 15) == 0,
+              "patch epilogue: h and bias must be 16-byte aligned");
     return mpo_launch_bias_relu_dropout_bf16(h_bf16, bias, (size_t)rows, cols, drop_p, seed, offset,
                                              reinterpret_cast<const unsigned long long*>(rng_epoch), stream);
 }
 int mpo_colsum_bf16(const void* x_bf16, float* out, int64_t rows, int cols, mpo_stream_t stream) {
+    MPO_CHECK(x_bf16 && out, "bf16 column sum: null operand");
+    MPO_CHECK(rows >= 0, "bf16 column sum: %lld rows", (long long)rows);
+    MPO_CHECK((reinterpret_cast<uintptr_t>(x_bf16) & 15) == 0, "bf16 column sum: x must be 16-byte aligned (bf16 x 8 loads)");
     return mpo_launch_colsum_bf16(x_bf16, out, (size_t)rows, cols, stream);
 }
 size_t mpo_patch_epilogue_backward_workspace_bytes(int64_t n, int cols) {
@@ -685,6 +693,10 @@ size_t mpo_patch_epilogue_backward_workspace_bytes(int64_t n, int cols) {
 }
 int mpo_patch_epilogue_backward(const void* h_bf16, const void* dy_bf16, void* g_bf16, int64_t n, int cols, float drop_p,
                                 float* d_bias, void* workspace, size_t workspace_bytes, mpo_stream_t stream) {
+    MPO_CHECK(h_bf16 && dy_bf16 && g_bf16, "patch epilogue backward: null operand");
+    MPO_CHECK(((reinterpret_cast<uintptr_t>(h_bf16) | reinterpret_cast<uintptr_t>(dy_bf16) |
+                reinterpret_cast<uintptr_t>(g_bf16)) & 15) == 0,
+              "patch epilogue backward: h, dy and g must be 16-byte aligned (bf16 x 8 loads)");
     if (!d_bias) return mpo_launch_relu_dropout_bwd_bf16(h_bf16, dy_bf16, g_bf16, (size_t)n, drop_p, cols, nullptr, stream);
     MPO_CHECK(workspace && workspace_bytes >= mpo_patch_epilogue_backward_workspace_bytes(n, cols),
               "patch epilogue backward: workspace too small (%zu bytes)", workspace_bytes);

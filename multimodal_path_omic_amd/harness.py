@@ -109,7 +109,9 @@ class GraphedWindowStep:
     update) captured ONCE into a HIP graph and replayed: ~500 launches per window cost one graph launch on
     the host instead of ~4 ms of Python / launch overhead.
 
-    Static inputs: the window's tensors are resident and fixed (one captured graph per resident window).
+    Static inputs: the window's tensors are resident and fixed (one captured graph per resident window).  An fp32 window's
+    feature scale (ops.feature_scale) is baked into the graph as a kernel argument: a replay after an in-place write to
+    that window raises instead of computing with the stale scale.
     Frozen-at-capture values that must change per step live on the device: the dropout epoch (ops.set_rng_epoch,
     bumped inside the graph) and Adam's step count (dp.FlatAdam.t_dev).  With world_size > 1 leave the optimiser
     out (`opt=None`): replay, then all-reduce the bucket and step eagerly.
@@ -148,6 +150,8 @@ class GraphedWindowStep:
             self.epoch.copy_(keep_epoch)
         torch.cuda.current_stream(dev).wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
+        bag_data = window[0].data
+        self._fp32_window_version = bag_data._version if bag_data.dtype == torch.float32 else None
         # thread_local: other threads (RCCL's watchdog under torch.distributed) may issue HIP calls meanwhile
         with torch.cuda.graph(self.graph, pool=pool, capture_error_mode="thread_local"):
             self.loss, self.risk = self._body(flush=not self.split)
@@ -200,5 +204,8 @@ class GraphedWindowStep:
         return self.graph.pool()
 
     def __call__(self):
+        if self._fp32_window_version is not None and self.window[0].data._version != self._fp32_window_version:
+            raise RuntimeError("GraphedWindowStep: the fp32 window was written in place after capture; its feature scale "
+                               "is baked into the graph -- capture a new step for the new contents")
         self.graph.replay()
         return self.loss, self.risk

@@ -180,7 +180,7 @@ class MultimodalCoAttentionTransformer(_FusionModelBase):
         lin, co = self.H[0], self.co_attention
         out, amap, _, g_tok = ops.patch_coattn_mcat(bags.data, bags, lin.weight, lin.bias, self.H[2].p if self.training else 0.0,
                                                     g_bag.reshape(n_slides * n_q, e), co.in_proj_weight, co.in_proj_bias,
-                                                    co.out_proj.weight, co.out_proj.bias, inference, pair)
+                                                    co.out_proj.weight, co.out_proj.bias, inference, pair, _qpass_owned=True)
         return out.view(n_slides, n_q, e), (bags.split_map(amap, n_q) if inference else None), g_tok.view(n_slides, n_q, e)
 
     def forward(self, wsi, omics, inference: bool = False):

@@ -273,7 +273,24 @@ def coattn_mcat(query, batch: BagBatch, in_w, in_b, out_w, out_b, need_weights: 
     return CoAttnMCATFn.apply(query, batch.data, in_w, in_b, out_w, out_b, batch, need_weights, bag_relu_gate)
 
 
-stats = {"colsum_handoffs": 0}           # counters the tests read to make sure a fused path really ran
+# counters the tests read to make sure a fused path really ran.  qpass_*: how a hand-on op's backward (the query handed on
+# by patch_coattn_mcat / coattn_nacagat / contextual_gate) met the gradient of that query -- accumulated in place on a
+# buffer the caller's wiring owns, or on a copy (see _query_grad_buffer)
+stats = {"colsum_handoffs": 0, "qpass_in_place": 0, "qpass_copied": 0}
+
+
+def _query_grad_buffer(d_qpass, owned: bool, query):
+    """-> (where a hand-on op's backward writes d_query, accumulate flag).  The kernels accumulate d_query onto the gradient
+    of the handed-on query.  Autograd may share that tensor with other consumers (an add's two inputs, a tensor hook,
+    the op's own other output), so the sum goes in place only when the caller's wiring owns the buffer (`owned`: the
+    TokenPair slice the model's window step hands in); otherwise it goes onto a copy."""
+    if d_qpass is None:
+        return torch.empty_like(query), False
+    if owned:
+        stats["qpass_in_place"] += 1
+        return d_qpass.contiguous(), True
+    stats["qpass_copied"] += 1
+    return d_qpass.clone(memory_format=torch.contiguous_format), True
 
 
 def _bias_grad_slot(bag_param, E, dev):
@@ -430,17 +447,27 @@ def feature_scale(x) -> float:
     """The power of two that puts max |x| of an fp32 patch matrix into [2^14, 2^15): the fp16 operand splits of
     mpo_patch_fc_f32_forward then use fp16's range whatever the features' own scale (1e-4 or 1e4).  One reduction over the
     window and one host read, cached on the tensor (a resident window is scanned once; call it -- or one eager forward --
-    before capturing a graph)."""
-    s = getattr(x, "_mpo_feature_scale", None)
-    if s is None:
-        if x.numel() == 0:
-            return 1.0
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("feature_scale(x) needs one host read: call ops.feature_scale(window.data) before capturing the graph")
-        m = float(x.detach().abs().amax())
-        s = math.ldexp(1.0, max(-100, min(100, 15 - math.frexp(m)[1]))) if (m > 0.0 and math.isfinite(m)) else 1.0
+    before capturing a graph).
+
+    The cache is keyed on the tensor's version counter, storage address and shape: an in-place write (mul_, copy_, a write
+    through any view of the same base -- views share the counter) makes the next call scan again.  Inference tensors have
+    no version counter and are scanned on every call."""
+    if x.numel() == 0:
+        return 1.0
+    try:
+        key = (x._version, x.data_ptr(), tuple(x.shape))
+    except RuntimeError:                                # inference tensor: no version counter, nothing to key a cache on
+        key = None
+    cached = getattr(x, "_mpo_feature_scale", None) if key is not None else None
+    if cached is not None and cached[:3] == key:
+        return cached[3]
+    if x.is_cuda and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("feature_scale(x) needs one host read: call ops.feature_scale(window.data) before capturing the graph")
+    m = float(x.detach().abs().amax())
+    s = math.ldexp(1.0, max(-100, min(100, 15 - math.frexp(m)[1]))) if (m > 0.0 and math.isfinite(m)) else 1.0
+    if key is not None:
         try:
-            x._mpo_feature_scale = s
+            x._mpo_feature_scale = (*key, s)
         except AttributeError:
             pass
     return s
@@ -465,7 +492,7 @@ class PatchCoAttnMCATFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, patch_w, patch_b, query, in_w, in_b, out_w, out_b, batch: BagBatch, need_weights: bool, drop_p: float,
-                tokens: "TokenPair | None" = None):
+                tokens: "TokenPair | None" = None, qpass_owned: bool = False):
         lib = L.lib()
         ctx.set_materialize_grads(False)
         n_slides = batch.n_slides
@@ -488,6 +515,7 @@ class PatchCoAttnMCATFn(torch.autograd.Function):
         ctx.param_refs = (patch_w, patch_b, in_w, in_b, out_w, out_b)
         ctx.batch, ctx.n_q = batch, n_q
         ctx.gate = 1.0 / (1.0 - _realised_drop(drop_p)) if drop_p > 0 else 1.0
+        ctx.qpass_owned = bool(qpass_owned)
         ctx.mark_non_differentiable(h_bag)
         # the query handed on to its second consumer (the omic branch's tokens): its gradient then arrives HERE and is
         # folded into the last GEMM of the backward (d_query += ...) instead of costing autograd an add launch
@@ -502,8 +530,7 @@ class PatchCoAttnMCATFn(torch.autograd.Function):
         dev = query.device
         d_out = d_out.contiguous() if d_out is not None else torch.zeros(R, E, device=dev)
         d_map = d_map.contiguous() if d_map is not None else None
-        accumulate = d_qpass is not None
-        d_query = d_qpass.contiguous() if accumulate else torch.empty_like(query)    # (in place on the incoming gradient)
+        d_query, accumulate = _query_grad_buffer(d_qpass, ctx.qpass_owned, query)
         g = torch.empty_like(h_bag)               # d(pre-activation of the patch layer): ReLU/dropout derivative applied in-kernel
         patch_w, patch_b, p_in_w, p_in_b, p_out_w, p_out_b = ctx.param_refs
         d_pw, d_pb = grad_out(patch_w), grad_out(patch_b)
@@ -520,7 +547,7 @@ class PatchCoAttnMCATFn(torch.autograd.Function):
             _deferred_patch.append((g, x, d_pw))   # filled by flush_patch_weight_grads() (data-parallel split exchange)
         else:
             patch_weight_grad(g, x, d_pw)
-        return None, d_pw, d_pb, d_query, d_in_w, d_in_b, d_out_w, d_out_b, None, None, None, None
+        return None, d_pw, d_pb, d_query, d_in_w, d_in_b, d_out_w, d_out_b, None, None, None, None, None
 
 
 class TokenPair:
@@ -558,12 +585,13 @@ def _realised_drop(p: float) -> float:
 
 
 def patch_coattn_mcat(x_bf16, batch: BagBatch, patch_w, patch_b, drop_p: float, query, in_w, in_b, out_w, out_b,
-                      need_weights: bool, tokens: "TokenPair | None" = None):
+                      need_weights: bool, tokens: "TokenPair | None" = None, _qpass_owned: bool = False):
     """-> (out (n_slides*n_q, E), ragged map | None, H_bag (rows, E) bf16, not differentiable, query handed on).
     tokens: `out` is produced into tokens.slot(0).  Use the returned query (not the argument) for the query's other
-    consumer: its gradient is then folded into this op's backward."""
+    consumer: its gradient is then folded into this op's backward.  _qpass_owned (the model's TokenPair wiring only): the
+    gradient arriving for the handed-on query is a buffer nobody else reads, so the backward may accumulate into it."""
     return PatchCoAttnMCATFn.apply(x_bf16, patch_w, patch_b, query, in_w, in_b, out_w, out_b, batch, need_weights,
-                                   float(drop_p), tokens)
+                                   float(drop_p), tokens, bool(_qpass_owned))
 
 
 def fused_patch_coattn_supported(x, embed: int, n_q: int) -> bool:
@@ -620,7 +648,7 @@ class CagFn(torch.autograd.Function):
     backward's d_q product accumulates onto it (no gradient-add launch)."""
 
     @staticmethod
-    def forward(ctx, q, q_hat, residual, dest, *params):
+    def forward(ctx, q, q_hat, residual, dest, qpass_owned, *params):
         lib = L.lib()
         ctx.set_materialize_grads(False)
         q, q_hat = q.contiguous(), q_hat.contiguous()
@@ -639,6 +667,7 @@ class CagFn(torch.autograd.Function):
         ctx.save_for_backward(q, q_hat, c, saved, *params)
         ctx.param_refs = params
         ctx.has_residual = residual is not None
+        ctx.qpass_owned = bool(qpass_owned)
         return (total if total is not None else c), q.view_as(q)
 
     @staticmethod
@@ -650,8 +679,7 @@ class CagFn(torch.autograd.Function):
         if dc is None:
             dc = torch.zeros_like(c)
         dc = dc.contiguous()
-        accumulate = d_qpass is not None
-        dq = d_qpass.contiguous() if accumulate else torch.empty_like(q)      # (in place on the incoming gradient)
+        dq, accumulate = _query_grad_buffer(d_qpass, ctx.qpass_owned, q)
         dqh = torch.empty_like(q_hat)
         grads = [grad_out(p) for p in ctx.param_refs]
         ws = _workspace(lib.mpo_cag_workspace_bytes(rows, hidden), q.device)
@@ -659,13 +687,14 @@ class CagFn(torch.autograd.Function):
         L.check(lib.mpo_cag_backward(L.ptr(q), L.ptr(q_hat), rows, dim, hidden, pa, L.ptr(saved), L.ptr(c),
                                      L.ptr(dc), L.ptr(dq), int(accumulate), L.ptr(dqh), ga, L.ptr(ws), ws.numel(),
                                      L.stream_of(q)), "mpo_cag_backward")
-        return (dq, dqh, dc if ctx.has_residual else None, None, *grads)
+        return (dq, dqh, dc if ctx.has_residual else None, None, None, *grads)
 
 
-def contextual_gate(q, q_hat, cag, residual=None, dest=None, hand_on: bool = False):
+def contextual_gate(q, q_hat, cag, residual=None, dest=None, hand_on: bool = False, _qpass_owned: bool = False):
     """C = CAG(q, q_hat); with `residual`: residual + C (into slot dest[1] of the TokenPair dest[0] when given).  hand_on: also returns q for its other
-    consumers (use THAT tensor there: their gradient is then folded into this op's backward)."""
-    out, q_pass = CagFn.apply(q, q_hat, residual, dest, cag.fc1[0].weight, cag.fc1[0].bias, cag.fc2[0].weight, cag.fc2[0].bias,
+    consumers (use THAT tensor there: their gradient is then folded into this op's backward).  _qpass_owned: see
+    patch_coattn_mcat."""
+    out, q_pass = CagFn.apply(q, q_hat, residual, dest, bool(_qpass_owned), cag.fc1[0].weight, cag.fc1[0].bias, cag.fc2[0].weight, cag.fc2[0].bias,
                               cag.fc3[0].weight, cag.fc3[0].bias, cag.G[1].weight, cag.G[1].bias,
                               cag.E[1].weight, cag.E[1].bias, cag.fc_c[0].weight, cag.fc_c[0].bias)
     return (out, q_pass) if hand_on else out
@@ -1176,7 +1205,8 @@ class CoAttnNaCAGaTFn(torch.autograd.Function):
     also for a bf16-stored bag: the gate multiplies k's rounding error (hard part 4)."""
 
     @staticmethod
-    def forward(ctx, query, bag_data, in_w, in_b, out_w, out_b, batch: BagBatch, drop_p: float, bag_relu_gate: float = 0.0):
+    def forward(ctx, query, bag_data, in_w, in_b, out_w, out_b, batch: BagBatch, drop_p: float, bag_relu_gate: float = 0.0,
+                qpass_owned: bool = False):
         lib = L.lib()
         n_slides = batch.n_slides
         R, E = query.shape
@@ -1228,6 +1258,7 @@ class CoAttnNaCAGaTFn(torch.autograd.Function):
         ctx.hb = hb if big else None                  # (the split-halves copy of the bag: kept for the backward)
         ctx.param_refs = (in_w, in_b, out_w, out_b)
         ctx.batch, ctx.n_q, ctx.drop = batch, n_q, (float(drop_p), seed, offset)
+        ctx.qpass_owned = bool(qpass_owned)
         # (4th output: the query handed on to its other consumers -- NaCAGaT's CAG and the omic branch's tokens; their gradient
         #  arrives here and the backward's d_query product accumulates onto it)
         return q_proj, out, amap, query.view_as(query)
@@ -1243,8 +1274,7 @@ class CoAttnNaCAGaTFn(torch.autograd.Function):
         d_out = d_out.contiguous() if d_out is not None else torch.zeros(R, E, device=dev)
         d_qproj = d_qproj.contiguous() if d_qproj is not None else None
         d_map = d_map.contiguous() if d_map is not None else None
-        accumulate = d_qpass is not None
-        d_query = d_qpass.contiguous() if accumulate else torch.empty_like(query)      # (in place on the incoming gradient)
+        d_query, accumulate = _query_grad_buffer(d_qpass, ctx.qpass_owned, query)
         d_k = torch.empty_like(kbag, dtype=bag_data.dtype)       # a bf16 bag takes its key gradient in bf16 (see below)
         # bf16 bag: the patch-side gradient is finished by ONE pass after the dK W_k GEMM (mpo_nacagat_patch_grad) instead
         # of outer-product kernel -> addmm_ read-modify-write -> element-wise derivative pass
@@ -1304,13 +1334,14 @@ class CoAttnNaCAGaTFn(torch.autograd.Function):
             L.check(lib.mpo_linear_backward_weight(L.ptr(d_k), L.ptr(bag_data), L.ptr(d_in_w[E:2 * E]), None, T, E, E, 1.0, s_),
                     "mpo_linear_backward_weight")
         # (d_in_b[E:2E], the key bias gradient = column sums of d_k, came out of the kernel that wrote d_k)
-        return d_query, d_h, d_in_w, d_in_b, d_out_w, d_out_b, None, None, None
+        return d_query, d_h, d_in_w, d_in_b, d_out_w, d_out_b, None, None, None, None
 
 
 def coattn_nacagat(query, batch: BagBatch, in_w, in_b, out_w, out_b, drop_p: float, bag_relu_gate: float = 0.0,
-                   hand_on: bool = False):
+                   hand_on: bool = False, _qpass_owned: bool = False):
     """query (n_slides*n_q, E) -> (q_proj, attn_out (n_slides*n_q, E), ragged post-dropout map[, query handed on]).
     bag_relu_gate = 1/(1-p) when the bag comes from patch_fc(..., pre_gated_grad=True): d_bag then already carries
-    that layer's ReLU/dropout derivative (bf16 bags only).  hand_on: a 4th result, the query for its other consumers."""
-    res = CoAttnNaCAGaTFn.apply(query, batch.data, in_w, in_b, out_w, out_b, batch, drop_p, bag_relu_gate)
+    that layer's ReLU/dropout derivative (bf16 bags only).  hand_on: a 4th result, the query for its other consumers.
+    _qpass_owned: see patch_coattn_mcat."""
+    res = CoAttnNaCAGaTFn.apply(query, batch.data, in_w, in_b, out_w, out_b, batch, drop_p, bag_relu_gate, bool(_qpass_owned))
     return res if hand_on else res[:3]

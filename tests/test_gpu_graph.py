@@ -97,3 +97,25 @@ def test_split_step_fills_the_same_bucket(dev, kind):
     torch.testing.assert_close(bucket_b.flat, ref, rtol=0, atol=0)
     assert not ops._deferred_patch
     ops.set_rng_epoch(None)
+
+
+def test_graph_refuses_an_fp32_window_written_after_capture(dev):
+    """An fp32 window's feature scale (ops.feature_scale, one host read) is a kernel argument baked into the graph: a
+    replay after an in-place write to that window would compute with the stale scale, so it must raise instead.  The
+    check is a host-side compare of the window's version counter; bf16 windows carry no such scale."""
+    ops.set_rng_epoch(None)
+    model, bucket, _, window = setup(dev, False, torch.float32)
+    step = harness.GraphedWindowStep(model, bucket, window, 6, opt=None, warmup=1, prime=False)
+    loss, _ = step()
+    assert torch.isfinite(loss).all()
+    window[0].data.copy_(window[0].data * 50.0)
+    with pytest.raises(RuntimeError, match="written in place after capture"):
+        step()
+    ops.set_rng_epoch(None)
+    model, bucket, _, window = setup(dev, False, torch.bfloat16)
+    step = harness.GraphedWindowStep(model, bucket, window, 6, opt=None, warmup=1, prime=False)
+    window[0].data.mul_(1.0)
+    loss, _ = step()                                       # (bf16: nothing frozen from the window's contents)
+    assert torch.isfinite(loss).all()
+    torch.cuda.synchronize()
+    ops.set_rng_epoch(None)

@@ -108,3 +108,45 @@ def test_other_geometries_are_not_claimed(dev):
     assert not ops.patch_fc_f32_supported(torch.empty(4, 1024, device=dev), torch.empty(128, 1024, device=dev))
     assert not ops.patch_fc_f32_supported(torch.empty(4, 1024, device=dev, dtype=torch.bfloat16), torch.empty(256, 1024, device=dev))
     assert ops.patch_fc_f32_supported(torch.empty(4, 1024, device=dev), torch.empty(256, 1024, device=dev))
+
+
+def _window_change(kind, x, base, gen):
+    """An in-place change of the window -> the gain by which its features (and, to keep the ReLU mask alive, the bias)
+    moved.  x is a view of `base` (rows past x hold NaN)."""
+    if kind == "mul_100":
+        x.mul_(100.0)
+        return 100.0
+    if kind == "mul_1e-3":
+        x.mul_(1e-3)
+        return 1e-3
+    if kind == "copy_50x":
+        x.copy_(torch.randn(x.shape, device=x.device, generator=gen) * 50.0)
+        return 50.0
+    if kind == "write_through_base":                # a view of x's base: views share the version counter
+        base[3:x.shape[0]:7].mul_(100.0)          # (every 7th row: the window's maximum moves 100x)
+        return 100.0
+    raise ValueError(kind)
+
+
+@pytest.mark.parametrize("kind", ["mul_100", "mul_1e-3", "copy_50x", "write_through_base"])
+def test_forward_after_an_in_place_change_of_the_window_rescales(dev, kind):
+    """feature_scale() is cached on the window tensor.  A second forward on the SAME tensor object after an
+    in-place change must not reuse the first scale: features past ~2-4x the cached maximum were clamped to fp16's 65504 in
+    the operand splits (finite, wrong, no error).  Both forwards against fp64 at the operand-scale test's bar."""
+    rows = 3000
+    x0, w, b, gen = _operands(rows, dev, 81)
+    base = torch.full((rows + 16, 1024), float("nan"), device=dev)
+    x = base[:rows]
+    x.copy_(x0)
+    wp = torch.nn.Parameter(w)
+    h = ops.patch_fc_f32(x, wp, torch.nn.Parameter(b), 0.0)
+    ref = torch.relu(x.double() @ w.double().t() + b.double())
+    err = float((h.double() - ref).abs().max() / ref.abs().max())
+    assert err < 3e-6, err
+    gain = _window_change(kind, x, base, gen)
+    b2 = b * gain
+    h = ops.patch_fc_f32(x, wp, torch.nn.Parameter(b2), 0.0)
+    ref = torch.relu(x.double() @ w.double().t() + b2.double())
+    err = float((h.double() - ref).abs().max() / ref.abs().max())
+    assert err < 3e-6, (kind, err)
+    assert float((h > 0).ne(ref > 0).float().mean()) < 2e-5

@@ -79,3 +79,36 @@ def test_geometries_the_kernel_is_not_built_for_raise(dev, embed, patch_dim):
     x = torch.zeros(3000, patch_dim, device=dev, dtype=torch.bfloat16)
     with pytest.raises(ValueError, match="patch weight gradient"):
         ops.patch_weight_grad(g, x, torch.empty(embed, patch_dim, device=dev))
+
+
+@pytest.mark.parametrize("rows", [1, 33, 2049, 48001])
+@pytest.mark.parametrize("workgroups", [32, 224])
+def test_fewer_workgroups_give_the_same_product(dev, monkeypatch, rows, workgroups):
+    """A data-parallel step runs this kernel on 224 workgroups (bench.py N > 1: CUs left to the all-reduce beside it);
+    32 is the fewest the launch accepts at patch_dim 1024 (8 row ranges).  Fewer row ranges, longer per range: the same
+    product, the same bar."""
+    monkeypatch.setattr(ops, "wgrad_workgroups", workgroups)
+    gen = torch.Generator(device=dev).manual_seed(rows + workgroups)
+    gbuf = torch.full((rows + 64, 256), float("nan"), device=dev, dtype=torch.bfloat16)
+    xbuf = torch.full((rows + 64, 1024), float("nan"), device=dev, dtype=torch.bfloat16)
+    g, x = gbuf[:rows], xbuf[:rows]
+    g.copy_(torch.randn(rows, 256, device=dev, generator=gen) * (torch.rand(rows, 256, device=dev, generator=gen) > 0.3))
+    x.copy_(torch.randn(rows, 1024, device=dev, generator=gen))
+    out = torch.full((256, 1024), float("nan"), device=dev)
+    ops.patch_weight_grad(g, x, out)
+    ref = _ref(g, x)
+    err = float((out.double() - ref).abs().max() / ref.abs().max().clamp_min(1e-30))
+    assert err < 2e-6, err
+
+
+def test_invalid_workgroup_count_is_refused(dev, monkeypatch):
+    """A count that is not a multiple of 8 row ranges x 4 column blocks (patch_dim 1024) is refused by the C ABI's check,
+    before anything is launched: the output keeps its contents."""
+    monkeypatch.setattr(ops, "wgrad_workgroups", 100)
+    g = torch.ones(64, 256, device=dev, dtype=torch.bfloat16)
+    x = torch.ones(64, 1024, device=dev, dtype=torch.bfloat16)
+    out = torch.full((256, 1024), 7.0, device=dev)
+    with pytest.raises(RuntimeError, match="workgroups must be 0 or a multiple of 32"):
+        ops.patch_weight_grad(g, x, out)
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all())

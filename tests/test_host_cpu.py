@@ -178,3 +178,43 @@ def test_empty_slides_are_refused():
         BagBatch.from_lengths(x, [5, 0])
     with pytest.raises(ValueError):
         BagBatch.from_lengths(x, [3, 3])
+
+
+def test_feature_scale_cache_follows_in_place_writes():
+    """ops.feature_scale caches the fp32 window's power-of-two scale on the tensor, keyed on its version counter, storage
+    and shape: any in-place write -- on the tensor, through a view of its base -- or a new storage makes the next call
+    scan again; an inference tensor (no version counter) is scanned on every call."""
+    import torch
+    from multimodal_path_omic_amd import ops
+
+    def fresh(t):
+        m = float(t.abs().max())
+        return 2.0 ** (15 - np.frexp(m)[1])
+
+    base = torch.randn(40, 1024)
+    x = base[:32]
+    s0 = ops.feature_scale(x)
+    assert s0 == fresh(x) and x._mpo_feature_scale[3] == s0
+    assert ops.feature_scale(x) == s0                      # cached: same version, storage, shape
+    x.mul_(100.0)
+    assert ops.feature_scale(x) == fresh(x) != s0
+    x.mul_(1e-3)
+    assert ops.feature_scale(x) == fresh(x)
+    x.copy_(torch.randn(32, 1024) * 50.0)
+    assert ops.feature_scale(x) == fresh(x)
+    s1 = ops.feature_scale(x)
+    base[3:32:7].mul_(1000.0)                              # a write through another view of the same base
+    assert ops.feature_scale(x) == fresh(x) != s1
+    x.data = torch.randn(32, 1024) * 1e-4                  # new storage, no in-place op on x
+    assert ops.feature_scale(x) == fresh(x)
+    x.data = torch.randn(16, 1024)                         # new shape
+    assert ops.feature_scale(x) == fresh(x)
+    with torch.inference_mode():
+        xi = torch.randn(8, 1024)
+    assert ops.feature_scale(xi) == fresh(xi)
+    assert getattr(xi, "_mpo_feature_scale", None) is None  # nothing cached on an inference tensor
+    with torch.inference_mode():
+        xi.mul_(1e4)
+    assert ops.feature_scale(xi) == fresh(xi)
+    assert ops.feature_scale(torch.zeros(4, 1024)) == 1.0
+    assert ops.feature_scale(torch.empty(0, 1024)) == 1.0
