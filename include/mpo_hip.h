@@ -322,7 +322,9 @@ int mpo_nacagat_patch_grad_fused(const int32_t* cu_rows, int n_slides, int total
  * n_branches (1..4) batches that many independent encoders of IDENTICAL geometry -- the model's path_transformer
  * and omic_transformer -- into one launch sequence: x, y are [n_branches][n_slides*T][d], params / grads hold
  * n_branches * layers * 12 pointers (branch-major), and the *_floats / *_bytes / rng_span queries take
- * n_branches * n_slides as their n_slides.  The token tail is launch-latency-bound, so the second branch is free. */
+ * n_branches * n_slides as their n_slides.  The token tail is launch-latency-bound, so the second branch is free.
+ * With dropout on and T <= 16 the forward refuses heads * T > max(ff, 3 d): the attention mask's stream would overlap
+ * the next one. */
 size_t mpo_encoder_saved_floats(int n_slides, int T, int d, int ff, int heads, int layers);
 size_t mpo_encoder_workspace_bytes(int n_slides, int T, int d, int ff);
 uint64_t mpo_encoder_rng_span(int n_slides, int T, int d, int ff, int layers);

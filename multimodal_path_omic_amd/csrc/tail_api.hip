@@ -144,6 +144,11 @@ int mpo_encoder_forward(const float* x, int n_branches, int n_slides, int T, int
     MPO_CHECK(n_slides >= 1 && layers >= 1 && d % heads == 0, "encoder: bad geometry (slides %d, layers %d, d %d, heads %d)",
               n_slides, layers, d, heads);
     MPO_CHECK(n_branches >= 1 && n_branches <= kMaxBranches, "encoder: 1..%d branches (got %d)", kMaxBranches, n_branches);
+    // the token tail's attention mask draws heads * T counters per token row from stream slot 0, which is only
+    // max(ff, 3 d) counters per row wide: more heads would run into the out-proj mask's slot (the long-T path hashes)
+    MPO_CHECK(drop_p <= 0.f || T > kSmallAttnMaxT || (uint64_t)heads * T <= (uint64_t)(ff > 3 * d ? ff : 3 * d),
+              "encoder: heads * T = %d * %d exceeds max(ff, 3 d) = %d: the attention dropout stream would overlap the next one",
+              heads, T, ff > 3 * d ? ff : 3 * d);
     const int NB = n_branches, R = n_slides * T, RT = NB * R, BT = NB * n_slides;
     const uint64_t stride = enc_stream_stride(BT, T, d, ff);
     Carver c(saved);

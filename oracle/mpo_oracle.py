@@ -60,7 +60,7 @@ def patch_fc(wsi, p, prefix="H", keep=None, storage=None, round_gemm_out=True, s
     storage_points: which of the three storage points are rounded -- "x" the patch matrix, "w" the weight operand,
     "h" H_bag (and the GEMM output under round_gemm_out) -- so a test can attribute a bf16-mode error to each of them."""
     x = wsi.squeeze(0) if wsi.dim() == 3 else wsi
-    x = _store(x.float(), storage if "x" in storage_points else None)
+    x = _store(x.to(p[prefix + ".0.weight"].dtype), storage if "x" in storage_points else None)   # fp32 unless fp64 params
     h = x @ _store(p[prefix + ".0.weight"], storage if "w" in storage_points else None).t()
     st_h = storage if "h" in storage_points else None
     if round_gemm_out:
@@ -69,13 +69,25 @@ def patch_fc(wsi, p, prefix="H", keep=None, storage=None, round_gemm_out=True, s
     return h if keep is None else h * keep
 
 
-def omic_fc(omics, p, prefix="G"):
-    """Per-group SNN: 2 x (Linear + ELU [+ AlphaDropout]); models/mcat/mcat.py:32-45,90-92."""
+def _alpha_dropout(x, keep, drop_p):
+    """nn.AlphaDropout(drop_p) with a given boolean keep mask: a * (keep ? x : alpha') + b."""
+    alpha_p = -1.7580993408473766
+    a = 1.0 / math.sqrt((1.0 - drop_p) * (1.0 + drop_p * alpha_p * alpha_p))
+    return a * torch.where(torch.as_tensor(keep, dtype=torch.bool), x, torch.full_like(x, alpha_p)) - a * alpha_p * drop_p
+
+
+def omic_fc(omics, p, prefix="G", ad_keeps=None, drop_p=0.25):
+    """Per-group SNN: 2 x (Linear + ELU [+ AlphaDropout]); models/mcat/mcat.py:32-45,90-92.
+    ad_keeps: per group a pair of boolean keep masks (True = kept) for the two AlphaDropout(drop_p) sites."""
     rows = []
     for i, o in enumerate(omics):
-        x = o.float().reshape(1, -1)
+        x = o.reshape(1, -1).to(p[f"{prefix}.{i}.0.0.weight"].dtype)      # fp32 params: o.float(); fp64: the fp64 oracle
         x = _elu(_lin(x, p, f"{prefix}.{i}.0.0"))
+        if ad_keeps is not None:
+            x = _alpha_dropout(x, ad_keeps[i][0].reshape(x.shape), drop_p)
         x = _elu(_lin(x, p, f"{prefix}.{i}.1.0"))
+        if ad_keeps is not None:
+            x = _alpha_dropout(x, ad_keeps[i][1].reshape(x.shape), drop_p)
         rows.append(x)
     return torch.cat(rows, 0)                                   # (N, d)
 
@@ -141,9 +153,13 @@ def pregating_contextual_attention(query, bag, p, prefix="co_attention", keep=No
 
 
 # --------------------------------------------------------------------------- H6
-def encoder_layer(x, p, prefix, nhead=8):
+def encoder_layer(x, p, prefix, nhead=8, keeps=None):
     """One post-norm nn.TransformerEncoderLayer (torch/nn/modules/transformer.py:661,
-    norm_first=False), ReLU FFN, dropout off.  x: (T, d) one slide, or (B, T, d)."""
+    norm_first=False), ReLU FFN, dropout off.  x: (T, d) one slide, or (B, T, d).
+    keeps: None, or the layer's four pre-scaled keep masks (attn, out, ff, ff_out) in the positions the stock layer
+    drops out: self_attn's attention probabilities (..., h, T, T), dropout1 on the out_proj output before the residual
+    add (..., T, d), the FFN's dropout after ReLU (..., T, ff), dropout2 on linear2's output (..., T, d)."""
+    k_attn, k_out, k_ff, k_ff2 = keeps if keeps is not None else (None,) * 4
     d = x.shape[-1]
     hd = d // nhead
     w, b = p[prefix + ".self_attn.in_proj_weight"], p[prefix + ".self_attn.in_proj_bias"]
@@ -154,18 +170,29 @@ def encoder_layer(x, p, prefix, nhead=8):
         return t.reshape(*t.shape[:-1], nhead, hd).transpose(-2, -3)
 
     s = heads(q) @ heads(k).transpose(-1, -2) / math.sqrt(hd)
-    o = torch.softmax(s, -1) @ heads(v)                         # (..., h, T, hd)
+    a = torch.softmax(s, -1)
+    if k_attn is not None:
+        a = a * k_attn
+    o = a @ heads(v)                                            # (..., h, T, hd)
     o = o.transpose(-2, -3).reshape(x.shape)
-    x = _layer_norm(x + _lin(o, p, prefix + ".self_attn.out_proj"),
-                    p[prefix + ".norm1.weight"], p[prefix + ".norm1.bias"])
-    f = _lin(torch.relu(_lin(x, p, prefix + ".linear1")), p, prefix + ".linear2")
+    o = _lin(o, p, prefix + ".self_attn.out_proj")
+    if k_out is not None:
+        o = o * k_out
+    x = _layer_norm(x + o, p[prefix + ".norm1.weight"], p[prefix + ".norm1.bias"])
+    f = torch.relu(_lin(x, p, prefix + ".linear1"))
+    if k_ff is not None:
+        f = f * k_ff
+    f = _lin(f, p, prefix + ".linear2")
+    if k_ff2 is not None:
+        f = f * k_ff2
     return _layer_norm(x + f, p[prefix + ".norm2.weight"], p[prefix + ".norm2.bias"])
 
 
-def set_transformer(x, p, prefix, num_layers=2, nhead=8):
-    """nn.TransformerEncoder(num_layers=2), no final norm; models/mcat/mcat.py:51-53,101-102."""
+def set_transformer(x, p, prefix, num_layers=2, nhead=8, keeps=None):
+    """nn.TransformerEncoder(num_layers=2), no final norm; models/mcat/mcat.py:51-53,101-102.
+    keeps: None, or per layer the four keep masks of encoder_layer."""
     for i in range(num_layers):
-        x = encoder_layer(x, p, f"{prefix}.layers.{i}", nhead)
+        x = encoder_layer(x, p, f"{prefix}.layers.{i}", nhead, keeps[i] if keeps is not None else None)
     return x
 
 
@@ -181,13 +208,14 @@ def gated_attention_scores(x, p, prefix, keep_a=None, keep_b=None):
     return _lin(a * b, p, prefix + ".attention_c")
 
 
-def gated_mil_pool(x, p, head_prefix, rho_prefix):
-    """Pooling idiom models/mcat/mcat.py:105-109: A^T, softmax over L, mm, rho (Linear+ReLU).
+def gated_mil_pool(x, p, head_prefix, rho_prefix, keep_a=None, keep_b=None, keep_rho=None):
+    """Pooling idiom models/mcat/mcat.py:105-109: A^T, softmax over L, mm, rho (Linear+ReLU+Dropout).
+    keep_a / keep_b (L, d): the scorer's two dropouts; keep_rho (d,): rho's dropout (pre-scaled keep masks).
     Returns (A (1,L) raw scores, h (d,))."""
-    a = gated_attention_scores(x, p, head_prefix).t()           # (1, L)
+    a = gated_attention_scores(x, p, head_prefix, keep_a, keep_b).t()     # (1, L)
     h = torch.softmax(a, dim=1) @ x                             # (1, d)
     h = torch.relu(_lin(h, p, rho_prefix + ".0")).squeeze()
-    return a, h
+    return a, (h if keep_rho is None else h * keep_rho.reshape(h.shape))
 
 
 # --------------------------------------------------------------------------- H8
@@ -264,25 +292,32 @@ def nacagat_forward(p, wsi, omics, bag_storage=None, round_gemm_out=False, stora
 
 
 # --------------------------------------------------------------------------- f3
-def bag_self_attention(x, p, prefix="self_attention", nhead=1):
+def bag_self_attention(x, p, prefix="self_attention", nhead=1, keep=None):
     """nn.MultiheadAttention(embed, num_heads)(x, x, x) on the unbatched (M, d) bag, dropout off
-    (models/ge_nacagat/ge_nacagat.py:27,49).  Returns (output (M, d), map averaged over heads (M, M))."""
+    (models/ge_nacagat/ge_nacagat.py:27,49).  Returns (output (M, d), map averaged over heads (M, M)).
+    keep (h, M, M): a pre-scaled attention-dropout mask; the returned map is then the dropped-out one, as the stock
+    module returns it."""
     m, d = x.shape
     hd = d // nhead
     qkv = x @ p[prefix + ".in_proj_weight"].t() + p[prefix + ".in_proj_bias"]
     q, k, v = (qkv[:, i * d:(i + 1) * d].reshape(m, nhead, hd).transpose(0, 1) for i in range(3))   # (h, M, hd)
     a = torch.softmax(q @ k.transpose(1, 2) / math.sqrt(hd), dim=-1)                                 # (h, M, M)
+    if keep is not None:
+        a = a * keep
     o = (a @ v).transpose(0, 1).reshape(m, d)
     return _lin(o, p, prefix + ".out_proj"), a.mean(0)
 
 
-def ge_nacagat_forward(p, wsi, bag_storage=None, round_gemm_out=False):
+def ge_nacagat_forward(p, wsi, bag_storage=None, round_gemm_out=False, keep_h=None, keep_sa=None, enc_keeps=None,
+                       pool_keeps=None):
     """GeneExprNarrowContextualAttentionGateTransformer.forward, models/ge_nacagat/ge_nacagat.py:43-72 (eval mode):
-    Y (n_classes,) = softmax over the classifier logits, {'attn': (M, M), 'path': (1, M) raw pooling scores}."""
-    h_bag = patch_fc(wsi, p, storage=bag_storage, round_gemm_out=round_gemm_out)
-    h_co, a_co = bag_self_attention(h_bag, p)
-    path = set_transformer(h_co, p, "path_transformer")
-    a_path, h_path = gated_mil_pool(path, p, "path_attention_head", "path_rho")
+    Y (n_classes,) = softmax over the classifier logits, {'attn': (M, M), 'path': (1, M) raw pooling scores}.
+    Training mode with given masks: keep_h (M, d) the patch layer's dropout, keep_sa (1, M, M) the self-attention's,
+    enc_keeps the set-Transformer's (see set_transformer), pool_keeps (keep_a, keep_b, keep_rho) the pooling head's."""
+    h_bag = patch_fc(wsi, p, keep=keep_h, storage=bag_storage, round_gemm_out=round_gemm_out)
+    h_co, a_co = bag_self_attention(h_bag, p, keep=keep_sa)
+    path = set_transformer(h_co, p, "path_transformer", keeps=enc_keeps)
+    a_path, h_path = gated_mil_pool(path, p, "path_attention_head", "path_rho", *(pool_keeps or ()))
     logits = _lin(h_path, p, "classifier")
     return torch.softmax(logits, dim=0), {"attn": a_co, "path": a_path}
 
