@@ -199,6 +199,28 @@ int mpo_adam_step_flat(float* params, const float* grads, float* exp_avg, float*
                        const int32_t* step_dev /* nullable: device-resident step count, overrides `step` */,
                        mpo_stream_t stream);
 
+/* ---- the other training.optimizer choices (models/mcat/main.py:284-300) and the L1 penalty (training.lambda, models/utils.py:33-40;
+ * main.py:51-54,69).  Additive to ABI 14: the entries below are new, no earlier entry changed, mpo_abi_version() stays 14.
+ * One pass over flat fp32 buffers, torch.optim 2.x single-tensor arithmetic in fp32, with the gradient
+ *   g' = g + l1 sign(p) + weight_decay p          (sign(0) = 0; l1 = lambda * slides of the window over all ranks)
+ *   MPO_OPTIM_ADAM      state1 = exp_avg, state2 = exp_avg_sq: mpo_adam_step_flat's update
+ *   MPO_OPTIM_ADAMAX    state1 = exp_avg, state2 = exp_inf: m = lerp(m, g', 1-b1); u = max(b2 u, |g'| + eps);
+ *                       p -= lr/(1-b1^t) m/u
+ *   MPO_OPTIM_ADADELTA  state1 = square_avg, state2 = acc_delta, rho = beta1: v = rho v + (1-rho) g'^2;
+ *                       d = sqrt(a+eps)/sqrt(v+eps) g'; a = rho a + (1-rho) d^2; p -= lr d
+ *   MPO_OPTIM_SGD       no state (both NULL): p -= lr g'
+ * lr_dev (nullable, one device float) overrides lr and step_dev (nullable) overrides step, so that a captured step follows
+ * a learning-rate schedule and the bias correction.  Pointers must be 4-byte aligned; 16-byte aligned buffers take
+ * 16-byte accesses. */
+enum { MPO_OPTIM_ADAM = 0, MPO_OPTIM_ADAMAX = 1, MPO_OPTIM_ADADELTA = 2, MPO_OPTIM_SGD = 3 };
+int mpo_optim_step_flat(int algorithm, float* params, const float* grads, float* state1, float* state2, int64_t n, float lr,
+                        const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, float l1, int step,
+                        const int32_t* step_dev, mpo_stream_t stream);
+/* out[0] = sum_i |x_i| (one device float; the L1 penalty's value over a flat parameter buffer).  Deterministic: two
+ * launches (fixed per-block partials in the workspace, then one block adds them in order in fp64), no atomics. */
+size_t mpo_abs_sum_flat_workspace_bytes(int64_t n);
+int mpo_abs_sum_flat(const float* x, int64_t n, float* out, void* workspace, size_t workspace_bytes, mpo_stream_t stream);
+
 /* Verification hook (tests): the 6 x d token-tail products run a branch-free GEMM body when the product is regular
  * (whole 16 x 16 tiles, K % 64 == 0, aligned operands, a gate known at compile time) and a general body otherwise; the two
  * are bit-identical.  enabled = 0 sends everything through the general body.  Returns the previous setting (default 1). */
@@ -421,6 +443,23 @@ int mpo_fusion_head_loss_forward(const float* hcat, int n_slides, int din, int h
 int mpo_fusion_head_loss_backward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes,
                                   const float* const* params, const float* saved, float* d_hcat, float* const* grads,
                                   void* workspace, size_t workspace_bytes, mpo_stream_t stream);
+
+/* ---- the `sct` loss = SurvivalClassificationTobitLoss (models/loss.py:62-85) on Y = softmax(logits) (mcat.py:138), for
+ * n_slides slides at once, per-slide losses: uncensored -log(Y[y] + eps), censored -log(sum_{j>=y} Y[j] + eps).
+ * The backward gives d_y from the per-slide upstream gradient d_loss (n_slides floats), or ONE device float broadcast to all
+ * slides when d_loss_is_scalar.  Additive to ABI 14. */
+int mpo_sct_loss_forward(const float* y, const int64_t* label, const float* censorship, int n_slides, int n_classes,
+                         float eps, float* loss, mpo_stream_t stream);
+int mpo_sct_loss_backward(const float* y, const int64_t* label, const float* censorship, int n_slides, int n_classes,
+                          float eps, const float* d_loss, int d_loss_is_scalar, float* d_y, mpo_stream_t stream);
+/* Training-step K6 with the `sct` loss in place of `ces`: same arguments, saved layout and backward
+ * (mpo_fusion_head_loss_backward) as mpo_fusion_head_loss_forward.  Hazards and survs take no gradient; risk = -sum_j S_j.
+ * The gradient w.r.t. the logits is formed stably (Y[y] / (Y[y] + eps), 1 - P summed over the classes below the label).
+ * Additive to ABI 14. */
+int mpo_fusion_head_sct_loss_forward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes,
+                                     const float* const* params, const int64_t* label, const float* censorship,
+                                     const float* slide_weight, float eps, float* hazards, float* survs, float* y,
+                                     float* loss, float* risk /* nullable */, float* saved, mpo_stream_t stream);
 
 /* ---- K3: ContextualAttentionGate.forward (models/blocks.py:232-253) on rows of (Q, Q_hat).
  * 12 pointers: fc1.0.weight,.bias, fc2.0.weight,.bias, fc3.0.weight,.bias, G.1.weight,.bias, E.1.weight,.bias,

@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmpo_hip.so")
 
 MPO_F32, MPO_BF16 = 0, 1
+OPTIM = {"adam": 0, "adamax": 1, "adadelta": 2, "sgd": 3}      # MPO_OPTIM_* of include/mpo_hip.h
 
 
 class BagPlanC(ctypes.Structure):
@@ -102,6 +103,13 @@ _SIGNATURES = {
     "mpo_fusion_head_loss_forward": (c_int, [_P] + [c_int] * 5 + [_P, _P, _P, _P, c_float, c_float] + [_P] * 6 + [_P]),
     "mpo_fusion_head_loss_backward": (c_int, [_P] + [c_int] * 5 + [_P, _P, _P, _P] + [_P, c_size_t, _P]),
     "mpo_step_counters_bump": (c_int, [_P, _P, _P]),
+    "mpo_sct_loss_forward": (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, _P]),
+    "mpo_sct_loss_backward": (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, c_int, _P, _P]),
+    "mpo_fusion_head_sct_loss_forward": (c_int, [_P] + [c_int] * 5 + [_P, _P, _P, _P, c_float] + [_P] * 6 + [_P]),
+    "mpo_optim_step_flat": (c_int, [c_int, _P, _P, _P, _P, ctypes.c_int64, c_float, _P, c_float, c_float, c_float, c_float,
+                                    c_float, c_int, _P, _P]),
+    "mpo_abs_sum_flat_workspace_bytes": (c_size_t, [ctypes.c_int64]),
+    "mpo_abs_sum_flat": (c_int, [_P, ctypes.c_int64, _P, _P, c_size_t, _P]),
     "mpo_set_gemm_fast_path": (c_int, [c_int]),
     "mpo_set_coattn_bwd_two_wave": (c_int, [c_int]),
     "mpo_set_nacagat_one_pass_key_grad": (c_int, [c_int]),

@@ -729,6 +729,36 @@ int mpo_adam_step_flat(float* params, const float* grads, float* exp_avg, float*
                                 step < 1 ? 1 : step, step_dev, stream);
 }
 
+// The other training.optimizer choices and the L1 penalty's fold (include/mpo_hip.h); additive to ABI 14.
+int mpo_optim_step_flat(int algorithm, float* params, const float* grads, float* state1, float* state2, int64_t n, float lr,
+                        const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, float l1, int step,
+                        const int32_t* step_dev, mpo_stream_t stream) {
+    MPO_CHECK(algorithm >= MPO_OPTIM_ADAM && algorithm <= MPO_OPTIM_SGD, "flat optimiser: unknown algorithm %d", algorithm);
+    MPO_CHECK(n >= 0, "flat optimiser: n = %lld", (long long)n);
+    MPO_CHECK(params && grads, "flat optimiser: null parameter or gradient buffer");
+    const bool stateful = algorithm != MPO_OPTIM_SGD;
+    MPO_CHECK(!stateful || (state1 && state2), "flat optimiser: algorithm %d needs both state buffers", algorithm);
+    const auto misaligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3u) != 0; };
+    MPO_CHECK(!misaligned(params) && !misaligned(grads) && !misaligned(state1) && !misaligned(state2) && !misaligned(lr_dev) &&
+              !misaligned(step_dev), "flat optimiser: buffers must be 4-byte aligned");
+    const bool counted = algorithm == MPO_OPTIM_ADAM || algorithm == MPO_OPTIM_ADAMAX;
+    MPO_CHECK(!counted || step >= 1 || step_dev, "flat optimiser: step counts from 1 (got %d)", step);
+    return mpo_launch_optim_flat(algorithm, params, grads, state1, state2, (size_t)n, lr, lr_dev, beta1, beta2, eps,
+                                 weight_decay, l1, step < 1 ? 1 : step, step_dev, static_cast<hipStream_t>(stream));
+}
+size_t mpo_abs_sum_flat_workspace_bytes(int64_t n) {
+    return n < 0 ? 0 : mpo_abs_sum_partials((size_t)n) * sizeof(float);
+}
+int mpo_abs_sum_flat(const float* x, int64_t n, float* out, void* workspace, size_t workspace_bytes, mpo_stream_t stream) {
+    MPO_CHECK(n >= 1, "abs sum: n = %lld", (long long)n);
+    MPO_CHECK(x && out && workspace, "abs sum: null argument");
+    MPO_CHECK((reinterpret_cast<uintptr_t>(x) & 3u) == 0 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0 &&
+              (reinterpret_cast<uintptr_t>(workspace) & 3u) == 0, "abs sum: pointers must be 4-byte aligned");
+    MPO_CHECK(workspace_bytes >= mpo_abs_sum_flat_workspace_bytes(n), "abs sum: workspace too small (%zu bytes)",
+              workspace_bytes);
+    return mpo_launch_abs_sum(x, (size_t)n, static_cast<float*>(workspace), out, static_cast<hipStream_t>(stream));
+}
+
 // Verification hook: the small-row GEMMs have a branch-free body for regular products and a general body; both must
 // give the same bits.  enabled = 0 routes every product through the general body.  Returns the previous setting.
 int mpo_set_gemm_fast_path(int enabled) { return mpo_gemm_fast_path(enabled); }

@@ -286,6 +286,14 @@ int mpo_launch_head_fwd(const float* logits, float* hazards, float* survs, float
 int mpo_launch_head_loss(const float* logits, const long long* label, const float* cens, const float* w, float* hazards,
                          float* survs, float* y, float* loss, float* risk, float* dlogits, int B, int C, float alpha,
                          float eps, hipStream_t s);
+// 'sct' loss (tail.hip): on Y alone, and fused with the head like mpo_launch_head_loss
+int mpo_launch_sct_loss_fwd(const float* y, const long long* label, const float* cens, float* loss, int B, int C, float eps,
+                            hipStream_t s);
+int mpo_launch_sct_loss_bwd(const float* y, const long long* label, const float* cens, const float* d_loss,
+                            int d_loss_scalar, float* d_y, int B, int C, float eps, hipStream_t s);
+int mpo_launch_head_sct_loss(const float* logits, const long long* label, const float* cens, const float* w, float* hazards,
+                             float* survs, float* y, float* loss, float* risk, float* dlogits, int B, int C, float eps,
+                             hipStream_t s);
 int mpo_launch_counters_bump(unsigned long long* epoch, int* step, hipStream_t s);
 int mpo_launch_head_bwd(const float* hazards, const float* survs, const float* y, const float* dhz, const float* dsv,
                         const float* dy, float* dlogits, int B, int C, hipStream_t s);
@@ -311,6 +319,12 @@ int mpo_launch_relu_dropout_bwd_bf16(const void* h, const void* dy, void* g, siz
 
 int mpo_launch_adam_flat(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps,
                          float wd, int step, const int* step_dev, hipStream_t stream);
+// flat optimiser family (optim.hip): algorithm = MPO_OPTIM_*; state1/state2 per algorithm (see include/mpo_hip.h)
+int mpo_launch_optim_flat(int algorithm, float* p, const float* g, float* s1, float* s2, size_t n, float lr,
+                          const float* lr_dev, float b1, float b2, float eps, float wd, float l1, int step,
+                          const int* step_dev, hipStream_t stream);
+size_t mpo_abs_sum_partials(size_t n);
+int mpo_launch_abs_sum(const float* x, size_t n, float* partials, float* out, hipStream_t stream);
 int mpo_launch_colsum_bf16(const void* x, float* out, size_t rows, int cols, hipStream_t stream);
 
 // gated (tanh on the fly) single-pass variants for K2 (bagops.hip)

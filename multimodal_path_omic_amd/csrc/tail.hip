@@ -726,6 +726,84 @@ __global__ void head_loss_kernel(const float* __restrict__ logits, const long lo
     }
     for (int i = 0; i < C; ++i) dlogits[o + i] = dl[i];
 }
+// ------------------------------------------------------------------ 'sct' loss (models/loss.py:62-85) on Y = softmax(logits)
+//   uncensored: -log(Y[y] + eps);  censored: -log(P + eps),  P = sum_{j >= y} Y[j]   (eps added, not clamped)
+// One thread per slide.  The backward of the standalone pair is taken w.r.t. Y (the survival head's backward carries
+// it through the softmax): d_Y[y] = -g / (Y[y] + eps), resp. d_Y[j >= y] = -g / (P + eps).
+__global__ void sct_loss_fwd_kernel(const float* __restrict__ y, const long long* __restrict__ label,
+                                    const float* __restrict__ cens, float* __restrict__ loss, int B, int C, float eps) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const size_t o = (size_t)b * C;
+    const int yb = (int)label[b];
+    float p = y[o + yb];
+    if (cens[b] != 0.0f)
+        for (int j = yb + 1; j < C; ++j) p += y[o + j];
+    loss[b] = -logf(p + eps);
+}
+__global__ void sct_loss_bwd_kernel(const float* __restrict__ y, const long long* __restrict__ label,
+                                    const float* __restrict__ cens, const float* __restrict__ d_loss, int d_loss_scalar,
+                                    float* __restrict__ d_y, int B, int C, float eps) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const size_t o = (size_t)b * C;
+    const int yb = (int)label[b];
+    const bool censored = cens[b] != 0.0f;
+    const float g = d_loss_scalar ? d_loss[0] : d_loss[b];
+    float p = y[o + yb];
+    if (censored)
+        for (int j = yb + 1; j < C; ++j) p += y[o + j];
+    const float d = -g / (p + eps);
+    for (int j = 0; j < C; ++j) d_y[o + j] = (j == yb || (censored && j > yb)) ? d : 0.0f;
+}
+
+// Training step with 'sct': head_loss_kernel's head, then the loss and its gradient w.r.t. the logits in a form that stays
+// finite and exact when Y[y] is tiny (the softmax Jacobian applied by hand, the (Y+eps) denominator kept):
+//   uncensored: r = Y[y] / (Y[y] + eps),  dlogit_j = w r (Y_j - [j == y])
+//   censored:   dlogit_j = w Y_j (P - [j >= y]) / (P + eps),  P - 1 = -Q  with Q = sum_{j < y} Y_j summed, not 1 - P
+// Hazards and survs receive no gradient; risk = -sum_j S_j as in the 'ces' kernel.
+__global__ void head_sct_loss_kernel(const float* __restrict__ logits, const long long* __restrict__ label,
+                                     const float* __restrict__ cens, const float* __restrict__ w,
+                                     float* __restrict__ hazards, float* __restrict__ survs, float* __restrict__ y,
+                                     float* __restrict__ loss, float* __restrict__ risk, float* __restrict__ dlogits,
+                                     int B, int C, float eps) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const size_t o = (size_t)b * C;
+    float yv[kMaxC];
+    float mx = logits[o];
+    for (int j = 1; j < C; ++j) mx = fmaxf(mx, logits[o + j]);
+    float s = 0.f, run = 1.0f, r = 0.f;
+    for (int j = 0; j < C; ++j) s += __expf(logits[o + j] - mx);
+    for (int j = 0; j < C; ++j) {
+        const float hz = 1.0f / (1.0f + __expf(-logits[o + j]));
+        run *= 1.0f - hz;
+        r -= run;
+        hazards[o + j] = hz;
+        survs[o + j] = run;
+        yv[j] = __expf(logits[o + j] - mx) / s;
+        y[o + j] = yv[j];
+    }
+    if (risk) risk[b] = r;
+    const int yb = (int)label[b];
+    const float g = w[b];
+    if (cens[b] == 0.0f) {
+        const float py = yv[yb];
+        loss[b] = -logf(py + eps);
+        const float gr = g * (py / (py + eps));
+        for (int j = 0; j < C; ++j) dlogits[o + j] = gr * (j == yb ? yv[j] - 1.0f : yv[j]);
+    } else {
+        float p = 0.f, q = 0.f;
+        for (int j = 0; j < C; ++j) {
+            if (j >= yb) p += yv[j];
+            else q += yv[j];
+        }
+        loss[b] = -logf(p + eps);
+        const float inv = g / (p + eps);
+        for (int j = 0; j < C; ++j) dlogits[o + j] = yv[j] * (j >= yb ? -q : p) * inv;
+    }
+}
+
 __global__ void counters_bump_kernel(unsigned long long* __restrict__ epoch, int* __restrict__ step) {
     if (threadIdx.x == 0) {
         if (epoch) epoch[0] += 1ull;
@@ -974,6 +1052,28 @@ int mpo_launch_head_loss(const float* logits, const long long* label, const floa
                          float eps, hipStream_t s) {
     MPO_CHECK(B >= 1 && C >= 1 && C <= kMaxC, "head + ces loss: %d slides x %d classes (classes in 1..%d)", B, C, kMaxC);
     head_loss_kernel<<<(B + 63) / 64, 64, 0, s>>>(logits, label, cens, w, hazards, survs, y, loss, risk, dlogits, B, C, alpha, eps);
+    MPO_LAUNCH_CHECK();
+    return 0;
+}
+int mpo_launch_sct_loss_fwd(const float* y, const long long* label, const float* cens, float* loss, int B, int C, float eps,
+                            hipStream_t s) {
+    MPO_CHECK(B >= 1 && C >= 1, "sct loss: empty batch (%d x %d)", B, C);
+    sct_loss_fwd_kernel<<<(B + 63) / 64, 64, 0, s>>>(y, label, cens, loss, B, C, eps);
+    MPO_LAUNCH_CHECK();
+    return 0;
+}
+int mpo_launch_sct_loss_bwd(const float* y, const long long* label, const float* cens, const float* d_loss,
+                            int d_loss_scalar, float* d_y, int B, int C, float eps, hipStream_t s) {
+    MPO_CHECK(B >= 1 && C >= 1, "sct loss: empty batch (%d x %d)", B, C);
+    sct_loss_bwd_kernel<<<(B + 63) / 64, 64, 0, s>>>(y, label, cens, d_loss, d_loss_scalar, d_y, B, C, eps);
+    MPO_LAUNCH_CHECK();
+    return 0;
+}
+int mpo_launch_head_sct_loss(const float* logits, const long long* label, const float* cens, const float* w, float* hazards,
+                             float* survs, float* y, float* loss, float* risk, float* dlogits, int B, int C, float eps,
+                             hipStream_t s) {
+    MPO_CHECK(B >= 1 && C >= 1 && C <= kMaxC, "head + sct loss: %d slides x %d classes (classes in 1..%d)", B, C, kMaxC);
+    head_sct_loss_kernel<<<(B + 63) / 64, 64, 0, s>>>(logits, label, cens, w, hazards, survs, y, loss, risk, dlogits, B, C, eps);
     MPO_LAUNCH_CHECK();
     return 0;
 }

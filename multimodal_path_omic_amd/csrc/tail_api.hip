@@ -523,6 +523,23 @@ int mpo_fusion_head_loss_forward(const float* hcat, int n_slides, int din, int h
                             loss, risk, dlogits, n_slides, n_classes, alpha, eps, static_cast<hipStream_t>(stream)));
     return 0;
 }
+// The same with the `sct` loss (head_sct_loss_kernel); the backward is mpo_fusion_head_loss_backward unchanged.
+int mpo_fusion_head_sct_loss_forward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes,
+                                     const float* const* P, const int64_t* label, const float* censorship,
+                                     const float* slide_weight, float eps, float* hazards, float* survs, float* y,
+                                     float* loss, float* risk, float* saved, mpo_stream_t stream) {
+    MPO_CHECK(hcat && P && label && censorship && slide_weight && hazards && survs && y && loss && saved,
+              "fusion head + sct loss forward: null argument");
+    Carver c(saved);
+    float* z1 = c.take((size_t)n_slides * hidden); float* z2 = c.take((size_t)n_slides * dout);
+    float* logits = c.take((size_t)n_slides * n_classes); float* dlogits = c.take((size_t)n_slides * n_classes);
+    RC(mpo_linear_fwd(hcat, P[0], P[1], z1, n_slides, din, hidden, 1.0f, MPO_ACT_RELU, stream));
+    RC(mpo_linear_fwd(z1, P[2], P[3], z2, n_slides, hidden, dout, 1.0f, MPO_ACT_RELU, stream));
+    RC(mpo_linear_fwd(z2, P[4], P[5], logits, n_slides, dout, n_classes, 1.0f, MPO_ACT_NONE, stream));
+    RC(mpo_launch_head_sct_loss(logits, reinterpret_cast<const long long*>(label), censorship, slide_weight, hazards, survs,
+                                y, loss, risk, dlogits, n_slides, n_classes, eps, static_cast<hipStream_t>(stream)));
+    return 0;
+}
 int mpo_fusion_head_loss_backward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes,
                                   const float* const* P, const float* saved, float* d_hcat, float* const* G,
                                   void* workspace, size_t workspace_bytes, mpo_stream_t stream) {
@@ -573,6 +590,22 @@ int mpo_ces_loss_backward(const float* hazards, const float* survs, const int64_
     return mpo_launch_ces_loss_bwd(hazards, survs, reinterpret_cast<const long long*>(label), censorship, d_loss,
                                    d_loss_is_scalar, d_hazards, d_survs, n_slides, n_classes, alpha, eps,
                                    static_cast<hipStream_t>(stream));
+}
+
+// ------------------------------------------------------------------------------------------- 'sct' loss
+int mpo_sct_loss_forward(const float* y, const int64_t* label, const float* censorship, int n_slides, int n_classes,
+                         float eps, float* loss, mpo_stream_t stream) {
+    MPO_CHECK(y && label && censorship && loss, "sct loss forward: null argument");
+    MPO_CHECK(n_classes >= 1 && n_classes <= 16, "sct loss: n_classes %d not in 1..16", n_classes);
+    return mpo_launch_sct_loss_fwd(y, reinterpret_cast<const long long*>(label), censorship, loss, n_slides, n_classes, eps,
+                                   static_cast<hipStream_t>(stream));
+}
+int mpo_sct_loss_backward(const float* y, const int64_t* label, const float* censorship, int n_slides, int n_classes,
+                          float eps, const float* d_loss, int d_loss_is_scalar, float* d_y, mpo_stream_t stream) {
+    MPO_CHECK(y && label && censorship && d_loss && d_y, "sct loss backward: null argument");
+    MPO_CHECK(n_classes >= 1 && n_classes <= 16, "sct loss: n_classes %d not in 1..16", n_classes);
+    return mpo_launch_sct_loss_bwd(y, reinterpret_cast<const long long*>(label), censorship, d_loss, d_loss_is_scalar, d_y,
+                                   n_slides, n_classes, eps, static_cast<hipStream_t>(stream));
 }
 
 // ------------------------------------------------------------------------------------------- K3 CAG

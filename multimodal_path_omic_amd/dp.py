@@ -133,6 +133,102 @@ class FlatAdam:
                                            self.flat_p.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
                                            0, L.ptr(self.t_dev), L.stream_of(self.flat_p)), "mpo_adam_step_flat")
 
+    def state_tensors(self):
+        """Every tensor a step writes (what a warm-up that must not train puts back)."""
+        return [self.flat_p, self.exp_avg, self.exp_avg_sq, self.t_dev]
+
+
+def _repoint_params(bucket: FlatGradBucket) -> torch.Tensor:
+    """Flat fp32 parameter buffer laid out like the gradient bucket; every parameter is re-pointed at its slice (the padding
+    between slices stays zero, and every update below keeps it zero)."""
+    flat_p = torch.zeros_like(bucket.flat)
+    for p, off in zip(bucket.params, bucket.offsets):
+        sl = flat_p[off:off + p.numel()].view_as(p)
+        sl.copy_(p.data)
+        p.data = sl
+        p._mpo_flat_param_base = flat_p
+    return flat_p
+
+
+class FlatOptimizer:
+    """The reference's training.optimizer choices (models/mcat/main.py:284-300) as ONE HIP pass over flat buffers
+    (mpo_optim_step_flat): 'adam' | 'adamax' | 'adadelta' | 'sgd', torch.optim 2.x single-tensor arithmetic in fp32.
+    Parameters are re-pointed at slices of a flat buffer as in FlatAdam.
+
+    The learning rate lives in a device scalar (`lr_dev`) and the step count in `t_dev`, so a captured step follows a
+    schedule (FlatExponentialLR) and the bias correction.  `l1_lambda` > 0 folds the L1 penalty's gradient
+    (training.lambda: lambda * l1_reg(model) added to every slide's loss, models/mcat/main.py:61,69, not divided by
+    grad_acc_step) into the pass: g' = g + lambda * S * sign(p) + weight_decay * p, S = the window's slides over ALL ranks
+    (step(l1_slides=S)); after the data-parallel AVG all-reduce this is the reference's update."""
+
+    DEFAULTS = {"adam": dict(betas=(0.9, 0.999), eps=1e-8), "adamax": dict(betas=(0.9, 0.999), eps=1e-8),
+                "adadelta": dict(betas=(0.9, 0.0), eps=1e-6), "sgd": dict(betas=(0.0, 0.0), eps=0.0)}
+
+    def __init__(self, bucket: FlatGradBucket, algorithm: str = "adam", lr: float = 2e-4, weight_decay: float = 0.0,
+                 betas=None, eps=None, rho=None, l1_lambda: float = 0.0):
+        """betas / eps default to torch.optim's for the algorithm; adadelta takes rho (default 0.9) instead of betas."""
+        if algorithm not in self.DEFAULTS:
+            raise ValueError(f"unknown flat optimiser '{algorithm}' ({' | '.join(self.DEFAULTS)})")
+        d = self.DEFAULTS[algorithm]
+        self.bucket, self.algorithm = bucket, algorithm
+        self.betas = tuple(betas) if betas is not None else d["betas"]
+        if algorithm == "adadelta":
+            self.betas = (0.9 if rho is None else float(rho), 0.0)
+        self.eps = d["eps"] if eps is None else float(eps)
+        self.wd = float(weight_decay)
+        self.l1_lambda = float(l1_lambda or 0.0)
+        self.flat_p = _repoint_params(bucket)
+        dev = self.flat_p.device
+        stateful = algorithm != "sgd"
+        self.state1 = torch.zeros_like(self.flat_p) if stateful else None
+        self.state2 = torch.zeros_like(self.flat_p) if stateful else None
+        self.t_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.lr = float(lr)
+        self.lr_dev = torch.full((1,), self.lr, dtype=torch.float32, device=dev)
+
+    def set_lr(self, lr: float):
+        """New learning rate (host value and the device scalar a captured step reads).  Call outside graph capture."""
+        self.lr = float(lr)
+        self.lr_dev.fill_(self.lr)
+
+    def state_tensors(self):
+        """Every tensor a step writes (what a warm-up that must not train puts back)."""
+        return [t for t in (self.flat_p, self.state1, self.state2, self.t_dev) if t is not None]
+
+    def l1_value(self) -> torch.Tensor:
+        """sum |p| over the flat parameters as a device scalar (deterministic; ops.flat_abs_sum)."""
+        from . import ops
+        return ops.flat_abs_sum(self.flat_p)
+
+    def step(self, bump: bool = True, l1_slides: "int | None" = None):
+        """One update.  bump=False: the caller advanced t_dev already (ops.bump_step_counters).  l1_slides: the number of
+        slides whose losses carried the L1 penalty since the last step (all ranks); required when l1_lambda > 0."""
+        from . import ops
+        if self.l1_lambda and l1_slides is None:
+            raise ValueError("FlatOptimizer.step: l1_lambda > 0 needs l1_slides (slides of the window over all ranks)")
+        if bump:
+            self.t_dev += 1
+        l1 = self.l1_lambda * l1_slides if self.l1_lambda else 0.0
+        ops.optim_step_flat(self.algorithm, self.flat_p, self.bucket.flat, self.state1, self.state2, self.lr, self.lr_dev,
+                            self.betas[0], self.betas[1], self.eps, self.wd, l1, 1, self.t_dev)
+
+
+class FlatExponentialLR:
+    """torch.optim.lr_scheduler.ExponentialLR (the reference's training.scheduler 'exp', models/mcat/main.py:302-307; one
+    step per epoch, main.py:82-84) for a FlatOptimizer: the chainable form lr <- lr * gamma on a Python float, written to
+    the optimiser's device scalar outside any graph."""
+
+    def __init__(self, opt: FlatOptimizer, gamma: float):
+        self.opt, self.gamma = opt, float(gamma)
+        self.last_epoch = 0
+
+    def step(self):
+        self.last_epoch += 1
+        self.opt.set_lr(self.opt.lr * self.gamma)
+
+    def get_last_lr(self):
+        return [self.opt.lr]
+
 
 def assign_slides(lengths: Sequence[int], world_size: int) -> "List[List[int]]":
     """Length-aware split of one accumulation window across ranks: greedy longest-first bin packing

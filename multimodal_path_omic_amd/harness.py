@@ -4,6 +4,7 @@ gradient accumulation over `grad_acc_step` slides, Harrell's C-index.  No per-sl
 (the reference's loss.item() at main.py:49 is exactly what this harness must not do)."""
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import List, Sequence
 
 import numpy as np
@@ -65,32 +66,121 @@ def make_window(slides: Sequence[dict], device, bag_dtype=torch.float32):
     return bags, omics, labels, cens
 
 
-def train_window(model, bags: BagBatch, omics, labels, cens, grad_acc_step: int, loss: str = "ces", lambda_reg: float = 0.01):
+CE_REFUSAL = ("loss 'ce' cannot train these models: the reference computes nn.CrossEntropyLoss()(Y, label.unsqueeze(0)) "
+              "with Y (1, C) and a (1, 1) target (models/mcat/main.py:46-47), which torch rejects on the first slide "
+              "('0D or 1D target tensor expected') -- there is no behaviour to reproduce; use 'ces' or 'sct'")
+
+
+def train_window(model, bags: BagBatch, omics, labels, cens, grad_acc_step: int, loss: str = "ces", lambda_reg: float = 0.01,
+                 alpha: float = 0.75, l1: float = 0.0):
     """Forward + backward of one window; gradients ACCUMULATE into .grad with the reference's
     1/grad_acc_step scaling per slide (models/mcat/main.py:69-70).  Returns (per-slide loss, risk) tensors
-    on the device -- no host sync.  loss: 'ces' (models/loss.py:5-28) or 'cesar' (:88-101: ces + lambda_reg * ||A_b||_2 of
-    the slide's co-attention map, models/nacagat/main.py:49-50)."""
+    on the device -- no host sync.  loss: 'ces' (models/loss.py:5-28, weight `alpha`), 'sct' (:62-85 on Y) or 'cesar'
+    (:88-101: ces + lambda_reg * ||A_b||_2 of the slide's co-attention map, models/nacagat/main.py:49-50).
+    l1 > 0 (training.lambda): every slide's REPORTED loss gains l1 * sum|W| over the weights the window runs with
+    (models/mcat/main.py:51-54,61); the penalty's gradient is not taken here -- the flat optimiser folds it into its
+    pass (dp.FlatOptimizer(l1_lambda=l1), step(l1_slides=...))."""
     from . import ops
     if loss == "cesar":
         hazards, survs, _, att = model.forward_window(bags, omics, inference=True)    # the map is an output here
-        per_slide, risk = ops.ces_loss(hazards, survs, labels, cens)
+        per_slide, risk = ops.ces_loss(hazards, survs, labels, cens, alpha)
         per_slide = per_slide + lambda_reg * ops.map_block_norm(att["coattn"])
-    elif loss == "ces":
+    elif loss in ("ces", "sct"):
         if getattr(model, "fusion", None) == "concat":
             # head, loss and the backward of both in one launch: the loss gradient is known before the forward
             w = _slide_weights(bags.n_slides, grad_acc_step, labels.device)
-            _, _, _, att = model.forward_window(bags, omics, ces_targets=(labels, cens, w))
+            _, _, _, att = model.forward_window(bags, omics, ces_targets=(labels, cens, w), fused_loss=loss, alpha=alpha)
             per_slide, risk = att["loss"], att["risk"]
             per_slide.backward(w)
-            return per_slide.detach(), risk
-        hazards, survs, _, _ = model.forward_window(bags, omics)
-        per_slide, risk = ops.ces_loss(hazards, survs, labels, cens)              # one HIP launch each way
+            return _with_penalty(model, per_slide.detach(), l1), risk
+        hazards, survs, y, _ = model.forward_window(bags, omics)
+        if loss == "ces":
+            per_slide, risk = ops.ces_loss(hazards, survs, labels, cens, alpha)    # one HIP launch each way
+        else:
+            per_slide, risk = ops.sct_loss(y, labels, cens), risk_score(survs.detach())
+    elif loss == "ce":
+        raise ValueError(CE_REFUSAL)
     else:
-        raise ValueError(f"loss '{loss}' is not built (ces | cesar)")
+        raise ValueError(f"loss '{loss}' is not built (ces | sct | cesar)")
     # d(sum(loss) / grad_acc_step) / d(loss_b) = 1 / grad_acc_step: hand it over as a cached constant instead of
     # building the sum / div graph (five tiny launches per window)
     per_slide.backward(_slide_weights(per_slide.numel(), grad_acc_step, per_slide.device))
-    return per_slide.detach(), risk
+    return _with_penalty(model, per_slide.detach(), l1), risk
+
+
+def _with_penalty(model, per_slide, l1: float):
+    return per_slide if not l1 else per_slide + l1 * weights_abs_sum(model)
+
+
+def weights_abs_sum(model) -> torch.Tensor:
+    """l1_reg(model) = sum over every parameter of sum |W| (models/utils.py:33-40) as a device scalar (1,), no host sync.
+    Parameters re-pointed into a flat optimiser's buffer (dp.FlatOptimizer, whose padding stays zero) cost one
+    deterministic reduction over that buffer; any other parameter one reduction of its own."""
+    from . import ops
+    bases, rest = {}, []
+    for p in model.parameters():
+        base = getattr(p, "_mpo_flat_param_base", None)
+        if base is not None and p.untyped_storage().data_ptr() == base.untyped_storage().data_ptr():
+            bases[id(base)] = base
+        else:
+            rest.append(p)
+    parts = [ops.flat_abs_sum(b) for b in bases.values()] + [ops.flat_abs_sum(p.detach().float()) for p in rest]
+    return parts[0] if len(parts) == 1 else torch.cat(parts).sum(0, keepdim=True)
+
+
+# ------------------------------------------------------------------------------------ the reference's training: config
+LOSSES = {"mcat": ("ces", "sct"), "nacagat": ("ces", "sct", "cesar")}
+OPTIMISERS = ("adam", "adamax", "adadelta", "sgd")
+
+
+@dataclass
+class TrainOptions:
+    """The reference's `training:` choices as this package runs them (models/mcat/main.py:272-318,
+    models/nacagat/main.py:283-296).  train_kwargs() feeds train_window / GraphedWindowStep; make_optimizer() and
+    make_scheduler() build the flat optimiser (with the L1 fold) and the per-epoch schedule."""
+    loss: str
+    alpha: float
+    lambda_reg: float             # cesar's attention-map weight (fixed 0.01 in the reference)
+    grad_acc_step: int
+    optimizer: str
+    lr: float
+    weight_decay: float
+    l1: float                     # training.lambda; 0.0 = no penalty
+    gamma: "float | None"         # ExponentialLR gamma, None = no schedule
+
+    def train_kwargs(self) -> dict:
+        return dict(loss=self.loss, alpha=self.alpha, lambda_reg=self.lambda_reg, l1=self.l1)
+
+    def make_optimizer(self, bucket):
+        from .dp import FlatOptimizer
+        wd = 0.0 if self.optimizer == "sgd" else self.weight_decay          # main.py:288-289 passes lr only
+        return FlatOptimizer(bucket, self.optimizer, lr=self.lr, weight_decay=wd, l1_lambda=self.l1)
+
+    def make_scheduler(self, opt):
+        from .dp import FlatExponentialLR
+        return None if self.gamma is None else FlatExponentialLR(opt, self.gamma)
+
+
+def training_options(training: dict, model: str = "mcat") -> TrainOptions:
+    """The reference's `training:` config dict -> TrainOptions, by the reference's own mapping: an unknown loss raises;
+    'cesar' exists for NaCAGaT only and always runs with alpha 0.75, lambda_reg 0.01 (CrossEntropySurvivalAttnRegLoss());
+    'ce' raises (CE_REFUSAL); unknown optimiser names (e.g. 'rms') become 'adam'; 'sgd' gets no weight decay;
+    lambda 0 / None means no penalty; any scheduler other than 'exp' means none."""
+    if model not in LOSSES:
+        raise ValueError(f"model '{model}' has no training loop here (mcat | nacagat)")
+    loss = training["loss"]
+    if loss == "ce":
+        raise ValueError(CE_REFUSAL)
+    if loss not in LOSSES[model]:
+        raise ValueError(f'Loss "{loss}" not implemented for {model} ({" | ".join(LOSSES[model])})')
+    alpha, lambda_reg = (0.75, 0.01) if loss == "cesar" else (float(training.get("alpha", 0.75)), 0.01)
+    name = training.get("optimizer")
+    name = name if name in OPTIMISERS else "adam"
+    lam = training.get("lambda")
+    gamma = float(training["gamma"]) if training.get("scheduler") == "exp" else None
+    return TrainOptions(loss=loss, alpha=alpha, lambda_reg=lambda_reg, grad_acc_step=int(training["grad_acc_step"]),
+                        optimizer=name, lr=float(training["lr"]), weight_decay=float(training.get("weight_decay") or 0.0),
+                        l1=float(lam) if lam else 0.0, gamma=gamma)
 
 
 _slide_weight_cache = {}
@@ -118,13 +208,18 @@ class GraphedWindowStep:
     """
 
     def __init__(self, model, bucket, window, grad_acc_step: int, opt=None, warmup: int = 2, pool=None,
-                 split_patch_grad: bool = False, prime: bool = True):
+                 split_patch_grad: bool = False, prime: bool = True, loss: str = "ces", alpha: float = 0.75,
+                 lambda_reg: float = 0.01, l1: "float | None" = None):
         """split_patch_grad (data-parallel steps, opt=None): the patch layer's weight gradient -- a 0.3 ms GEMM nobody
         downstream waits for -- is captured into a SECOND graph, `replay_tail()`.  The caller replays the main graph,
         starts the all-reduce of every other gradient (bucket.all_reduce_mean_async(lo=head)), replays the tail while
-        that collective runs, then reduces the head slice: the exchange step hides behind compute."""
+        that collective runs, then reduces the head slice: the exchange step hides behind compute.
+        loss / alpha / lambda_reg / l1: train_window's (TrainOptions.train_kwargs()); l1 defaults to the optimiser's
+        l1_lambda, whose gradient fold the captured opt.step() applies for this window's slides."""
         from . import ops
         self.model, self.bucket, self.opt = model, bucket, opt
+        self.l1 = float(getattr(opt, "l1_lambda", 0.0) if l1 is None else l1)
+        self.train_kwargs = dict(loss=loss, alpha=alpha, lambda_reg=lambda_reg, l1=self.l1)
         self.window, self.acc = window, grad_acc_step
         self.split = bool(split_patch_grad)
         if self.split and opt is not None:
@@ -137,7 +232,7 @@ class GraphedWindowStep:
         self.epoch = ops._rng_epoch_tensor
         # warm-up runs execute real steps (allocator, lazy initialisation): construction must not train the model, so the
         # optimiser state they touch is put back afterwards (the capture itself executes nothing)
-        keep = None if opt is None else [t.clone() for t in (opt.flat_p, opt.exp_avg, opt.exp_avg_sq, opt.t_dev)]
+        keep = None if opt is None else [t.clone() for t in opt.state_tensors()]
         keep_epoch = self.epoch.clone()
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -145,7 +240,7 @@ class GraphedWindowStep:
             for _ in range(warmup):
                 self._body()
             if keep is not None:
-                for t, k in zip((opt.flat_p, opt.exp_avg, opt.exp_avg_sq, opt.t_dev), keep):
+                for t, k in zip(opt.state_tensors(), keep):
                     t.copy_(k)
             self.epoch.copy_(keep_epoch)
         torch.cuda.current_stream(dev).wait_stream(side)
@@ -169,7 +264,7 @@ class GraphedWindowStep:
                 if self.tail_graph is not None:
                     self.tail_graph.replay()
             if keep is not None:
-                for t, k in zip((opt.flat_p, opt.exp_avg, opt.exp_avg_sq, opt.t_dev), keep):
+                for t, k in zip(opt.state_tensors(), keep):
                     t.copy_(k)
             self.epoch.copy_(keep_epoch)
             bucket.flat.copy_(grads)
@@ -182,14 +277,17 @@ class GraphedWindowStep:
         bags, omics, labels, cens = self.window
         ops.defer_patch_weight_grad = self.split
         try:
-            out = train_window(self.model, bags, omics, labels, cens, self.acc)
+            out = train_window(self.model, bags, omics, labels, cens, self.acc, **self.train_kwargs)
         finally:
             ops.defer_patch_weight_grad = False
         self.bucket.finish()
         if self.split and flush:
             ops.flush_patch_weight_grads()
         if self.opt is not None:
-            self.opt.step(bump=False)
+            if getattr(self.opt, "l1_lambda", 0.0):
+                self.opt.step(bump=False, l1_slides=bags.n_slides)
+            else:
+                self.opt.step(bump=False)
         return out
 
     def head_numel(self) -> int:

@@ -91,12 +91,13 @@ class _FusionModelBase(nn.Module):
         return ops.omic_snn(omics, self.G, self.training, tokens)
 
     # ---- window API
-    def forward_window(self, bags: BagBatch, omics: "List[torch.Tensor]", inference: bool = False, ces_targets=None):
+    def forward_window(self, bags: BagBatch, omics: "List[torch.Tensor]", inference: bool = False, ces_targets=None,
+                       fused_loss: str = "ces", alpha: float = 0.75):
         """bags: raw patch features (total_rows, 1024) of the window; omics: per group (B, d_i).
         Returns hazards, survs, Y (B, C) and {'coattn': [ (N, M_b) ] | None, 'path': (B,1,N), 'omic': (B,1,N)}.
         ces_targets = (labels, censorship, slide_weight) (training step, fusion 'concat'): the `ces` loss and its backward
         ride in the head's launch (ops.fusion_head_loss_cat); the dict gains 'loss' and 'risk' (per slide), and
-        backward must be driven as loss.backward(slide_weight).
+        backward must be driven as loss.backward(slide_weight).  fused_loss names that loss: 'ces' (weight `alpha`) or 'sct'.
 
         The path and the omic set-Transformer / pooling head have identical geometry and run as ONE launch sequence
         with grouped GEMMs (ops.encoder_stacked, ops.gated_pool_stacked): the token tail is a latency-bound chain of
@@ -115,7 +116,7 @@ class _FusionModelBase(nn.Module):
             if not concat:
                 raise ValueError("forward_window(ces_targets=...) is built for fusion 'concat'")
             att["loss"], att["risk"], hazards, survs, y = ops.fusion_head_loss_cat(h, self.fusion_layer, self.classifier,
-                                                                                   *ces_targets)
+                                                                                   *ces_targets, alpha=alpha, loss=fused_loss)
             return hazards, survs, y, att
         if concat:                              # h IS (B, [h_path | h_omic]): the pooling launch wrote it interleaved
             hazards, survs, y = ops.fusion_head_cat(h, self.fusion_layer, self.classifier)

@@ -276,7 +276,7 @@ def coattn_mcat(query, batch: BagBatch, in_w, in_b, out_w, out_b, need_weights: 
 # counters the tests read to make sure a fused path really ran.  qpass_*: how a hand-on op's backward (the query handed on
 # by patch_coattn_mcat / coattn_nacagat / contextual_gate) met the gradient of that query -- accumulated in place on a
 # buffer the caller's wiring owns, or on a copy (see _query_grad_buffer)
-stats = {"colsum_handoffs": 0, "qpass_in_place": 0, "qpass_copied": 0}
+stats = {"colsum_handoffs": 0, "qpass_in_place": 0, "qpass_copied": 0, "head_loss_ces": 0, "head_loss_sct": 0}
 
 
 def _query_grad_buffer(d_qpass, owned: bool, query):
@@ -1065,6 +1065,71 @@ def ces_loss(hazards, survs, label, censorship, alpha: float = 0.75, eps: float 
     return CesLossFn.apply(hazards, survs, label, censorship, alpha, eps)
 
 
+class SctLossFn(torch.autograd.Function):
+    """'sct' loss (models/loss.py:62-85) on Y = softmax(logits) for a whole window, one launch each way: per-slide losses.
+    The gradient goes to Y only; the survival head's backward carries it through the softmax."""
+
+    @staticmethod
+    def forward(ctx, y, label, censorship, eps):
+        lib = L.lib()
+        ctx.set_materialize_grads(False)
+        y = y.contiguous()
+        label = label.view(-1).to(torch.int64).contiguous()
+        censorship = censorship.view(-1).to(torch.float32).contiguous()
+        b, c = y.shape
+        loss = torch.empty(b, device=y.device, dtype=torch.float32)
+        L.check(lib.mpo_sct_loss_forward(L.ptr(y), L.ptr(label), L.ptr(censorship), b, c, float(eps), L.ptr(loss),
+                                         L.stream_of(y)), "mpo_sct_loss_forward")
+        ctx.save_for_backward(y, label, censorship)
+        ctx.eps = float(eps)
+        return loss
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        lib = L.lib()
+        if d_loss is None:
+            return None, None, None, None
+        y, label, censorship = ctx.saved_tensors
+        b, c = y.shape
+        scalar = d_loss.stride(0) == 0 and b > 1          # loss.sum().backward(): one broadcast value
+        d_loss = d_loss.as_strided((1,), (1,)) if scalar else d_loss.contiguous()
+        d_y = torch.empty_like(y)
+        L.check(lib.mpo_sct_loss_backward(L.ptr(y), L.ptr(label), L.ptr(censorship), b, c, ctx.eps, L.ptr(d_loss), int(scalar),
+                                          L.ptr(d_y), L.stream_of(y)), "mpo_sct_loss_backward")
+        return d_y, None, None, None
+
+
+def sct_loss(y, label, censorship, eps: float = 1e-7):
+    """-> per-slide 'sct' loss (B,) of Y (B, C) (no risk: that needs survs, risk = -survs.sum(1))."""
+    return SctLossFn.apply(y, label, censorship, eps)
+
+
+def flat_abs_sum(x) -> torch.Tensor:
+    """sum |x| over a contiguous fp32 tensor as a device scalar (1,): the L1 penalty's value (models/utils.py:33-40).
+    Deterministic (two launches, fixed partial sums, no atomics); no host sync."""
+    lib = L.lib()
+    if x.dtype != torch.float32:
+        raise ValueError("flat_abs_sum: fp32 tensors only")
+    x = x.detach().contiguous().view(-1)
+    out = torch.empty(1, device=x.device, dtype=torch.float32)
+    ws = _workspace(lib.mpo_abs_sum_flat_workspace_bytes(x.numel()), x.device)
+    L.check(lib.mpo_abs_sum_flat(L.ptr(x), x.numel(), L.ptr(out), L.ptr(ws), ws.numel(), L.stream_of(x)), "mpo_abs_sum_flat")
+    return out
+
+
+def optim_step_flat(algorithm: str, params, grads, state1, state2, lr: float, lr_dev=None, beta1: float = 0.9,
+                    beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0, l1: float = 0.0, step: int = 1,
+                    step_dev=None):
+    """One mpo_optim_step_flat over flat fp32 buffers (include/mpo_hip.h): 'adam' | 'adamax' | 'adadelta' (rho = beta1) |
+    'sgd' (state1 = state2 = None).  lr_dev (fp32 (1,)) / step_dev (int32 (1,)) override lr / step on the device."""
+    if algorithm not in L.OPTIM:
+        raise ValueError(f"unknown flat optimiser '{algorithm}' ({' | '.join(L.OPTIM)})")
+    L.check(L.lib().mpo_optim_step_flat(L.OPTIM[algorithm], L.ptr(params), L.ptr(grads), L.ptr(state1), L.ptr(state2),
+                                        params.numel(), float(lr), L.ptr(lr_dev), float(beta1), float(beta2), float(eps),
+                                        float(weight_decay), float(l1), int(step), L.ptr(step_dev), L.stream_of(params)),
+            "mpo_optim_step_flat")
+
+
 class FusionHeadFn(torch.autograd.Function):
     """K6: concat-fusion MLP + classifier + survival head."""
 
@@ -1121,7 +1186,7 @@ class FusionHeadLossFn(torch.autograd.Function):
     gradient tensor.  Returns (loss (B,), risk (B,), hazards, survs, Y); only `loss` carries gradient."""
 
     @staticmethod
-    def forward(ctx, hcat, label, censorship, slide_weight, alpha, eps, *params):
+    def forward(ctx, hcat, label, censorship, slide_weight, alpha, eps, kind, *params):
         lib = L.lib()
         ctx.set_materialize_grads(False)
         hcat = hcat.contiguous()
@@ -1137,10 +1202,17 @@ class FusionHeadLossFn(torch.autograd.Function):
         loss = torch.empty(b, device=dev, dtype=torch.float32)
         risk = torch.empty(b, device=dev, dtype=torch.float32)
         saved = torch.empty(lib.mpo_fusion_head_loss_saved_floats(b, hidden, dout, c), device=dev, dtype=torch.float32)
-        L.check(lib.mpo_fusion_head_loss_forward(
-            L.ptr(hcat), b, din, hidden, dout, c, L.ptr_array(params), L.ptr(label), L.ptr(censorship), L.ptr(slide_weight),
-            float(alpha), float(eps), L.ptr(hz), L.ptr(sv), L.ptr(y), L.ptr(loss), L.ptr(risk), L.ptr(saved),
-            L.stream_of(hcat)), "mpo_fusion_head_loss_forward")
+        if kind == "ces":
+            L.check(lib.mpo_fusion_head_loss_forward(
+                L.ptr(hcat), b, din, hidden, dout, c, L.ptr_array(params), L.ptr(label), L.ptr(censorship), L.ptr(slide_weight),
+                float(alpha), float(eps), L.ptr(hz), L.ptr(sv), L.ptr(y), L.ptr(loss), L.ptr(risk), L.ptr(saved),
+                L.stream_of(hcat)), "mpo_fusion_head_loss_forward")
+        else:                                   # 'sct' (fusion_head_loss_cat checked the name)
+            L.check(lib.mpo_fusion_head_sct_loss_forward(
+                L.ptr(hcat), b, din, hidden, dout, c, L.ptr_array(params), L.ptr(label), L.ptr(censorship), L.ptr(slide_weight),
+                float(eps), L.ptr(hz), L.ptr(sv), L.ptr(y), L.ptr(loss), L.ptr(risk), L.ptr(saved),
+                L.stream_of(hcat)), "mpo_fusion_head_sct_loss_forward")
+        stats["head_loss_" + kind] += 1
         ctx.save_for_backward(hcat, saved, slide_weight, *params)
         ctx.param_refs = params
         ctx.mark_non_differentiable(risk, hz, sv, y)
@@ -1151,7 +1223,7 @@ class FusionHeadLossFn(torch.autograd.Function):
         lib = L.lib()
         hcat, saved, slide_weight, *params = ctx.saved_tensors
         if d_loss is None:
-            return (None,) * (6 + len(params))
+            return (None,) * (7 + len(params))
         if d_loss.data_ptr() != slide_weight.data_ptr() or d_loss.shape != slide_weight.shape:
             raise RuntimeError("fusion_head_loss: backward() must be driven with the slide_weight tensor given to forward "
                                "(the loss gradient is folded into the forward launch)")
@@ -1163,13 +1235,20 @@ class FusionHeadLossFn(torch.autograd.Function):
         L.check(lib.mpo_fusion_head_loss_backward(
             L.ptr(hcat), b, din, hidden, dout, c, L.ptr_array(params), L.ptr(saved), L.ptr(d_hcat), L.ptr_array(grads),
             L.ptr(ws), ws.numel(), L.stream_of(hcat)), "mpo_fusion_head_loss_backward")
-        return (d_hcat, None, None, None, None, None, *grads)
+        return (d_hcat, None, None, None, None, None, None, *grads)
 
 
-def fusion_head_loss_cat(hcat, fusion_layer, classifier, label, censorship, slide_weight, alpha: float = 0.75, eps: float = 1e-7):
-    """Training-step K6: -> (per-slide `ces` loss, risk, hazards, survs, Y); drive backward with `slide_weight` itself."""
+FUSED_LOSSES = ("ces", "sct")
+
+
+def fusion_head_loss_cat(hcat, fusion_layer, classifier, label, censorship, slide_weight, alpha: float = 0.75, eps: float = 1e-7,
+                         loss: str = "ces"):
+    """Training-step K6: -> (per-slide loss, risk, hazards, survs, Y); drive backward with `slide_weight` itself.
+    loss: 'ces' (models/loss.py:5-28, weight `alpha`) or 'sct' (models/loss.py:62-85 on Y; `alpha` unused)."""
+    if loss not in FUSED_LOSSES:
+        raise ValueError(f"fusion_head_loss_cat: loss '{loss}' has no fused head launch ({' | '.join(FUSED_LOSSES)})")
     seq = fusion_layer.fusion_layer
-    return FusionHeadLossFn.apply(hcat, label, censorship, slide_weight, alpha, eps, seq[0].weight, seq[0].bias,
+    return FusionHeadLossFn.apply(hcat, label, censorship, slide_weight, alpha, eps, loss, seq[0].weight, seq[0].bias,
                                   seq[2].weight, seq[2].bias, classifier.weight, classifier.bias)
 
 
