@@ -83,11 +83,12 @@ int mpo_coattn_mcat_forward(const void* bag, int bag_dtype, const int32_t* cu_ro
                             const float* out_proj_weight, const float* out_proj_bias,
                             float* out, float* attn_map, float* saved, const mpo_bag_plan* plan /* nullable */,
                             void* workspace, size_t workspace_bytes, mpo_stream_t stream);
-/* ---- row f1: the patch layer fused with K1's forward, ONE pass over the raw patch matrix.
+/* ---- row f1: the patch layer and K1's forward in ONE call (two bag launches).
  * Replaces models/mcat/mcat.py:24-29,87 (self.H = Linear(1024, 256) + ReLU + Dropout) AND :97 (the co-attention call) for a
- * bf16-stored window:  h_bag = Dropout_p(ReLU(patches W_H^T + b_H))  is produced tile by tile on the MFMA, consumed for
- * the scores / online softmax / context while it is still in LDS, and written once (bf16, [total_rows, embed]) for
- * mpo_coattn_mcat_backward, which takes `saved` and h_bag exactly as after mpo_coattn_mcat_forward.
+ * bf16-stored window:  h_bag = Dropout_p(ReLU(patches W_H^T + b_H))  is produced on the MFMA by the patch-layer kernel
+ * (mpo_patch_fc_forward's) and written once (bf16, [total_rows, embed]); K1's partial pass then reads it back for the
+ * scores / online softmax / context, and mpo_coattn_mcat_backward takes `saved` and h_bag exactly as after
+ * mpo_coattn_mcat_forward.
  *   patches [total_rows, patch_dim] bf16;  patch_weight [embed, patch_dim] fp32 (rounded to bf16 operands inside),
  *   patch_bias [embed] fp32.  Built for patch_dim 1024, embed 256 ('medium'), n_q <= 8.
  * Dropout: counter hash of (seed, offset [+ *rng_epoch << 40]), one draw per 16 elements, 8 random bits each: the realised drop
@@ -104,8 +105,8 @@ int mpo_patch_coattn_mcat_forward(const void* patches, const int32_t* cu_rows, i
                                   const mpo_bag_plan* plan /* nullable */, void* workspace, size_t workspace_bytes,
                                   mpo_stream_t stream);
 /* The patch layer alone: h_bag [total_rows, embed] bf16 = dropout(relu(patches W^T + b)) (models/mcat/mcat.py:24-29,87), one
- * pass of the fused kernel with its co-attention slices off (NaCAGaT needs H_bag for more than one product; MCAT outside
- * the fused configuration).  Same dropout stream and realised rate as mpo_patch_coattn_mcat_forward.
+ * pass of the patch-layer kernel (NaCAGaT needs H_bag for more than one product; MCAT outside the 1024 -> 256
+ * configuration).  Same dropout stream and realised rate as mpo_patch_coattn_mcat_forward.
  * patch_dim 1024; embed 128 / 256 / 512 = model_size small / medium / big (models/mcat/mcat.py:16-21) on the one kernel:
  * 128 as a 256-column block whose upper half is not stored, 512 as one pass per 256-column half.  Other widths: error. */
 size_t mpo_patch_fc_workspace_bytes(int embed, int patch_dim);

@@ -36,20 +36,24 @@ inline int direct_nbmax(int k) { return k <= 256 ? 4 : DMAXB; }
 // operands, a gate it knows at compile time.  Everything else goes through the general body.
 bool g_fast_path = true;                   // mpo_set_gemm_fast_path(): verification hook, on in production
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-// -> gate class of the member (0 none, 1 value gate, 2 regenerated dropout, 3 AlphaDropout + ELU derivative), or -1: not
-// for the fast body
+// -> gate class of a product (0 none, 1 value gate, 2 regenerated dropout, 3 AlphaDropout + ELU derivative), or -1: a gate the
+// special bodies do not know, or a value gate that is missing (or, where the body loads it as vectors, not 16-byte aligned)
+inline int gate_class(const GemmArgs& g, bool need_aligned_gate) {
+    const bool gate_ok = g.gate != nullptr && (!need_aligned_gate || aligned16(g.gate));
+    switch (g.gate_mode) {
+        case MPO_GATE_NONE: return 0;
+        case MPO_GATE_RNG: return 2;
+        case MPO_GATE_RELU: case MPO_GATE_ELU: case MPO_GATE_TANH: case MPO_GATE_SIGMOID: case MPO_GATE_MUL: return gate_ok ? 1 : -1;
+        case MPO_GATE_ELU_ADROP: return gate_ok ? 3 : -1;
+        default: return -1;
+    }
+}
+// -> gate class of the member, or -1: not for the fast body
 inline int fast_class(const GemmArgs& g) {
     if (!g_fast_path) return -1;
     if (g.M <= 0 || g.N <= 0 || (g.M & 15) || (g.N & 15) || g.K < 16 || (g.K & 15)) return -1;
     if ((g.lda & 3) || (g.ldb & 3) || !aligned16(g.A) || !aligned16(g.B)) return -1;
-    switch (g.gate_mode) {
-        case MPO_GATE_NONE: return 0;
-        case MPO_GATE_RNG: return 2;
-        case MPO_GATE_RELU: case MPO_GATE_ELU: case MPO_GATE_TANH: case MPO_GATE_SIGMOID: case MPO_GATE_MUL:
-            return (g.gate != nullptr && aligned16(g.gate)) ? 1 : -1;
-        case MPO_GATE_ELU_ADROP: return (g.gate != nullptr && aligned16(g.gate)) ? 3 : -1;
-        default: return -1;
-    }
+    return gate_class(g, true);
 }
 // -> gate class, or -1: a product with many rows for gemm_f32_rows.hip (32 x 64 tiles): A k-contiguous, whole column blocks
 // and k-blocks, vector-loadable operands, no bias-gradient output
@@ -57,28 +61,14 @@ inline int rows_class(const GemmArgs& g, int layout) {
     if (!g_fast_path || !(layout & 2) || g.M < 512 || (g.N & 63) || g.K < 64 || (g.K & 63) || g.bias_grad != nullptr) return -1;
     if ((g.lda & 3) || !aligned16(g.A)) return -1;
     if ((layout & 1) && ((g.ldb & 3) || !aligned16(g.B))) return -1;
-    switch (g.gate_mode) {
-        case MPO_GATE_NONE: return 0;
-        case MPO_GATE_RNG: return 2;
-        case MPO_GATE_RELU: case MPO_GATE_ELU: case MPO_GATE_TANH: case MPO_GATE_SIGMOID: case MPO_GATE_MUL:
-            return (g.gate != nullptr && aligned16(g.gate)) ? 1 : -1;
-        case MPO_GATE_ELU_ADROP: return (g.gate != nullptr && aligned16(g.gate)) ? 3 : -1;
-        default: return -1;
-    }
+    return gate_class(g, true);
 }
 // -> gate class, or -1: a weight-gradient product over a long row axis for gemm_f32_longk.hip (K cut into slices over the grid,
 // partial blocks added atomically): both operands k-strided, whole 32 x 64 blocks, nothing but alpha in the epilogue
 inline int longk_class(const GemmArgs& g, int layout) {
     if (!g_fast_path || layout != 0 || g.K < 2048 || (g.M & 31) || (g.N & 63) || (g.lda & 3)) return -1;
     if (g.bias || g.mask || g.residual || g.act != MPO_ACT_NONE || g.drop_p > 0.f) return -1;
-    switch (g.gate_mode) {
-        case MPO_GATE_NONE: return 0;
-        case MPO_GATE_RNG: return 2;
-        case MPO_GATE_RELU: case MPO_GATE_ELU: case MPO_GATE_TANH: case MPO_GATE_SIGMOID: case MPO_GATE_MUL:
-            return g.gate != nullptr ? 1 : -1;
-        case MPO_GATE_ELU_ADROP: return g.gate != nullptr ? 3 : -1;
-        default: return -1;
-    }
+    return gate_class(g, false);
 }
 inline void launch_longk(const GemmArgs& g, int gate_class, hipStream_t stream) {
     if (int e = mpo_longk_single(g, gate_class, stream)) mpo_set_error("long-K weight gradient: zero-fill failed (hip error %d)", e);
@@ -93,6 +83,13 @@ void launch_direct_single(const GemmArgs& g, int layout, dim3 grid, hipStream_t 
     if (direct_nbmax(g.K) == 4) mpo_direct_single_nb4(g, layout, grid, stream);
     else mpo_direct_single_nb8(g, layout, grid, stream);
 }
+// grid over the largest member of a group; false: no member has an output
+inline bool group_extent(const GemmGroup& grp, dim3& grid) {
+    int mx = 0, nx = 0;
+    for (int i = 0; i < grp.n; ++i) { mx = std::max(mx, grp.g[i].M); nx = std::max(nx, grp.g[i].N); }
+    grid = dim3((nx + DB - 1) / DB, (mx + DB - 1) / DB, grp.n);
+    return mx > 0 && nx > 0;
+}
 void launch_direct_group(const GemmGroup& all, dim3 grid, hipStream_t stream) {
     // members with many rows (gemm_f32_rows.hip) or a long inner dimension (gemm_f32_longk.hip) leave the group for their own
     // launches; the members of a group are independent products, so the order of the launches does not matter
@@ -105,11 +102,7 @@ void launch_direct_group(const GemmGroup& all, dim3 grid, hipStream_t stream) {
         else grp.g[grp.n++] = all.g[i];
     }
     if (grp.n == 0) return;
-    if (grp.n != all.n) {
-        int mx = 0, nx = 0;
-        for (int i = 0; i < grp.n; ++i) { mx = std::max(mx, grp.g[i].M); nx = std::max(nx, grp.g[i].N); }
-        grid = dim3((nx + DB - 1) / DB, (mx + DB - 1) / DB, grp.n);
-    }
+    if (grp.n != all.n) group_extent(grp, grid);
     int kmax = 0, classes = 0;                                    // classes: bit c set when a member has gate class c
     bool fast = true;
     for (int i = 0; i < grp.n; ++i) {
@@ -165,38 +158,24 @@ int mpo_launch_gemm(const GemmArgs& g, int a_kc, int b_kc, hipStream_t stream) {
     return 0;
 }
 
-int mpo_launch_gemm_group(const GemmGroup& grp, int a_kc, int b_kc, hipStream_t stream) {
-    MPO_CHECK(grp.n >= 1 && grp.n <= 8, "grouped gemm: 1..8 members (got %d)", grp.n);
-    int mx = 0, nx = 0;
+// the two group launchers: member check, grid extent, launch.  layout < 0: every member carries its own
+static int launch_group(const char* what, GemmGroup grp, int layout, hipStream_t stream) {
+    MPO_CHECK(grp.n >= 1 && grp.n <= 8, "%s: 1..8 members (got %d)", what, grp.n);
     for (int i = 0; i < grp.n; ++i) {
-        MPO_CHECK(grp.g[i].K > 0, "grouped gemm: member %d has K = %d", i, grp.g[i].K);
-        if (grp.g[i].M > mx) mx = grp.g[i].M;
-        if (grp.g[i].N > nx) nx = grp.g[i].N;
+        MPO_CHECK(grp.g[i].K > 0, "%s: member %d has K = %d", what, i, grp.g[i].K);
+        if (layout >= 0) grp.g[i].layout = layout;
+        else MPO_CHECK(grp.g[i].layout >= 0 && grp.g[i].layout <= 3, "%s: member %d has layout %d", what, i, grp.g[i].layout);
     }
-    if (mx <= 0 || nx <= 0) return 0;
-    GemmGroup tagged = grp;
-    for (int i = 0; i < tagged.n; ++i) tagged.g[i].layout = 2 * (a_kc ? 1 : 0) + (b_kc ? 1 : 0);
-    dim3 dgrid((nx + DB - 1) / DB, (mx + DB - 1) / DB, grp.n);
-    launch_direct_group(tagged, dgrid, stream);
-    MPO_LAUNCH_CHECK();
-    return 0;
-}
-
-int mpo_launch_gemm_mixed(const GemmGroup& grp, hipStream_t stream) {
-    MPO_CHECK(grp.n >= 1 && grp.n <= 8, "mixed grouped gemm: 1..8 members (got %d)", grp.n);
-    int mx = 0, nx = 0;
-    for (int i = 0; i < grp.n; ++i) {
-        MPO_CHECK(grp.g[i].K > 0, "mixed grouped gemm: member %d has K = %d", i, grp.g[i].K);
-        MPO_CHECK(grp.g[i].layout >= 0 && grp.g[i].layout <= 3, "mixed grouped gemm: member %d has layout %d", i, grp.g[i].layout);
-        if (grp.g[i].M > mx) mx = grp.g[i].M;
-        if (grp.g[i].N > nx) nx = grp.g[i].N;
-    }
-    if (mx <= 0 || nx <= 0) return 0;
-    dim3 dgrid((nx + DB - 1) / DB, (mx + DB - 1) / DB, grp.n);
+    dim3 dgrid;
+    if (!group_extent(grp, dgrid)) return 0;
     launch_direct_group(grp, dgrid, stream);
     MPO_LAUNCH_CHECK();
     return 0;
 }
+int mpo_launch_gemm_group(const GemmGroup& grp, int a_kc, int b_kc, hipStream_t stream) {
+    return launch_group("grouped gemm", grp, 2 * (a_kc ? 1 : 0) + (b_kc ? 1 : 0), stream);
+}
+int mpo_launch_gemm_mixed(const GemmGroup& grp, hipStream_t stream) { return launch_group("mixed grouped gemm", grp, -1, stream); }
 
 int mpo_launch_colsum(const float* x, float* out, int M, int N, int ld, int accumulate, hipStream_t stream) {
     if (N <= 0) return 0;

@@ -109,6 +109,7 @@ __device__ __forceinline__ unsigned long long epoch_offset(unsigned long long of
 // ---- host-side error plumbing (one definition in capi.hip) ----
 void mpo_set_error(const char* fmt, ...);
 #define MPO_CHECK(cond, ...) do { if (!(cond)) { mpo_set_error(__VA_ARGS__); return 1; } } while (0)
+#define RC(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)      // pass a launcher's error code up
 #define MPO_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
     mpo_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); return 2; } } while (0)
 #define MPO_LAUNCH_CHECK() MPO_HIP(hipGetLastError())

@@ -2,41 +2,17 @@
 // K4 set-Transformer encoder, K5 gated attention-MIL pooling, K6 fusion + survival head.
 // Each entry is a fixed sequence of launches (GEMMs with fused epilogues/gates + the kernels of tail.hip)
 // on the caller's stream, in caller-provided buffers.
-#include <type_traits>
+#include <algorithm>
 #include <vector>
 
 #include "../../include/mpo_hip.h"
 #include "mpo_common.h"
 #include "mpo_kernels.h"
+#include "mpo_layout.h"
 
 namespace {
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-struct Arena {
-    char* base;
-    size_t size, off = 0;
-    Arena(void* p, size_t n) : base(static_cast<char*>(p)), size(n) {}
-    float* floats(size_t n) {
-        const size_t o = align_up(off, 256);
-        if (o + n * 4 > size) return nullptr;
-        off = o + n * 4;
-        return reinterpret_cast<float*>(base + o);
-    }
-};
-struct Sizer {                         // mirrors Arena to size a workspace
-    size_t off = 0;
-    void floats(size_t n) { off = align_up(off, 256) + n * 4; }
-};
-// carve the saved buffer sequentially (floats, 64-float aligned so float4 accesses stay aligned)
-struct Carver {
-    float* p;
-    explicit Carver(float* base) : p(base) {}
-    float* take(size_t n) { float* r = p; p += (n + 63) / 64 * 64; return r; }
-};
-struct CarveSizer {
-    size_t n = 0;
-    float* take(size_t k) { n += (k + 63) / 64 * 64; return nullptr; }
-};
+using SavedCount = Count<kPad64>;              // `saved` of the tail: see kPad64
 
 inline DropSpec stream_of(float p, uint64_t seed, uint64_t base, uint64_t stride, int k, const uint64_t* epoch) {
     DropSpec d;
@@ -55,28 +31,35 @@ inline GateSpec gate_rng(DropSpec d) {
     return s;
 }
 
-#define RC(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 // a layer's dx (layout 2) and dW (layout 0) products share one mixed launch
 #define PAIR(dxa, dwa) RC(mpo_linear_bwd_pair((dxa), (dwa), stream))
 
 // ------------------------------------------------------------------------------------------- K4 encoder
 enum { P_INW, P_INB, P_OUTW, P_OUTB, P_L1W, P_L1B, P_L2W, P_L2B, P_N1W, P_N1B, P_N2W, P_N2B, P_PER_LAYER };
 
-struct EncLayerSaved {
-    float *qkv, *psave, *o, *s1, *st1, *x1, *f, *s2, *st2, *x2;
-};
+template <typename T> struct EncLayerSaved { T *qkv, *psave, *o, *s1, *st1, *x1, *f, *s2, *st2, *x2; };
 template <typename C>
-void enc_carve(C& c, EncLayerSaved* out, int B, int T, int d, int ff, int H) {
+void enc_carve(C& c, EncLayerSaved<typename C::elem>* out, int B, int T, int d, int ff, int H) {
     const size_t R = (size_t)B * T;
-    EncLayerSaved s;
-    s.qkv = c.take(R * 3 * d);
+    EncLayerSaved<typename C::elem> s;
+    s.qkv = c.floats(R * 3 * d);
     // attention state: the two T x T probability matrices per head of the token tail, or (T = the rows of a bag) one
     // log-sum-exp per head and row (+ the operand forms of the three-term bf16 path)
-    s.psave = c.take(T <= kSmallAttnMaxT ? (size_t)B * 2 * H * T * T : mpo_bag_sa_saved_floats(B, T, d, H));
-    s.o = c.take(R * d);
-    s.s1 = c.take(R * d); s.st1 = c.take(2 * R); s.x1 = c.take(R * d); s.f = c.take(R * ff);
-    s.s2 = c.take(R * d); s.st2 = c.take(2 * R); s.x2 = c.take(R * d);
+    s.psave = c.floats(T <= kSmallAttnMaxT ? (size_t)B * 2 * H * T * T : mpo_bag_sa_saved_floats(B, T, d, H));
+    s.o = c.floats(R * d);
+    s.s1 = c.floats(R * d); s.st1 = c.floats(2 * R); s.x1 = c.floats(R * d); s.f = c.floats(R * ff);
+    s.s2 = c.floats(R * d); s.st2 = c.floats(2 * R); s.x2 = c.floats(R * d);
     if (out) *out = s;
+}
+// backward workspace: one buffer set per layer (each layer's dx and dW products share one grouped launch), carved in the order
+// the backward walks the layers.  Layer 0 writes its d_in to the caller's dx; sa_floats: attention scratch of a long token
+// axis (0: T <= kSmallAttnMaxT)
+struct EncLayerWs { float *ds2, *df, *dx1, *ds1, *dob, *dqkv, *din, *sa; };
+template <typename C>
+void enc_bwd_ws(C& c, EncLayerWs* W, int layers, size_t R, size_t d, size_t ff, size_t sa_floats) {
+    for (int l = layers - 1; l >= 0; --l)
+        W[l] = {c.floats(R * d), c.floats(R * ff), c.floats(R * d), c.floats(R * d), c.floats(R * d), c.floats(R * 3 * d),
+                l == 0 ? nullptr : c.floats(R * d), sa_floats ? c.floats(sa_floats) : nullptr};
 }
 inline uint64_t enc_stream_stride(int B, int T, int d, int ff) {
     const uint64_t R = (uint64_t)B * T;
@@ -84,35 +67,61 @@ inline uint64_t enc_stream_stride(int B, int T, int d, int ff) {
     return m / 4 + 2;
 }
 
-}  // namespace
+// ---- K5 gated pooling
+// (B slides of L rows over all branches, R = B * L)
+template <typename T> struct PoolSaved { T *a, *b, *ab, *w, *hpool; };
+template <class A> PoolSaved<typename A::elem> pool_saved(A& c, size_t B, size_t L, size_t d) {
+    const size_t R = B * L;
+    return {c.floats(R * d), c.floats(R * d), c.floats(R * d), c.floats(R), c.floats(B * d)};
+}
+struct PoolWs { float *dhpool, *dscores, *dab, *da, *db; };
+template <class A> PoolWs pool_ws(A& c, size_t B, size_t L, size_t d) {
+    const size_t R = B * L;
+    return {c.floats(B * d), c.floats(R), c.floats(R * d), c.floats(R * d), c.floats(R * d)};
+}
+// counters between the three dropout streams (a, b, rho) of the pooling head
+inline uint64_t pool_stream_stride(uint64_t B, uint64_t L, uint64_t d) { return B * L * d / 4 + 2 + kMaxBranches; }
 
-extern "C" {
+// ---- K6 fusion + head
+// saved: z1 [B,hidden] | z2 [B,dout] | logits [B,C]; the training-step form (`with_loss`) adds d_logits [B,C]
+template <typename T> struct HeadSaved { T *z1, *z2, *logits, *dlogits; };
+template <class A> HeadSaved<typename A::elem> head_saved(A& c, size_t B, size_t hidden, size_t dout, size_t n_classes, bool with_loss) {
+    return {c.floats(B * hidden), c.floats(B * dout), c.floats(B * n_classes), with_loss ? c.floats(B * n_classes) : nullptr};
+}
+// (the training-step backward has its d_logits in `saved` and leaves the first block unused)
+struct HeadWs { float *dlogits, *dz2, *dz1; };
+template <class A> HeadWs head_ws(A& c, size_t B, size_t hidden, size_t dout, size_t n_classes) {
+    return {c.floats(B * n_classes), c.floats(B * dout), c.floats(B * hidden)};
+}
 
-size_t mpo_encoder_saved_floats(int n_slides, int T, int d, int ff, int heads, int layers) {
-    CarveSizer c;
-    for (int l = 0; l < layers; ++l) enc_carve(c, (EncLayerSaved*)nullptr, n_slides, T, d, ff, heads);
-    return c.n;
+// ---- K3 CAG
+// saved: u1 u2 u3 t1 t3 G E m  [R,h each] | stats_g [R,2] | stats_e [R,2]
+template <typename T> struct CagSaved { T *u1, *u2, *u3, *t1, *t3, *g, *e, *m, *sg, *se; };
+template <class A> CagSaved<typename A::elem> cag_saved(A& c, size_t rows, size_t hidden) {
+    const size_t n = rows * hidden;
+    return {c.floats(n), c.floats(n), c.floats(n), c.floats(n), c.floats(n), c.floats(n), c.floats(n), c.floats(n),
+            c.floats(2 * rows), c.floats(2 * rows)};
 }
-size_t mpo_encoder_workspace_bytes(int n_slides, int T, int d, int ff) {
-    const size_t R = (size_t)n_slides * T;
-    Sizer s;
-    for (int l = 0; l < 8; ++l) {                          // one buffer set per layer (max 8 layers)
-        s.floats(R * d); s.floats(R * ff); s.floats(R * d); s.floats(R * d); s.floats(R * d); s.floats(R * 3 * d); s.floats(R * d);
-        // long token axes: scratch of the bag self-attention backward (heads are not known here: 8 of width 32 is the
-        // one geometry with more than the per-head row sums, and d floats per row covers it)
-        if (T > kSmallAttnMaxT) s.floats(mpo_bag_sa_bwd_floats(n_slides, T, d, d / 32 > 0 ? d / 32 : 1) + (size_t)R * d);
-    }
-    return s.off + 256;
+struct CagWs { float *dm, *dG, *dE, *ds12, *ds3; };
+template <class A> CagWs cag_ws(A& c, size_t rows, size_t hidden) {
+    const size_t n = rows * hidden;
+    return {c.floats(n), c.floats(n), c.floats(n), c.floats(n), c.floats(n)};
 }
-uint64_t mpo_encoder_rng_span(int n_slides, int T, int d, int ff, int layers) {
-    return enc_stream_stride(n_slides, T, d, ff) * 4 * (uint64_t)layers;
+
+// ---- omic SNNs
+// One [n_slides, d] block per group: u1 in `saved`, du1 in the backward's workspace.
+template <class A> std::vector<typename A::elem*> snn_blocks(A& c, int n_groups, size_t n_slides, size_t d) {
+    std::vector<typename A::elem*> b(n_groups > 0 ? n_groups : 0);
+    for (auto& p : b) p = c.floats(n_slides * d);
+    return b;
 }
+// counters between the 2 * n_groups AlphaDropout streams
+inline uint64_t snn_stream_stride(uint64_t n_slides, uint64_t n_groups, uint64_t d) { return n_slides * n_groups * d / 4 + 2; }
 
 // ---- branch batching: n_branches independent modules of IDENTICAL geometry (the path and the omic set-Transformer /
 // pooling head of one model) run as ONE launch sequence.  Activations are [branch][rows][width]; every GEMM becomes a
 // grouped launch with one member per branch; LayerNorm picks its parameters by row.  The dependent launch chain of
 // the token tail is latency-bound, so the second branch rides along for free.
-namespace {
 // dropout stream of branch br inside one stream slot: branches are rows_x_width elements apart
 inline DropSpec drop_br(DropSpec d, int br, size_t elems_per_branch) { d.off += (uint64_t)br * ((elems_per_branch + 3) / 4); return d; }
 inline GateSpec gate_rng_br(DropSpec d, int br, size_t elems_per_branch) { return gate_rng(drop_br(d, br, elems_per_branch)); }
@@ -121,7 +130,7 @@ inline int launch_in_groups(const std::vector<GemmArgs>& list, int a_kc, int b_k
     for (size_t i0 = 0; i0 < list.size(); i0 += 8) {
         GemmGroup grp;
         for (size_t i = i0; i < list.size() && i < i0 + 8; ++i) grp.g[grp.n++] = list[i];
-        if (int rc = mpo_launch_gemm_group(grp, a_kc, b_kc, stream)) return rc;
+        RC(mpo_launch_gemm_group(grp, a_kc, b_kc, stream));
     }
     return 0;
 }
@@ -134,7 +143,38 @@ struct GroupBuilder {
     }
     int launch(hipStream_t s) { return g.n ? mpo_launch_gemm_mixed(g, s) : 0; }
 };
+// one grouped launch per product pair of a backward: members (dx_br, dW_br) for every branch
+template <class MkDx, class MkDw> int launch_pairs(int n_branches, hipStream_t stream, MkDx&& mk_dx, MkDw&& mk_dw) {
+    GroupBuilder g;
+    for (int br = 0; br < n_branches; ++br) {
+        RC(g.add(mk_dx(br)));
+        RC(g.add(mk_dw(br)));
+    }
+    return g.launch(stream);
+}
 }  // namespace
+
+extern "C" {
+
+size_t mpo_encoder_saved_floats(int n_slides, int T, int d, int ff, int heads, int layers) {
+    SavedCount c;
+    for (int l = 0; l < layers; ++l) enc_carve(c, nullptr, n_slides, T, d, ff, heads);
+    return c.n_floats();
+}
+size_t mpo_encoder_workspace_bytes(int n_slides, int T, int d, int ff) {
+    // neither the layer nor the head count is known here: the backward's own layout for its maximum of 8 layers and, on a long
+    // token axis, the head count whose attention scratch is largest -- an upper bound
+    size_t sa = 0;
+    for (int H = 1; H <= d && T > kSmallAttnMaxT; ++H)
+        if (d % H == 0) sa = std::max(sa, mpo_bag_sa_bwd_floats(n_slides, T, d, H));
+    WsCount c;
+    EncLayerWs W[8];
+    enc_bwd_ws(c, W, 8, (size_t)n_slides * T, d, ff, sa);
+    return c.workspace_bytes();
+}
+uint64_t mpo_encoder_rng_span(int n_slides, int T, int d, int ff, int layers) {
+    return enc_stream_stride(n_slides, T, d, ff) * 4 * (uint64_t)layers;
+}
 
 // nn.TransformerEncoder (post-norm layers, ReLU FFN, no final norm): models/mcat/mcat.py:51-53,101-102;
 // layer arithmetic torch/nn/modules/transformer.py:661 (norm_first=False).
@@ -151,10 +191,10 @@ int mpo_encoder_forward(const float* x, int n_branches, int n_slides, int T, int
               heads, T, ff > 3 * d ? ff : 3 * d);
     const int NB = n_branches, R = n_slides * T, RT = NB * R, BT = NB * n_slides;
     const uint64_t stride = enc_stream_stride(BT, T, d, ff);
-    Carver c(saved);
+    Carve<kPad64> c(saved);
     const float* in = x;
     for (int l = 0; l < layers; ++l) {
-        EncLayerSaved S;
+        EncLayerSaved<float> S;
         enc_carve(c, &S, BT, T, d, ff, heads);
         const uint64_t base = offset + stride * 4 * (uint64_t)l;
         const DropSpec d0 = stream_of(drop_p, seed, base, stride, 0, rng_epoch), d1 = stream_of(drop_p, seed, base, stride, 1, rng_epoch),
@@ -196,22 +236,18 @@ int mpo_encoder_backward(const float* x, int n_branches, int n_slides, int T, in
     const int NB = n_branches, R = n_slides * T, RT = NB * R, BT = NB * n_slides;
     const uint64_t stride = enc_stream_stride(BT, T, d, ff);
     MPO_CHECK(layers <= 8, "encoder: at most 8 layers (got %d)", layers);
-    EncLayerSaved S[8];
-    Carver c(const_cast<float*>(saved));
+    EncLayerSaved<const float> S[8];
+    Carve<kPad64, const float> c(saved);
     for (int l = 0; l < layers; ++l) enc_carve(c, &S[l], BT, T, d, ff, heads);
-    Arena ws(workspace, workspace_bytes);
-    // each layer's dx and dW products share one grouped launch (every layer has its own buffer set)
+    WsCarve ws(workspace, workspace_bytes);
+    EncLayerWs W[8];
+    enc_bwd_ws(ws, W, layers, RT, d, ff, T <= kSmallAttnMaxT ? 0 : mpo_bag_sa_bwd_floats(BT, T, d, heads));
+    MPO_CHECK(ws.ok(), "encoder backward: workspace too small (%zu bytes)", workspace_bytes);
     const float* dcur = dy;
     const size_t Rd = (size_t)R * d, Rf = (size_t)R * ff, Rq = (size_t)R * 3 * d;
     for (int l = layers - 1; l >= 0; --l) {
-        float* ds2 = ws.floats((size_t)RT * d);
-        float* df = ws.floats((size_t)RT * ff);
-        float* dx1 = ws.floats((size_t)RT * d);
-        float* ds1 = ws.floats((size_t)RT * d);
-        float* dob = ws.floats((size_t)RT * d);
-        float* dqkv = ws.floats((size_t)RT * 3 * d);
-        float* din = l == 0 ? dx : ws.floats((size_t)RT * d);
-        MPO_CHECK(ds2 && df && dx1 && ds1 && dob && dqkv && din, "encoder backward: workspace too small (%zu bytes)", workspace_bytes);
+        float *ds2 = W[l].ds2, *df = W[l].df, *dx1 = W[l].dx1, *ds1 = W[l].ds1, *dob = W[l].dob, *dqkv = W[l].dqkv;
+        float* din = l == 0 ? dx : W[l].din;
         auto P = [&](int br, int i) { return params[((size_t)br * layers + l) * P_PER_LAYER + i]; };
         auto G = [&](int br, int i) { return grads[((size_t)br * layers + l) * P_PER_LAYER + i]; };
         const float* in = l == 0 ? x : S[l - 1].x2;
@@ -223,16 +259,7 @@ int mpo_encoder_backward(const float* x, int n_branches, int n_slides, int T, in
             n1.w[br] = P(br, P_N1W); n1.dw[br] = G(br, P_N1W); n1.db[br] = G(br, P_N1B);
             n2.w[br] = P(br, P_N2W); n2.dw[br] = G(br, P_N2W); n2.db[br] = G(br, P_N2B);
         }
-        // one grouped launch per product pair: members (dx_br, dW_br) for every branch
-        auto pairs = [&](auto&& mk_dx, auto&& mk_dw) -> int {
-            GroupBuilder main_g;
-            for (int br = 0; br < NB; ++br) {
-                RC(main_g.add(mk_dx(br)));
-                RC(main_g.add(mk_dw(br)));
-            }
-            RC(main_g.launch(stream));
-            return 0;
-        };
+        auto pairs = [&](auto&& mk_dx, auto&& mk_dw) { return launch_pairs(NB, stream, mk_dx, mk_dw); };
         // x2 = LN2(s2)
         RC(mpo_launch_ln_bwd_br(dcur, S[l].s2, S[l].st2, n2, ds2, RT, d, 0, 3, stream));
         // s2 = x1 + drop3(f W2^T + b2)
@@ -256,10 +283,8 @@ int mpo_encoder_backward(const float* x, int n_branches, int n_slides, int T, in
         if (T <= kSmallAttnMaxT) {
             RC(mpo_launch_mha_small_bwd(S[l].qkv, S[l].psave, dob, dqkv, BT, T, d, heads, stream));
         } else {
-            float* sa_ws = ws.floats(mpo_bag_sa_bwd_floats(BT, T, d, heads));
-            MPO_CHECK(sa_ws, "encoder backward: workspace too small for the attention scratch (%zu bytes)", workspace_bytes);
             const DropSpec d0 = stream_of(drop_p, seed, base, stride, 0, rng_epoch);
-            RC(mpo_launch_bag_sa_bwd(S[l].qkv, S[l].o, S[l].psave, dob, BT, T, d, heads, d0.p, d0.seed, d0.off, d0.epoch, dqkv, sa_ws, stream));
+            RC(mpo_launch_bag_sa_bwd(S[l].qkv, S[l].o, S[l].psave, dob, BT, T, d, heads, d0.p, d0.seed, d0.off, d0.epoch, dqkv, W[l].sa, stream));
         }
         // qkv = in W_in^T + b_in;  d_in = ds1 + dqkv W_in
         RC(pairs([&](int br) {
@@ -298,20 +323,9 @@ int mpo_bag_self_attention_backward(const float* qkv, const float* out, const fl
 
 // ------------------------------------------------------------------------------------------- K5 gated pooling
 // params: attention_a.0.weight, .bias, attention_b.0.weight, .bias, attention_c.weight, .bias, rho.0.weight, .bias
-// saved: a [R,d] | b [R,d] | ab [R,d] | w [R] | hpool [B,d]      (R, B over all branches)
-size_t mpo_gated_pool_saved_floats(int n_slides, int L, int d) {
-    CarveSizer c;
-    const size_t R = (size_t)n_slides * L;
-    c.take(R * d); c.take(R * d); c.take(R * d); c.take(R); c.take((size_t)n_slides * d);
-    return c.n;
-}
-size_t mpo_gated_pool_workspace_bytes(int n_slides, int L, int d) {
-    const size_t R = (size_t)n_slides * L;
-    Sizer s;
-    s.floats((size_t)n_slides * d); s.floats(R); s.floats(R * d); s.floats(R * d); s.floats(R * d);
-    return s.off + 256;
-}
-uint64_t mpo_gated_pool_rng_span(int n_slides, int L, int d) { return 3 * ((uint64_t)n_slides * L * d / 4 + 2 + kMaxBranches); }
+size_t mpo_gated_pool_saved_floats(int n_slides, int L, int d) { SavedCount c; pool_saved(c, n_slides, L, d); return c.n_floats(); }
+size_t mpo_gated_pool_workspace_bytes(int n_slides, int L, int d) { WsCount c; pool_ws(c, n_slides, L, d); return c.workspace_bytes(); }
+uint64_t mpo_gated_pool_rng_span(int n_slides, int L, int d) { return 3 * pool_stream_stride(n_slides, L, d); }
 
 // AttentionNetGated (models/blocks.py:13-48) + the pooling idiom of models/mcat/mcat.py:105-109:
 // scores = W_c[drop(tanh(W_a x)) * drop(sigmoid(W_b x))] + b_c; h = drop(relu(W_rho (softmax_L(scores) x) + b_rho))
@@ -326,11 +340,11 @@ int mpo_gated_pool_forward(const float* x, int n_branches, int n_slides, int L, 
     MPO_CHECK(n_branches >= 1 && n_branches <= kMaxBranches, "gated pool: 1..%d branches (got %d)", kMaxBranches, n_branches);
     MPO_CHECK(!h_interleaved || (d & 3) == 0, "gated pool: interleaved h needs d %% 4 == 0 (got %d)", d);
     const int NB = n_branches, R = n_slides * L, RT = NB * R, BT = NB * n_slides;
-    const uint64_t stride = (uint64_t)RT * d / 4 + 2 + kMaxBranches;
+    const uint64_t stride = pool_stream_stride(BT, L, d);
     const size_t Rd = (size_t)R * d, Bd = (size_t)n_slides * d;
-    Carver c(saved);
-    float* a = c.take((size_t)RT * d); float* b = c.take((size_t)RT * d); float* ab = c.take((size_t)RT * d);
-    float* w = c.take(RT); float* hpool = c.take((size_t)BT * d);
+    Carve<kPad64> c(saved);
+    const PoolSaved<float> S = pool_saved(c, BT, L, d);
+    float *a = S.a, *b = S.b, *ab = S.ab, *w = S.w, *hpool = S.hpool;
     auto P = [&](int br, int i) { return params[br * 8 + i]; };
     const DropSpec s0 = stream_of(head_drop_p, seed, offset, stride, 0, rng_epoch), s1 = stream_of(head_drop_p, seed, offset, stride, 1, rng_epoch),
                    s2 = stream_of(rho_drop_p, seed, offset, stride, 2, rng_epoch);
@@ -378,27 +392,16 @@ int mpo_gated_pool_backward(const float* x, int n_branches, int n_slides, int L,
     MPO_CHECK(n_branches >= 1 && n_branches <= 2, "gated pool backward: 1..2 branches (got %d)", n_branches);
     const int NB = n_branches, R = n_slides * L, RT = NB * R, BT = NB * n_slides;
     const size_t Rd = (size_t)R * d, Bd = (size_t)n_slides * d;
-    Carver c(const_cast<float*>(saved));
-    const float* a = c.take((size_t)RT * d); const float* b = c.take((size_t)RT * d); const float* ab = c.take((size_t)RT * d);
-    const float* w = c.take(RT); const float* hpool = c.take((size_t)BT * d);
-    Arena ws(workspace, workspace_bytes);
-    float* dhpool = ws.floats((size_t)BT * d);
-    float* dscores = ws.floats(RT);
-    float* dab = ws.floats((size_t)RT * d);
-    float* da = ws.floats((size_t)RT * d);
-    float* db = ws.floats((size_t)RT * d);
-    MPO_CHECK(dhpool && dscores && dab && da && db, "gated pool backward: workspace too small (%zu bytes)", workspace_bytes);
+    Carve<kPad64, const float> c(saved);
+    const PoolSaved<const float> S = pool_saved(c, BT, L, d);
+    const float *a = S.a, *b = S.b, *ab = S.ab, *w = S.w, *hpool = S.hpool;
+    WsCarve ws(workspace, workspace_bytes);
+    const PoolWs W = pool_ws(ws, BT, L, d);
+    MPO_CHECK(ws.ok(), "gated pool backward: workspace too small (%zu bytes)", workspace_bytes);
+    float *dhpool = W.dhpool, *dscores = W.dscores, *dab = W.dab, *da = W.da, *db = W.db;
     auto P = [&](int br, int i) { return params[br * 8 + i]; };
     auto G = [&](int br, int i) { return grads[br * 8 + i]; };
-    auto pairs = [&](auto&& mk_dx, auto&& mk_dw) -> int {
-        GroupBuilder main_g;
-        for (int br = 0; br < NB; ++br) {
-            RC(main_g.add(mk_dx(br)));
-            RC(main_g.add(mk_dw(br)));
-        }
-        RC(main_g.launch(stream));
-        return 0;
-    };
+    auto pairs = [&](auto&& mk_dx, auto&& mk_dw) { return launch_pairs(NB, stream, mk_dx, mk_dw); };
     // h = drop(relu(hpool W_rho^T + b_rho));  h / dh either [branch][n_slides][d] or interleaved [n_slides][branch][d]
     const size_t h_off = h_interleaved ? (size_t)d : Bd;
     const int h_ld = h_interleaved ? NB * d : d;
@@ -449,31 +452,49 @@ int mpo_gated_pool_backward(const float* x, int n_branches, int n_slides, int L,
 
 // ------------------------------------------------------------------------------------------- K6 fusion + head
 // params: fusion_layer.0.weight, .bias, fusion_layer.2.weight, .bias, classifier.weight, .bias
-// saved: z1 [B,hidden] | z2 [B,dout] | logits [B,C]
 size_t mpo_fusion_head_saved_floats(int n_slides, int hidden, int dout, int n_classes) {
-    CarveSizer c;
-    c.take((size_t)n_slides * hidden); c.take((size_t)n_slides * dout); c.take((size_t)n_slides * n_classes);
-    return c.n;
+    SavedCount c;
+    head_saved(c, n_slides, hidden, dout, n_classes, false);
+    return c.n_floats();
+}
+size_t mpo_fusion_head_loss_saved_floats(int n_slides, int hidden, int dout, int n_classes) {
+    SavedCount c;
+    head_saved(c, n_slides, hidden, dout, n_classes, true);
+    return c.n_floats();
 }
 size_t mpo_fusion_head_workspace_bytes(int n_slides, int hidden, int dout, int n_classes) {
-    Sizer s;
-    s.floats((size_t)n_slides * n_classes); s.floats((size_t)n_slides * dout); s.floats((size_t)n_slides * hidden);
-    return s.off + 256;
+    WsCount c;
+    head_ws(c, n_slides, hidden, dout, n_classes);
+    return c.workspace_bytes();
 }
 
-// ConcatFusion (models/fusion.py:7-19) on the concatenated [h_path | h_omic], classifier and the
-// survival head of models/mcat/mcat.py:126-138.
+// ConcatFusion (models/fusion.py:7-19) on the concatenated [h_path | h_omic] and the classifier (models/mcat/mcat.py:126-129)
+static int head_mlp_forward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes, const float* const* P,
+                            const HeadSaved<float>& S, hipStream_t stream) {
+    RC(mpo_linear_fwd(hcat, P[0], P[1], S.z1, n_slides, din, hidden, 1.0f, MPO_ACT_RELU, stream));
+    RC(mpo_linear_fwd(S.z1, P[2], P[3], S.z2, n_slides, hidden, dout, 1.0f, MPO_ACT_RELU, stream));
+    return mpo_linear_fwd(S.z2, P[4], P[5], S.logits, n_slides, dout, n_classes, 1.0f, MPO_ACT_NONE, stream);
+}
+static int head_mlp_backward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes, const float* const* P,
+                             const HeadSaved<const float>& S, const float* dlogits, const HeadWs& W, float* d_hcat,
+                             float* const* G, hipStream_t stream) {
+    PAIR(mpo_args_bwd_input(dlogits, P[4], W.dz2, n_slides, dout, n_classes, 1.0f, 0),
+         mpo_args_bwd_weight(dlogits, S.z2, G[4], G[5], n_slides, dout, n_classes, 1.0f));
+    PAIR(mpo_args_bwd_input(W.dz2, P[2], W.dz1, n_slides, hidden, dout, 1.0f, 0, gate(S.z2, MPO_GATE_RELU)),
+         mpo_args_bwd_weight(W.dz2, S.z1, G[2], G[3], n_slides, hidden, dout, 1.0f, gate(S.z2, MPO_GATE_RELU)));
+    PAIR(mpo_args_bwd_input(W.dz1, P[0], d_hcat, n_slides, din, hidden, 1.0f, 0, gate(S.z1, MPO_GATE_RELU)),
+         mpo_args_bwd_weight(W.dz1, hcat, G[0], G[1], n_slides, din, hidden, 1.0f, gate(S.z1, MPO_GATE_RELU)));
+    return 0;
+}
+
+// ... and the survival head of models/mcat/mcat.py:130-138
 int mpo_fusion_head_forward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes,
                             const float* const* P, float* hazards, float* survs, float* y, float* saved,
                             mpo_stream_t stream) {
-    Carver c(saved);
-    float* z1 = c.take((size_t)n_slides * hidden); float* z2 = c.take((size_t)n_slides * dout);
-    float* logits = c.take((size_t)n_slides * n_classes);
-    RC(mpo_linear_fwd(hcat, P[0], P[1], z1, n_slides, din, hidden, 1.0f, MPO_ACT_RELU, stream));
-    RC(mpo_linear_fwd(z1, P[2], P[3], z2, n_slides, hidden, dout, 1.0f, MPO_ACT_RELU, stream));
-    RC(mpo_linear_fwd(z2, P[4], P[5], logits, n_slides, dout, n_classes, 1.0f, MPO_ACT_NONE, stream));
-    RC(mpo_launch_head_fwd(logits, hazards, survs, y, n_slides, n_classes, stream));
-    return 0;
+    Carve<kPad64> c(saved);
+    const HeadSaved<float> S = head_saved(c, n_slides, hidden, dout, n_classes, false);
+    RC(head_mlp_forward(hcat, n_slides, din, hidden, dout, n_classes, P, S, stream));
+    return mpo_launch_head_fwd(S.logits, hazards, survs, y, n_slides, n_classes, stream);
 }
 
 int mpo_fusion_head_backward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes,
@@ -481,47 +502,28 @@ int mpo_fusion_head_backward(const float* hcat, int n_slides, int din, int hidde
                              const float* y, const float* d_hazards, const float* d_survs, const float* d_y,
                              float* d_hcat, float* const* G, void* workspace, size_t workspace_bytes,
                              mpo_stream_t stream) {
-    Carver c(const_cast<float*>(saved));
-    const float* z1 = c.take((size_t)n_slides * hidden); const float* z2 = c.take((size_t)n_slides * dout);
-    Arena ws(workspace, workspace_bytes);
-    float* dlogits = ws.floats((size_t)n_slides * n_classes);
-    float* dz2 = ws.floats((size_t)n_slides * dout);
-    float* dz1 = ws.floats((size_t)n_slides * hidden);
-    MPO_CHECK(dlogits && dz2 && dz1, "fusion head backward: workspace too small (%zu bytes)", workspace_bytes);
-    RC(mpo_launch_head_bwd(hazards, survs, y, d_hazards, d_survs, d_y, dlogits, n_slides, n_classes, stream));
-    PAIR(mpo_args_bwd_input(dlogits, P[4], dz2, n_slides, dout, n_classes, 1.0f, 0),
-         mpo_args_bwd_weight(dlogits, z2, G[4], G[5], n_slides, dout, n_classes, 1.0f));
-    PAIR(mpo_args_bwd_input(dz2, P[2], dz1, n_slides, hidden, dout, 1.0f, 0, gate(z2, MPO_GATE_RELU)),
-         mpo_args_bwd_weight(dz2, z1, G[2], G[3], n_slides, hidden, dout, 1.0f, gate(z2, MPO_GATE_RELU)));
-    PAIR(mpo_args_bwd_input(dz1, P[0], d_hcat, n_slides, din, hidden, 1.0f, 0, gate(z1, MPO_GATE_RELU)),
-         mpo_args_bwd_weight(dz1, hcat, G[0], G[1], n_slides, din, hidden, 1.0f, gate(z1, MPO_GATE_RELU)));
-    return 0;
+    Carve<kPad64, const float> c(saved);
+    const HeadSaved<const float> S = head_saved(c, n_slides, hidden, dout, n_classes, false);
+    WsCarve ws(workspace, workspace_bytes);
+    const HeadWs W = head_ws(ws, n_slides, hidden, dout, n_classes);
+    MPO_CHECK(ws.ok(), "fusion head backward: workspace too small (%zu bytes)", workspace_bytes);
+    RC(mpo_launch_head_bwd(hazards, survs, y, d_hazards, d_survs, d_y, W.dlogits, n_slides, n_classes, stream));
+    return head_mlp_backward(hcat, n_slides, din, hidden, dout, n_classes, P, S, W.dlogits, W, d_hcat, G, stream);
 }
 
 // Training-step form: the same MLP, then head + 'ces' loss + their backward in ONE launch (head_loss_kernel); the
 // gradient w.r.t. the logits is kept in `saved` and the backward starts at the classifier products.
-// saved: z1 [B,hidden] | z2 [B,dout] | logits [B,C] | d_logits [B,C]
-size_t mpo_fusion_head_loss_saved_floats(int n_slides, int hidden, int dout, int n_classes) {
-    CarveSizer c;
-    c.take((size_t)n_slides * hidden); c.take((size_t)n_slides * dout); c.take((size_t)n_slides * n_classes);
-    c.take((size_t)n_slides * n_classes);
-    return c.n;
-}
 int mpo_fusion_head_loss_forward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes,
                                  const float* const* P, const int64_t* label, const float* censorship,
                                  const float* slide_weight, float alpha, float eps, float* hazards, float* survs, float* y,
                                  float* loss, float* risk, float* saved, mpo_stream_t stream) {
     MPO_CHECK(hcat && P && label && censorship && slide_weight && hazards && survs && y && loss && saved,
               "fusion head + loss forward: null argument");
-    Carver c(saved);
-    float* z1 = c.take((size_t)n_slides * hidden); float* z2 = c.take((size_t)n_slides * dout);
-    float* logits = c.take((size_t)n_slides * n_classes); float* dlogits = c.take((size_t)n_slides * n_classes);
-    RC(mpo_linear_fwd(hcat, P[0], P[1], z1, n_slides, din, hidden, 1.0f, MPO_ACT_RELU, stream));
-    RC(mpo_linear_fwd(z1, P[2], P[3], z2, n_slides, hidden, dout, 1.0f, MPO_ACT_RELU, stream));
-    RC(mpo_linear_fwd(z2, P[4], P[5], logits, n_slides, dout, n_classes, 1.0f, MPO_ACT_NONE, stream));
-    RC(mpo_launch_head_loss(logits, reinterpret_cast<const long long*>(label), censorship, slide_weight, hazards, survs, y,
-                            loss, risk, dlogits, n_slides, n_classes, alpha, eps, static_cast<hipStream_t>(stream)));
-    return 0;
+    Carve<kPad64> c(saved);
+    const HeadSaved<float> S = head_saved(c, n_slides, hidden, dout, n_classes, true);
+    RC(head_mlp_forward(hcat, n_slides, din, hidden, dout, n_classes, P, S, stream));
+    return mpo_launch_head_loss(S.logits, reinterpret_cast<const long long*>(label), censorship, slide_weight, hazards, survs, y,
+                                loss, risk, S.dlogits, n_slides, n_classes, alpha, eps, static_cast<hipStream_t>(stream));
 }
 // The same with the `sct` loss (head_sct_loss_kernel); the backward is mpo_fusion_head_loss_backward unchanged.
 int mpo_fusion_head_sct_loss_forward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes,
@@ -530,35 +532,21 @@ int mpo_fusion_head_sct_loss_forward(const float* hcat, int n_slides, int din, i
                                      float* loss, float* risk, float* saved, mpo_stream_t stream) {
     MPO_CHECK(hcat && P && label && censorship && slide_weight && hazards && survs && y && loss && saved,
               "fusion head + sct loss forward: null argument");
-    Carver c(saved);
-    float* z1 = c.take((size_t)n_slides * hidden); float* z2 = c.take((size_t)n_slides * dout);
-    float* logits = c.take((size_t)n_slides * n_classes); float* dlogits = c.take((size_t)n_slides * n_classes);
-    RC(mpo_linear_fwd(hcat, P[0], P[1], z1, n_slides, din, hidden, 1.0f, MPO_ACT_RELU, stream));
-    RC(mpo_linear_fwd(z1, P[2], P[3], z2, n_slides, hidden, dout, 1.0f, MPO_ACT_RELU, stream));
-    RC(mpo_linear_fwd(z2, P[4], P[5], logits, n_slides, dout, n_classes, 1.0f, MPO_ACT_NONE, stream));
-    RC(mpo_launch_head_sct_loss(logits, reinterpret_cast<const long long*>(label), censorship, slide_weight, hazards, survs,
-                                y, loss, risk, dlogits, n_slides, n_classes, eps, static_cast<hipStream_t>(stream)));
-    return 0;
+    Carve<kPad64> c(saved);
+    const HeadSaved<float> S = head_saved(c, n_slides, hidden, dout, n_classes, true);
+    RC(head_mlp_forward(hcat, n_slides, din, hidden, dout, n_classes, P, S, stream));
+    return mpo_launch_head_sct_loss(S.logits, reinterpret_cast<const long long*>(label), censorship, slide_weight, hazards, survs,
+                                    y, loss, risk, S.dlogits, n_slides, n_classes, eps, static_cast<hipStream_t>(stream));
 }
 int mpo_fusion_head_loss_backward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes,
                                   const float* const* P, const float* saved, float* d_hcat, float* const* G,
                                   void* workspace, size_t workspace_bytes, mpo_stream_t stream) {
-    Carver c(const_cast<float*>(saved));
-    const float* z1 = c.take((size_t)n_slides * hidden); const float* z2 = c.take((size_t)n_slides * dout);
-    c.take((size_t)n_slides * n_classes);
-    const float* dlogits = c.take((size_t)n_slides * n_classes);
-    Arena ws(workspace, workspace_bytes);
-    ws.floats((size_t)n_slides * n_classes);                    // (layout of mpo_fusion_head_workspace_bytes)
-    float* dz2 = ws.floats((size_t)n_slides * dout);
-    float* dz1 = ws.floats((size_t)n_slides * hidden);
-    MPO_CHECK(dz2 && dz1, "fusion head + loss backward: workspace too small (%zu bytes)", workspace_bytes);
-    PAIR(mpo_args_bwd_input(dlogits, P[4], dz2, n_slides, dout, n_classes, 1.0f, 0),
-         mpo_args_bwd_weight(dlogits, z2, G[4], G[5], n_slides, dout, n_classes, 1.0f));
-    PAIR(mpo_args_bwd_input(dz2, P[2], dz1, n_slides, hidden, dout, 1.0f, 0, gate(z2, MPO_GATE_RELU)),
-         mpo_args_bwd_weight(dz2, z1, G[2], G[3], n_slides, hidden, dout, 1.0f, gate(z2, MPO_GATE_RELU)));
-    PAIR(mpo_args_bwd_input(dz1, P[0], d_hcat, n_slides, din, hidden, 1.0f, 0, gate(z1, MPO_GATE_RELU)),
-         mpo_args_bwd_weight(dz1, hcat, G[0], G[1], n_slides, din, hidden, 1.0f, gate(z1, MPO_GATE_RELU)));
-    return 0;
+    Carve<kPad64, const float> c(saved);
+    const HeadSaved<const float> S = head_saved(c, n_slides, hidden, dout, n_classes, true);
+    WsCarve ws(workspace, workspace_bytes);
+    const HeadWs W = head_ws(ws, n_slides, hidden, dout, n_classes);
+    MPO_CHECK(ws.ok(), "fusion head + loss backward: workspace too small (%zu bytes)", workspace_bytes);
+    return head_mlp_backward(hcat, n_slides, din, hidden, dout, n_classes, P, S, S.dlogits, W, d_hcat, G, stream);
 }
 
 // ------------------------------------------------------------------------------------------- survival head alone
@@ -610,28 +598,16 @@ int mpo_sct_loss_backward(const float* y, const int64_t* label, const float* cen
 
 // ------------------------------------------------------------------------------------------- K3 CAG
 // params: fc1.0.weight,.bias, fc2.0.weight,.bias, fc3.0.weight,.bias, G.1.weight,.bias, E.1.weight,.bias, fc_c.0.weight,.bias
-// saved: u1 u2 u3 t1 t3 G E m  [R,h each] | stats_g [R,2] | stats_e [R,2]
-size_t mpo_cag_saved_floats(int rows, int hidden) {
-    CarveSizer c;
-    for (int i = 0; i < 8; ++i) c.take((size_t)rows * hidden);
-    c.take(2 * (size_t)rows); c.take(2 * (size_t)rows);
-    return c.n;
-}
-size_t mpo_cag_workspace_bytes(int rows, int hidden) {
-    Sizer s;
-    for (int i = 0; i < 5; ++i) s.floats((size_t)rows * hidden);
-    return s.off + 256;
-}
+size_t mpo_cag_saved_floats(int rows, int hidden) { SavedCount c; cag_saved(c, rows, hidden); return c.n_floats(); }
+size_t mpo_cag_workspace_bytes(int rows, int hidden) { WsCount c; cag_ws(c, rows, hidden); return c.workspace_bytes(); }
 
 // ContextualAttentionGate.forward, models/blocks.py:247-253
 int mpo_cag_forward(const float* q, const float* q_hat, int rows, int dim, int hidden, const float* const* P,
                     float* c_out, float* saved, const float* residual, float* sum_out, mpo_stream_t stream) {
     MPO_CHECK((residual == nullptr) == (sum_out == nullptr), "CAG forward: residual and sum_out go together");
-    Carver c(saved);
-    float* u1 = c.take((size_t)rows * hidden); float* u2 = c.take((size_t)rows * hidden); float* u3 = c.take((size_t)rows * hidden);
-    float* t1 = c.take((size_t)rows * hidden); float* t3 = c.take((size_t)rows * hidden);
-    float* g = c.take((size_t)rows * hidden); float* e = c.take((size_t)rows * hidden); float* m = c.take((size_t)rows * hidden);
-    float* sg = c.take(2 * (size_t)rows); float* se = c.take(2 * (size_t)rows);
+    Carve<kPad64> c(saved);
+    const CagSaved<float> S = cag_saved(c, rows, hidden);
+    float *u1 = S.u1, *u2 = S.u2, *u3 = S.u3, *t1 = S.t1, *t3 = S.t3, *g = S.g, *e = S.e, *m = S.m, *sg = S.sg, *se = S.se;
     {
         const GemmArgs g3 = mpo_args_fwd(q_hat, P[4], P[5], u3, rows, dim, hidden, 1.0f, MPO_ACT_ELU);
         RC(mpo_gemm_together(stream, mpo_args_fwd(q, P[0], P[1], u1, rows, dim, hidden, 1.0f, MPO_ACT_ELU),
@@ -652,17 +628,13 @@ int mpo_cag_forward(const float* q, const float* q_hat, int rows, int dim, int h
 int mpo_cag_backward(const float* q, const float* q_hat, int rows, int dim, int hidden, const float* const* P,
                      const float* saved, const float* c_out, const float* d_c, float* d_q, int d_q_accumulate, float* d_q_hat,
                      float* const* G, void* workspace, size_t workspace_bytes, mpo_stream_t stream) {
-    Carver c(const_cast<float*>(saved));
-    const float* u1 = c.take((size_t)rows * hidden); const float* u2 = c.take((size_t)rows * hidden);
-    const float* u3 = c.take((size_t)rows * hidden); const float* t1 = c.take((size_t)rows * hidden);
-    const float* t3 = c.take((size_t)rows * hidden); const float* g = c.take((size_t)rows * hidden);
-    const float* e = c.take((size_t)rows * hidden); const float* m = c.take((size_t)rows * hidden);
-    const float* sg = c.take(2 * (size_t)rows); const float* se = c.take(2 * (size_t)rows);
-    Arena ws(workspace, workspace_bytes);
-    float* dm = ws.floats((size_t)rows * hidden); float* dG = ws.floats((size_t)rows * hidden);
-    float* dE = ws.floats((size_t)rows * hidden); float* ds12 = ws.floats((size_t)rows * hidden);
-    float* ds3 = ws.floats((size_t)rows * hidden);
-    MPO_CHECK(dm && dG && dE && ds12 && ds3, "CAG backward: workspace too small (%zu bytes)", workspace_bytes);
+    Carve<kPad64, const float> c(saved);
+    const CagSaved<const float> S = cag_saved(c, rows, hidden);
+    const float *u1 = S.u1, *u2 = S.u2, *u3 = S.u3, *t1 = S.t1, *t3 = S.t3, *g = S.g, *e = S.e, *m = S.m, *sg = S.sg, *se = S.se;
+    WsCarve ws(workspace, workspace_bytes);
+    const CagWs W = cag_ws(ws, rows, hidden);
+    MPO_CHECK(ws.ok(), "CAG backward: workspace too small (%zu bytes)", workspace_bytes);
+    float *dm = W.dm, *dG = W.dG, *dE = W.dE, *ds12 = W.ds12, *ds3 = W.ds3;
     // C = ELU(m Wc^T + bc)
     RC(mpo_linear_bwd_pair(mpo_args_bwd_input(d_c, P[10], dm, rows, hidden, hidden, 1.0f, 0, gate(c_out, MPO_GATE_ELU)),
                            mpo_args_bwd_weight(d_c, m, G[10], G[11], rows, hidden, hidden, 1.0f, gate(c_out, MPO_GATE_ELU)), stream));
@@ -690,26 +662,27 @@ int mpo_cag_backward(const float* q, const float* q_hat, int rows, int dim, int 
 // the second layer writes straight into G_bag [n_slides, n_groups, d] (row stride n_groups * d).
 // params per group: 0.0.weight [d, width_i], 0.0.bias, 1.0.weight [d, d], 1.0.bias        saved: u1 [n_groups][n_slides, d]
 size_t mpo_omic_snn_saved_floats(int n_slides, int n_groups, int d) {
-    CarveSizer c;
-    for (int i = 0; i < n_groups; ++i) c.take((size_t)n_slides * d);
-    return c.n;
+    SavedCount c;
+    snn_blocks(c, n_groups, n_slides, d);
+    return c.n_floats();
 }
 size_t mpo_omic_snn_workspace_bytes(int n_slides, int n_groups, int d) {
-    Sizer s;
-    for (int i = 0; i < n_groups; ++i) s.floats((size_t)n_slides * d);
-    return s.off + 256;
+    WsCount c;
+    snn_blocks(c, n_groups, n_slides, d);
+    return c.workspace_bytes();
 }
-uint64_t mpo_omic_snn_rng_span(int n_slides, int n_groups, int d) { return 2ull * n_groups * ((uint64_t)n_slides * n_groups * d / 4 + 2); }
+uint64_t mpo_omic_snn_rng_span(int n_slides, int n_groups, int d) { return 2ull * n_groups * snn_stream_stride(n_slides, n_groups, d); }
 
 int mpo_omic_snn_forward(const float* const* x, const int* widths, int n_groups, int n_slides, int d,
                          const float* const* params, float drop_p, uint64_t seed, uint64_t offset,
                          const uint64_t* rng_epoch, float* g_bag, float* saved, mpo_stream_t stream) {
     MPO_CHECK(n_groups >= 1, "omic SNN: at least one group (got %d)", n_groups);
-    const uint64_t stride = (uint64_t)n_slides * n_groups * d / 4 + 2;
-    Carver c(saved);
+    const uint64_t stride = snn_stream_stride(n_slides, n_groups, d);
+    Carve<kPad64> c(saved);
+    const std::vector<float*> u1s = snn_blocks(c, n_groups, n_slides, d);
     std::vector<GemmArgs> l1(n_groups), l2(n_groups);
     for (int i = 0; i < n_groups; ++i) {
-        float* u1 = c.take((size_t)n_slides * d);
+        float* u1 = u1s[i];
         const float* const* P = params + 4 * i;
         GemmArgs& a = l1[i];
         a.A = x[i]; a.B = P[0]; a.bias = P[1]; a.C = u1;
@@ -732,15 +705,17 @@ int mpo_omic_snn_backward(const float* const* x, const int* widths, int n_groups
                           const uint64_t* rng_epoch, const float* g_bag, const float* saved, const float* d_g_bag,
                           float* const* grads, void* workspace, size_t workspace_bytes, mpo_stream_t stream) {
     MPO_CHECK(n_groups >= 1, "omic SNN: at least one group (got %d)", n_groups);
-    const uint64_t stride = (uint64_t)n_slides * n_groups * d / 4 + 2;
-    Carver c(const_cast<float*>(saved));
-    Arena ws(workspace, workspace_bytes);
+    const uint64_t stride = snn_stream_stride(n_slides, n_groups, d);
+    Carve<kPad64, const float> c(saved);
+    const std::vector<const float*> u1s = snn_blocks(c, n_groups, n_slides, d);
+    WsCarve ws(workspace, workspace_bytes);
+    const std::vector<float*> du1s = snn_blocks(ws, n_groups, n_slides, d);
+    MPO_CHECK(ws.ok(), "omic SNN backward: workspace too small (%zu bytes)", workspace_bytes);
     std::vector<GemmArgs> dx(n_groups), dw2(n_groups), dw1(n_groups);
     const unsigned long long* ep = reinterpret_cast<const unsigned long long*>(rng_epoch);
     for (int i = 0; i < n_groups; ++i) {
-        const float* u1 = c.take((size_t)n_slides * d);
-        float* du1 = ws.floats((size_t)n_slides * d);
-        MPO_CHECK(du1, "omic SNN backward: workspace too small (%zu bytes)", workspace_bytes);
+        const float* u1 = u1s[i];
+        float* du1 = du1s[i];
         const float* const* P = params + 4 * i;
         float* const* G = grads + 4 * i;
         const float* dy = d_g_bag + (size_t)i * d;          // [n_slides, d] with row stride n_groups * d

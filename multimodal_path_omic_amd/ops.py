@@ -303,8 +303,8 @@ def _bias_grad_slot(bag_param, E, dev):
         return bag_param._mpo_grad_view.view(E)         # (PatchFcFn.backward's grad_out(bias) then claims this slice)
     return torch.empty(E, device=dev, dtype=torch.float32)
 
-# Data-parallel steps split the backward in two: everything except the patch layer's weight gradient (dW_H = g^T X, a
-# 0.3 ms library GEMM that nothing downstream waits for) runs first, then the all-reduce of all other gradients is
+# Data-parallel steps split the backward in two: everything except the patch layer's weight gradient (dW_H = g^T X on
+# csrc/patch_wgrad.hip, which nothing downstream waits for) runs first, then the all-reduce of all other gradients is
 # started and dW_H is computed WHILE that collective runs (harness.GraphedWindowStep(split_patch_grad=True)).
 defer_patch_weight_grad = False
 _deferred_patch = []
@@ -314,6 +314,15 @@ def flush_patch_weight_grads():
     for g, x, dw in _deferred_patch:
         patch_weight_grad(g, x, dw)
     _deferred_patch.clear()
+
+def _patch_weight_grad_now_or_deferred(g, x, dw, weight):
+    """dW_H = g^T X into dw: queued for flush_patch_weight_grads() when the split exchange is on and dw IS the weight's slice
+    of the flat gradient bucket (the caller has already returned it), else computed now."""
+    if defer_patch_weight_grad and getattr(weight, "_mpo_grad_view", None) is not None \
+            and dw.data_ptr() == weight._mpo_grad_view.data_ptr():
+        _deferred_patch.append((g, x, dw))
+    else:
+        patch_weight_grad(g, x, dw)
 
 
 # ------------------------------------------------------------------------------------ patch layer (row H2)
@@ -369,11 +378,7 @@ class PatchFcFn(torch.autograd.Function):
                 stats["colsum_handoffs"] += 1
             else:
                 _colsum_two_stage(g, db)
-        if defer_patch_weight_grad and getattr(ctx.param_refs[0], "_mpo_grad_view", None) is not None \
-                and dw.data_ptr() == ctx.param_refs[0]._mpo_grad_view.data_ptr():
-            _deferred_patch.append((g, x, dw))      # dw aliases the bucket slice: filled by flush_patch_weight_grads()
-        else:
-            patch_weight_grad(g, x, dw)
+        _patch_weight_grad_now_or_deferred(g, x, dw, ctx.param_refs[0])
         return None, dw, db, None, None, None
 
 
@@ -483,10 +488,11 @@ def patch_fc_f32(x, weight, bias, drop_p: float):
     return PatchFcF32Fn.apply(x, weight, bias, float(drop_p))
 
 
-# ------------------------------------------------------------------------------------ row f1: patch layer + K1 in one pass
+# ------------------------------------------------------------------------------------ row f1: patch layer + K1 in one call
 class PatchCoAttnMCATFn(torch.autograd.Function):
-    """H_bag = dropout_p(relu(X W_H^T + b_H)) AND MCAT's co-attention over it (models/mcat/mcat.py:24-29,87,97) with ONE
-    pass over the raw bf16 patch matrix: mpo_patch_coattn_mcat_forward.  H_bag is written once (bf16) and kept for the
+    """H_bag = dropout_p(relu(X W_H^T + b_H)) AND MCAT's co-attention over it (models/mcat/mcat.py:24-29,87,97) in ONE
+    C-ABI call, mpo_patch_coattn_mcat_forward: two bag launches, the patch-layer kernel over the raw bf16 patch matrix and K1's
+    partial pass over the H_bag it wrote.  H_bag is written once (bf16) and kept for the
     backward, which is K1's backward pass (d_bag arrives already multiplied by the ReLU / dropout derivative, with its
     column sums = the patch layer's bias gradient) followed by the patch layer's weight gradient g^T X."""
 
@@ -542,11 +548,7 @@ class PatchCoAttnMCATFn(torch.autograd.Function):
             L.ptr(g), L.ptr(d_pb), L.ptr(d_in_w), L.ptr(d_in_b), L.ptr(d_out_w), L.ptr(d_out_b), ctx.gate, batch.plan(),
             L.ptr(ws), ws.numel(), L.stream_of(query)), "mpo_coattn_mcat_backward")
         stats["colsum_handoffs"] += 1
-        if defer_patch_weight_grad and getattr(patch_w, "_mpo_grad_view", None) is not None \
-                and d_pw.data_ptr() == patch_w._mpo_grad_view.data_ptr():
-            _deferred_patch.append((g, x, d_pw))   # filled by flush_patch_weight_grads() (data-parallel split exchange)
-        else:
-            patch_weight_grad(g, x, d_pw)
+        _patch_weight_grad_now_or_deferred(g, x, d_pw, patch_w)
         return None, d_pw, d_pb, d_query, d_in_w, d_in_b, d_out_w, d_out_b, None, None, None, None, None
 
 

@@ -218,3 +218,55 @@ def test_feature_scale_cache_follows_in_place_writes():
     assert ops.feature_scale(xi) == fresh(xi)
     assert ops.feature_scale(torch.zeros(4, 1024)) == 1.0
     assert ops.feature_scale(torch.empty(0, 1024)) == 1.0
+
+
+# Queries whose parent-commit value exceeded what their entry carves: the recorded value is an upper bound for them.
+#   mpo_encoder_workspace_bytes: the hand-written sum counted a seventh rows x d block for layer 0 (whose d_in is the caller's
+#   dx) and, on long token axes, an extra rows x d beside the attention scratch; the query now runs the backward's own layout
+#   function for 8 layers and the head count with the largest scratch.
+LAYOUT_QUERIES_THAT_MAY_SHRINK = {"mpo_encoder_workspace_bytes"}
+
+
+def test_size_queries_equal_the_recorded_layouts():
+    """Every saved_floats / workspace_bytes / rng_span query over a grid of geometries that reaches every branch of the buffer
+    layouts (tests/golden/layout_sizes.json: [query, arguments, value], recorded from the build before the layouts moved into
+    single definitions).  Callers size `saved` and `workspace` by these numbers and the entries carve them with the same
+    layout functions, so a query that moves by one byte is a changed buffer layout."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "layout_sizes.json")) as f:
+        rows = json.load(f)
+    assert len(rows) >= 2000
+    lib, seen = L.lib(), set()
+    for name, args, want in rows:
+        got = getattr(lib, name)(*args)
+        seen.add(name)
+        if name in LAYOUT_QUERIES_THAT_MAY_SHRINK:
+            assert got <= want, (name, args, got, want)
+        else:
+            assert got == want, (name, args, got, want)
+    queries = {n for n in L.exported_symbols() if n.endswith(("_saved_floats", "_workspace_bytes", "_rng_span"))}
+    assert seen == queries
+
+
+def test_entries_refuse_a_short_workspace_before_their_first_launch():
+    """An entry checks workspace_bytes once, against its own layout, before it launches anything: on a machine without a GPU
+    the refusal is the 'workspace too small' error (rc 1), not a failed launch.  One byte short of the layout where the
+    query is exactly layout + 256 bytes of slack, an empty workspace elsewhere."""
+    lib = L.lib()
+    N = None
+    short = lambda query_bytes: query_bytes - 256 - 1
+    calls = {
+        "mpo_cag_backward": (N, N, 48, 256, 256, N, N, N, N, N, 0, N, N, N, short(lib.mpo_cag_workspace_bytes(48, 256)), N),
+        "mpo_gated_pool_backward": (N, 2, 8, 6, 256, N, 0.25, 0.25, N, N, N, 1, N, N, N, N,
+                                    short(lib.mpo_gated_pool_workspace_bytes(16, 6, 256)), N),
+        "mpo_fusion_head_backward": (N, 8, 512, 256, 256, 4) + (N,) * 11 + (short(lib.mpo_fusion_head_workspace_bytes(8, 256, 256, 4)), N),
+        "mpo_fusion_head_loss_backward": (N, 8, 512, 256, 256, 4, N, N, N, N, N, short(lib.mpo_fusion_head_workspace_bytes(8, 256, 256, 4)), N),
+        "mpo_omic_snn_backward": (N, N, 6, 8, 256, N, 0.25, 0, 0, N, N, N, N, N, N, short(lib.mpo_omic_snn_workspace_bytes(8, 6, 256)), N),
+        "mpo_encoder_backward": (N, 2, 8, 6, 256, 512, 8, 2, N, 0.25, 0, 0, N, N, N, N, N, N, 0, N),
+        "mpo_coattn_mcat_forward": (N, L.MPO_BF16, N, 8, 8000, 1000, N, 6, 256) + (N,) * 9 + (0, N),
+        "mpo_coattn_mcat_backward": (N, L.MPO_BF16, N, 8, 8000, 1000, N, 6, 256) + (N,) * 7 + (0,) + (N,) * 6 + (1.0, N, N, 0, N),
+        "mpo_coattn_nacagat_forward": (N, L.MPO_F32, N, L.MPO_BF16, N, 8, 8000, 1000, N, 6, 512, N, N, N, N, 0.25, 0, 0) + (N,) * 8 + (0, N),
+    }
+    for name, args in calls.items():
+        assert getattr(lib, name)(*args) == 1, name
+        assert b"workspace too small" in lib.mpo_last_error(), (name, lib.mpo_last_error())
