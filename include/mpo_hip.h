@@ -462,6 +462,24 @@ int mpo_fusion_head_sct_loss_forward(const float* hcat, int n_slides, int din, i
                                      const float* slide_weight, float eps, float* hazards, float* survs, float* y,
                                      float* loss, float* risk /* nullable */, float* saved, mpo_stream_t stream);
 
+/* ---- training-step head of the gene-expression model: classifier + softmax (models/ge_nacagat/ge_nacagat.py:63-67) and
+ * the reference's `ce` loss (models/ge_nacagat/main.py:33: nn.CrossEntropyLoss applied to the ALREADY soft-maxed Y, i.e.
+ * loss_b = logsumexp(Y_b) - Y_b[label_b]) for n_bags bags, ONE launch each way.  h [n_bags, d] is the pooling head's rho
+ * output; params = classifier.weight [n_classes, d], classifier.bias; y [n_bags, n_classes], loss [n_bags].
+ * The backward takes the per-bag upstream gradient d_loss (n_bags floats; 1 / grad_acc_step in the reference's loop,
+ * main.py:51) and OVERWRITES d_h [n_bags, d] and grads = d classifier.weight, d classifier.bias.  It keeps no state from
+ * the forward (no `saved`, no workspace, hence no size query): it forms the n_classes logits of a bag again from h.  dW and
+ * db are summed over the bags in bag order by one workgroup per class (no atomics) -- sized for the bags of one
+ * accumulation window, not for thousands.
+ * d in {128, 256, 512}, n_classes in 2..8; anything else is refused (rc 1, mpo_last_error()).  A label outside
+ * [0, n_classes) is FLAGGED, not clamped: that bag's loss is NaN, its y is still the softmax, and it contributes zero to
+ * every gradient; nothing is read out of bounds.  Additive to ABI 14. */
+int mpo_ge_head_loss_forward(const float* h, int n_bags, int d, int n_classes, const float* const* params,
+                             const int64_t* label, float* y, float* loss, mpo_stream_t stream);
+int mpo_ge_head_loss_backward(const float* h, int n_bags, int d, int n_classes, const float* const* params,
+                              const int64_t* label, const float* d_loss, float* d_h, float* const* grads,
+                              mpo_stream_t stream);
+
 /* ---- K3: ContextualAttentionGate.forward (models/blocks.py:232-253) on rows of (Q, Q_hat).
  * 12 pointers: fc1.0.weight,.bias, fc2.0.weight,.bias, fc3.0.weight,.bias, G.1.weight,.bias, E.1.weight,.bias,
  * fc_c.0.weight,.bias */

@@ -106,6 +106,8 @@ _SIGNATURES = {
     "mpo_sct_loss_forward": (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, _P]),
     "mpo_sct_loss_backward": (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, c_int, _P, _P]),
     "mpo_fusion_head_sct_loss_forward": (c_int, [_P] + [c_int] * 5 + [_P, _P, _P, _P, c_float] + [_P] * 6 + [_P]),
+    "mpo_ge_head_loss_forward": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "mpo_ge_head_loss_backward": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "mpo_optim_step_flat": (c_int, [c_int, _P, _P, _P, _P, ctypes.c_int64, c_float, _P, c_float, c_float, c_float, c_float,
                                     c_float, c_int, _P, _P]),
     "mpo_abs_sum_flat_workspace_bytes": (c_size_t, [ctypes.c_int64]),

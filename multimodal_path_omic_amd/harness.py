@@ -71,6 +71,26 @@ CE_REFUSAL = ("loss 'ce' cannot train these models: the reference computes nn.Cr
               "('0D or 1D target tensor expected') -- there is no behaviour to reproduce; use 'ces' or 'sct'")
 
 
+def make_ge_window(slides: Sequence[dict], device, bag_dtype=torch.float32):
+    """List of gene-expression slide dicts ({'wsi': (M, 1024), 'gene_expr_class': int}, the pairs
+    dataset/ge_dataset.py yields) -> (BagBatch, labels (B,) int64)."""
+    bags = BagBatch.from_list([s["wsi"].to(device=device, dtype=bag_dtype, non_blocking=True) for s in slides])
+    labels = torch.tensor([int(s["gene_expr_class"]) for s in slides], dtype=torch.int64).to(device, non_blocking=True)
+    return bags, labels
+
+
+def train_ge_window(model, bags: BagBatch, labels, grad_acc_step: int, l1: float = 0.0):
+    """Forward + backward of one window of the gene-expression model (models/ge_nacagat/main.py:24-52): the `ce` loss on Y
+    in the head's launch, gradients ACCUMULATE into .grad with the reference's 1 / grad_acc_step per bag (main.py:51), no
+    M x M map is allocated.  Returns the per-bag loss (B,) on the device -- no host sync.  l1: as in train_window (the
+    REPORTED loss gains l1 * sum|W|, main.py:41-43; the penalty's gradient is folded by dp.FlatOptimizer)."""
+    w = _slide_weights(bags.n_slides, grad_acc_step, labels.device)
+    _, att = model.forward_window(bags, need_maps=False, ce_targets=(labels, w))
+    per_bag = att["loss"]
+    per_bag.backward(w)
+    return _with_penalty(model, per_bag.detach(), l1)
+
+
 def train_window(model, bags: BagBatch, omics, labels, cens, grad_acc_step: int, loss: str = "ces", lambda_reg: float = 0.01,
                  alpha: float = 0.75, l1: float = 0.0):
     """Forward + backward of one window; gradients ACCUMULATE into .grad with the reference's
@@ -129,15 +149,16 @@ def weights_abs_sum(model) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------ the reference's training: config
-LOSSES = {"mcat": ("ces", "sct"), "nacagat": ("ces", "sct", "cesar")}
+LOSSES = {"mcat": ("ces", "sct"), "nacagat": ("ces", "sct", "cesar"), "ge_nacagat": ("ce",)}
 OPTIMISERS = ("adam", "adamax", "adadelta", "sgd")
 
 
 @dataclass
 class TrainOptions:
     """The reference's `training:` choices as this package runs them (models/mcat/main.py:272-318,
-    models/nacagat/main.py:283-296).  train_kwargs() feeds train_window / GraphedWindowStep; make_optimizer() and
-    make_scheduler() build the flat optimiser (with the L1 fold) and the per-epoch schedule."""
+    models/nacagat/main.py:283-296, models/ge_nacagat/main.py:223-263).  train_kwargs() feeds train_window /
+    GraphedWindowStep (for the gene-expression model, whose only loss is `ce`: train_ge_window(..., l1=o.l1));
+    make_optimizer() and make_scheduler() build the flat optimiser (with the L1 fold) and the per-epoch schedule."""
     loss: str
     alpha: float
     lambda_reg: float             # cesar's attention-map weight (fixed 0.01 in the reference)
@@ -164,12 +185,13 @@ class TrainOptions:
 def training_options(training: dict, model: str = "mcat") -> TrainOptions:
     """The reference's `training:` config dict -> TrainOptions, by the reference's own mapping: an unknown loss raises;
     'cesar' exists for NaCAGaT only and always runs with alpha 0.75, lambda_reg 0.01 (CrossEntropySurvivalAttnRegLoss());
-    'ce' raises (CE_REFUSAL); unknown optimiser names (e.g. 'rms') become 'adam'; 'sgd' gets no weight decay;
+    'ce' raises for the fusion models (CE_REFUSAL) and is the one loss of 'ge_nacagat' (models/ge_nacagat/main.py:223-227, where
+    the call is well-formed); unknown optimiser names (e.g. 'rms') become 'adam'; 'sgd' gets no weight decay;
     lambda 0 / None means no penalty; any scheduler other than 'exp' means none."""
     if model not in LOSSES:
-        raise ValueError(f"model '{model}' has no training loop here (mcat | nacagat)")
+        raise ValueError(f"model '{model}' has no training loop here ({' | '.join(LOSSES)})")
     loss = training["loss"]
-    if loss == "ce":
+    if loss == "ce" and "ce" not in LOSSES[model]:
         raise ValueError(CE_REFUSAL)
     if loss not in LOSSES[model]:
         raise ValueError(f'Loss "{loss}" not implemented for {model} ({" | ".join(LOSSES[model])})')
@@ -205,6 +227,10 @@ class GraphedWindowStep:
     Frozen-at-capture values that must change per step live on the device: the dropout epoch (ops.set_rng_epoch,
     bumped inside the graph) and Adam's step count (dp.FlatAdam.t_dev).  With world_size > 1 leave the optimiser
     out (`opt=None`): replay, then all-reduce the bucket and step eagerly.
+
+    The gene-expression model takes the window (bags, labels) of make_ge_window: the body is train_ge_window (its one
+    loss, `ce`), the call returns the per-bag loss alone, and split_patch_grad is refused (no data-parallel exchange is
+    built for that model).
     """
 
     def __init__(self, model, bucket, window, grad_acc_step: int, opt=None, warmup: int = 2, pool=None,
@@ -222,6 +248,12 @@ class GraphedWindowStep:
         self.train_kwargs = dict(loss=loss, alpha=alpha, lambda_reg=lambda_reg, l1=self.l1)
         self.window, self.acc = window, grad_acc_step
         self.split = bool(split_patch_grad)
+        self.ge = len(window) == 2                          # (bags, labels): the gene-expression model's window
+        if self.ge and self.split:
+            raise ValueError("split_patch_grad is built for the fusion models' data-parallel steps, not for the "
+                             "gene-expression model")
+        if self.ge and loss not in ("ces", "ce"):           # ('ces' is this constructor's default)
+            raise ValueError(f"loss '{loss}' is not built for the gene-expression model (ce)")
         if self.split and opt is not None:
             raise ValueError("split_patch_grad is for steps whose optimiser runs after an all-reduce (opt=None)")
         self.tail_graph = None
@@ -249,7 +281,8 @@ class GraphedWindowStep:
         self._fp32_window_version = bag_data._version if bag_data.dtype == torch.float32 else None
         # thread_local: other threads (RCCL's watchdog under torch.distributed) may issue HIP calls meanwhile
         with torch.cuda.graph(self.graph, pool=pool, capture_error_mode="thread_local"):
-            self.loss, self.risk = self._body(flush=not self.split)
+            out = self._body(flush=not self.split)
+        self.loss, self.risk = (out, None) if self.ge else out
         if self.split:
             self._held = list(ops._deferred_patch)          # keep the queued operands alive between the two graphs
             self.tail_graph = torch.cuda.CUDAGraph()
@@ -274,12 +307,16 @@ class GraphedWindowStep:
         from . import ops
         ops.bump_step_counters(self.epoch, self.opt.t_dev if self.opt is not None else None)   # one launch for both
         self.bucket.begin()
-        bags, omics, labels, cens = self.window
-        ops.defer_patch_weight_grad = self.split
-        try:
-            out = train_window(self.model, bags, omics, labels, cens, self.acc, **self.train_kwargs)
-        finally:
-            ops.defer_patch_weight_grad = False
+        bags = self.window[0]
+        if self.ge:
+            out = train_ge_window(self.model, bags, self.window[1], self.acc, l1=self.l1)
+        else:
+            _, omics, labels, cens = self.window
+            ops.defer_patch_weight_grad = self.split
+            try:
+                out = train_window(self.model, bags, omics, labels, cens, self.acc, **self.train_kwargs)
+            finally:
+                ops.defer_patch_weight_grad = False
         self.bucket.finish()
         if self.split and flush:
             ops.flush_patch_weight_grads()
@@ -306,4 +343,4 @@ class GraphedWindowStep:
             raise RuntimeError("GraphedWindowStep: the fp32 window was written in place after capture; its feature scale "
                                "is baked into the graph -- capture a new step for the new contents")
         self.graph.replay()
-        return self.loss, self.risk
+        return self.loss if self.ge else (self.loss, self.risk)

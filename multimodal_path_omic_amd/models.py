@@ -265,5 +265,45 @@ class GeneExprNarrowContextualAttentionGateTransformer(nn.Module):
         y = torch.softmax(logits, dim=0)          # F.softmax without dim on a vector (ge_nacagat.py:67)
         return y, {"attn": a_coattn, "path": a_path[0]}
 
+    # bags this short take the token tail's short-axis kernels (T <= 16), whose window form is not verified here
+    MIN_WINDOW_ROWS = 17
+
+    def forward_window(self, bags: BagBatch, need_maps: bool = False, ce_targets=None):
+        """bags: raw patch features (total_rows, 1024) of a window of B bags.
+        Returns Y (B, C) and {'attn': [ (M_b, M_b) ] | None, 'path': [ (1, M_b) ]}.
+        ce_targets = (labels (B,), slide_weight (B,) fp32) (training step): the `ce` loss of models/ge_nacagat/main.py:33 and
+        its backward ride in the head's launch (ops.ge_head_loss); the dict gains 'loss' (per bag), and backward is driven as
+        loss.backward(slide_weight).
+
+        The patch layer runs once over the ragged window.  Self-attention, set-Transformer and pooling take a uniform row
+        count, so they run bag by bag on that bag's rows (a bag costs milliseconds, its launches nothing measurable); the
+        pooled rows are gathered and go through ONE head launch.  need_maps=False hands the attention kernel no map to
+        write: a training step allocates no M x M tensor."""
+        if min(bags.lengths) < self.MIN_WINDOW_ROWS:
+            raise ValueError(f"forward_window: every bag needs at least {self.MIN_WINDOW_ROWS} rows (got {min(bags.lengths)}); "
+                             "shorter bags go through forward()")
+        labels = weight = None
+        if ce_targets is not None:
+            labels, weight = ce_targets
+            if tuple(weight.shape) != (bags.n_slides,) or weight.dtype != torch.float32:
+                raise ValueError("forward_window: slide_weight must be one fp32 value per bag")
+        h_bag = self._patch_fc(bags).data.float()
+        pooled, paths, maps = [], [], ([] if need_maps else None)
+        for h_b in h_bag.split(bags.lengths):
+            h_coattn, a_coattn = ops.bag_self_attention(h_b, self.self_attention, self.training, need_weights=need_maps)
+            path_trans = self.path_transformer(h_coattn)
+            a_path, h_path = ops.gated_pool(path_trans.unsqueeze(0), self.path_attention_head, self.path_rho, self.training)
+            pooled.append(h_path)
+            paths.append(a_path[0])
+            if need_maps:
+                maps.append(a_coattn)
+        h = pooled[0] if len(pooled) == 1 else torch.cat(pooled, 0)
+        att = {"attn": maps, "path": paths}
+        if labels is not None:
+            att["loss"], y = ops.ge_head_loss(h, self.classifier, labels)
+            return y, att
+        logits = ops.linear(h, self.classifier.weight, self.classifier.bias)
+        return torch.softmax(logits, dim=1), att
+
     def get_trainable_parameters(self):
         return sum(p.numel() for p in self.parameters() if p.requires_grad)

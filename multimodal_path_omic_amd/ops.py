@@ -276,7 +276,8 @@ def coattn_mcat(query, batch: BagBatch, in_w, in_b, out_w, out_b, need_weights: 
 # counters the tests read to make sure a fused path really ran.  qpass_*: how a hand-on op's backward (the query handed on
 # by patch_coattn_mcat / coattn_nacagat / contextual_gate) met the gradient of that query -- accumulated in place on a
 # buffer the caller's wiring owns, or on a copy (see _query_grad_buffer)
-stats = {"colsum_handoffs": 0, "qpass_in_place": 0, "qpass_copied": 0, "head_loss_ces": 0, "head_loss_sct": 0}
+stats = {"colsum_handoffs": 0, "qpass_in_place": 0, "qpass_copied": 0, "head_loss_ces": 0, "head_loss_sct": 0,
+         "head_loss_ce": 0}
 
 
 def _query_grad_buffer(d_qpass, owned: bool, query):
@@ -1252,6 +1253,54 @@ def fusion_head_loss_cat(hcat, fusion_layer, classifier, label, censorship, slid
     seq = fusion_layer.fusion_layer
     return FusionHeadLossFn.apply(hcat, label, censorship, slide_weight, alpha, eps, loss, seq[0].weight, seq[0].bias,
                                   seq[2].weight, seq[2].bias, classifier.weight, classifier.bias)
+
+
+class GeHeadLossFn(torch.autograd.Function):
+    """Training-step head of the gene-expression model: classifier + softmax (models/ge_nacagat/ge_nacagat.py:63-67) and the
+    reference's `ce` loss on the already soft-maxed Y (models/ge_nacagat/main.py:33), one launch each way
+    (mpo_ge_head_loss_*).  Returns (loss (B,), Y (B, C)); only `loss` carries gradient.  Drive it as
+    loss.backward(slide_weight) with one weight per bag (1 / grad_acc_step in the reference's loop, main.py:51)."""
+
+    @staticmethod
+    def forward(ctx, h, label, weight, bias):
+        lib = L.lib()
+        ctx.set_materialize_grads(False)
+        h = h.contiguous()
+        b, d = h.shape
+        c = weight.shape[0]
+        label = label.view(-1).to(torch.int64).contiguous()
+        if label.numel() != b:
+            raise ValueError(f"ge_head_loss: {label.numel()} labels for {b} bags")
+        y = torch.empty(b, c, device=h.device, dtype=torch.float32)
+        loss = torch.empty(b, device=h.device, dtype=torch.float32)
+        L.check(lib.mpo_ge_head_loss_forward(L.ptr(h), b, d, c, L.ptr_array((weight, bias)), L.ptr(label), L.ptr(y), L.ptr(loss),
+                                             L.stream_of(h)), "mpo_ge_head_loss_forward")
+        stats["head_loss_ce"] += 1
+        ctx.save_for_backward(h, label, weight, bias)
+        ctx.param_refs = (weight, bias)
+        ctx.mark_non_differentiable(y)
+        return loss, y
+
+    @staticmethod
+    def backward(ctx, d_loss, _d_y):
+        lib = L.lib()
+        h, label, weight, bias = ctx.saved_tensors
+        if d_loss is None:
+            return None, None, None, None
+        b, d = h.shape
+        d_loss = d_loss.to(torch.float32).contiguous()          # (loss.sum().backward() hands a stride-0 expansion)
+        d_h = torch.empty_like(h)
+        grads = [grad_out(p) for p in ctx.param_refs]
+        L.check(lib.mpo_ge_head_loss_backward(L.ptr(h), b, d, weight.shape[0], L.ptr_array((weight, bias)), L.ptr(label),
+                                              L.ptr(d_loss), L.ptr(d_h), L.ptr_array(grads), L.stream_of(h)),
+                "mpo_ge_head_loss_backward")
+        return (d_h, None, *grads)
+
+
+def ge_head_loss(h, classifier, label):
+    """h (B, d) pooled rows, classifier nn.Linear(d, C), label (B,) -> (per-bag `ce` loss (B,), Y (B, C)).  d in 128 / 256 /
+    512 and C in 2..8, anything else raises; a label outside [0, C) gives that bag a NaN loss and no gradient."""
+    return GeHeadLossFn.apply(h, label, classifier.weight, classifier.bias)
 
 
 def bump_step_counters(rng_epoch=None, adam_step=None):
