@@ -105,10 +105,161 @@ class FlatGradBucket:
         return _Then()
 
 
-class FlatAdam:
+# torch.optim class and the names of the two per-parameter moments (state1, state2 of the flat pass) per algorithm
+_TORCH_OPTIM = {"adam": ("Adam", ("exp_avg", "exp_avg_sq")), "adamax": ("Adamax", ("exp_avg", "exp_inf")),
+                "adadelta": ("Adadelta", ("square_avg", "acc_delta")), "sgd": ("SGD", ())}
+# param-group flags of torch.optim whose non-default setting selects arithmetic the flat pass does not have
+_UNBUILT_FLAGS = ("amsgrad", "maximize", "decoupled_weight_decay", "momentum", "dampening", "nesterov")
+
+
+def package_only_parameter_names(model) -> "List[str]":
+    """Names of the parameters of `model` that the reference model does not register (modules declare them in
+    `package_only_parameters`; today fusion.GatedConcatFusion's gates): they appear in neither dict a reference program
+    reads from a checkpoint."""
+    out = []
+    for prefix, module in model.named_modules():
+        for sub in getattr(module, "package_only_parameters", ()):
+            head = f"{prefix}.{sub}." if prefix else f"{sub}."
+            out += [n for n, _ in model.named_parameters() if n.startswith(head)]
+    return out
+
+
+def _host_clone(t: torch.Tensor) -> torch.Tensor:
+    """A compact copy on the CPU (never a view: torch.save pickles a view's whole storage)."""
+    t = t.detach()
+    return t.cpu() if t.device.type != "cpu" else t.clone()
+
+
+class _TorchStateDict:
+    """state_dict() / load_state_dict() of the flat optimisers in the format of the torch.optim class they restate, so that
+    either side continues a run of the other.  Expects bucket, algorithm, lr, betas, eps, wd, t_dev and _moments()."""
+
+    def _param_group(self, n_params: int) -> dict:
+        """The one param group as the installed torch.optim class writes it: its own key set and flag defaults."""
+        cls_name, _ = _TORCH_OPTIM[self.algorithm]
+        kw = dict(lr=self.lr, weight_decay=self.wd)
+        if self.algorithm in ("adam", "adamax"):
+            kw.update(betas=tuple(self.betas), eps=self.eps)
+        elif self.algorithm == "adadelta":
+            kw.update(rho=self.betas[0], eps=self.eps)
+        group = getattr(torch.optim, cls_name)([torch.zeros(1)], **kw).state_dict()["param_groups"][0]
+        group["params"] = list(range(n_params))
+        return group
+
+    def _split_by_name(self, model):
+        """(bucket indices of the parameters the reference has, in its order; {name: bucket index} of the others)."""
+        if model is None:
+            return list(range(len(self.bucket.params))), {}
+        by_id = {id(p): n for n, p in model.named_parameters()}
+        names = [by_id.get(id(p)) for p in self.bucket.params]
+        if None in names:
+            raise ValueError("state_dict: the bucket holds a parameter that is not one of the model's")
+        only = set(package_only_parameter_names(model))
+        return ([i for i, n in enumerate(names) if n not in only], {n: i for i, n in enumerate(names) if n in only})
+
+    def state_dict(self, model=None):
+        """torch.optim.{Adam, Adamax, Adadelta, SGD}.state_dict() of the same run: one param group, `params` 0 .. n-1 in
+        bucket order, per parameter `step` (0-dim fp32) and the two moments in the parameter's shape (SGD: no state).  Every
+        tensor is a clone on the CPU.  One host sync (the step count).
+
+        With `model`: returns (dict, package_only).  The dict covers the parameters the reference model has, in its
+        filter(requires_grad, model.parameters()) order; `package_only` maps the names of the others
+        (package_only_parameter_names) to their state entries."""
+        shared, only = self._split_by_name(model)
+        _, keys = _TORCH_OPTIM[self.algorithm]
+        host = [m.detach().cpu() for m in self._moments()]
+        t = float(int(self.t_dev))
+
+        def entry(i):
+            p, off = self.bucket.params[i], self.bucket.offsets[i]
+            e = {"step": torch.tensor(t, dtype=torch.float32)}
+            for k, m in zip(keys, host):
+                e[k] = m[off:off + p.numel()].view(p.shape).clone()
+            return e
+
+        state = {j: entry(i) for j, i in enumerate(shared)} if keys else {}
+        sd = {"state": state, "param_groups": [self._param_group(len(shared))]}
+        if model is None:
+            return sd
+        return sd, ({n: entry(i) for n, i in only.items()} if keys else {})
+
+    def load_state_dict(self, state_dict, model=None, package_only=None):
+        """Continue from a state_dict() of this class or of the torch.optim class it restates (`step` a tensor or an int,
+        moments of any float dtype).  Everything is checked first and then copied IN PLACE into the flat buffers, t_dev and
+        lr_dev: every data_ptr() is kept (a captured step stays valid) and the padding stays zero.  Hyper-parameters come
+        from the dict, as with torch.  Parameters without an entry (torch keeps none for a parameter that never had a
+        gradient) get zero moments.  `model` / `package_only`: as returned by state_dict(model); package-only parameters
+        without an entry (a file written by the reference) get zero moments too.  Raises ValueError on moments of another
+        algorithm, a wrong shape or parameter count, or per-parameter steps that differ (there is one step count)."""
+        shared, only = self._split_by_name(model)
+        _, keys = _TORCH_OPTIM[self.algorithm]
+        groups = state_dict["param_groups"]
+        if len(groups) != 1:
+            raise ValueError(f"load_state_dict: {len(groups)} param groups; the flat optimiser has one")
+        group = groups[0]
+        if len(group["params"]) != len(shared):
+            raise ValueError(f"load_state_dict: parameter count differs: the state_dict lists {len(group['params'])} "
+                             f"parameters, the optimiser holds {len(shared)}")
+        for flag in _UNBUILT_FLAGS:
+            if group.get(flag):
+                raise ValueError(f"load_state_dict: {flag}={group[flag]!r} is not built in the flat {self.algorithm} pass")
+        entries = {}                                        # bucket index -> (label, state entry)
+        for j, pid in enumerate(group["params"]):
+            e = state_dict["state"].get(pid)
+            if e:
+                entries[shared[j]] = (f"parameter {pid}", e)
+        unknown = [k for k in state_dict["state"] if k not in group["params"]]
+        if unknown:
+            raise ValueError(f"load_state_dict: state for parameters {unknown[:5]} that the param group does not list")
+        for name, e in (package_only or {}).items():
+            if name not in only:
+                raise ValueError(f"load_state_dict: package-only state for '{name}', which this model does not have")
+            if e:
+                entries[only[name]] = (f"parameter '{name}'", e)
+        steps = set()
+        for i, (label, e) in entries.items():
+            got = sorted(k for k, v in e.items() if k != "step" and v is not None)
+            if got != sorted(keys):
+                raise ValueError(f"load_state_dict: {label} holds {got}: not the moments of '{self.algorithm}' "
+                                 f"({', '.join(keys) if keys else 'none'})")
+            for k in keys:
+                if tuple(e[k].shape) != tuple(self.bucket.params[i].shape):
+                    raise ValueError(f"load_state_dict: shape of {k} of {label} differs: the state_dict has "
+                                     f"{tuple(e[k].shape)}, the parameter {tuple(self.bucket.params[i].shape)}")
+            if "step" in e:
+                steps.add(int(float(e["step"])))
+        if len(steps) > 1:
+            raise ValueError(f"load_state_dict: per-parameter steps differ ({sorted(steps)[:4]} ...): the flat optimiser "
+                             f"keeps one step count")
+        with torch.no_grad():
+            for j, (k, flat) in enumerate(zip(keys, self._moments())):
+                for i, (p, off) in enumerate(zip(self.bucket.params, self.bucket.offsets)):
+                    sl = flat[off:off + p.numel()]
+                    if i in entries:
+                        sl.copy_(entries[i][1][k].reshape(-1))
+                    else:
+                        sl.zero_()
+            if keys:
+                self.t_dev.fill_(steps.pop() if steps else 0)
+        self._set_hyper(group)
+
+    def _set_hyper(self, group: dict):
+        self.lr = float(group["lr"])
+        if getattr(self, "lr_dev", None) is not None:
+            self.lr_dev.fill_(self.lr)
+        self.wd = float(group.get("weight_decay", 0.0))
+        if self.algorithm in ("adam", "adamax"):
+            self.betas, self.eps = tuple(float(b) for b in group["betas"]), float(group["eps"])
+        elif self.algorithm == "adadelta":
+            self.betas, self.eps = (float(group["rho"]), 0.0), float(group["eps"])
+
+
+class FlatAdam(_TorchStateDict):
     """torch.optim.Adam(lr, betas, eps, weight_decay) (the reference's default optimiser,
     models/mcat/main.py:284-300) as ONE HIP kernel over flat buffers: parameters are re-pointed at slices of
     a flat fp32 buffer laid out like the gradient bucket; exp_avg / exp_avg_sq are flat too."""
+
+    algorithm = "adam"
 
     def __init__(self, bucket: FlatGradBucket, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         self.bucket, self.lr, self.betas, self.eps, self.wd = bucket, lr, betas, eps, weight_decay
@@ -137,6 +288,9 @@ class FlatAdam:
         """Every tensor a step writes (what a warm-up that must not train puts back)."""
         return [self.flat_p, self.exp_avg, self.exp_avg_sq, self.t_dev]
 
+    def _moments(self):
+        return [self.exp_avg, self.exp_avg_sq]
+
 
 def _repoint_params(bucket: FlatGradBucket) -> torch.Tensor:
     """Flat fp32 parameter buffer laid out like the gradient bucket; every parameter is re-pointed at its slice (the padding
@@ -150,7 +304,7 @@ def _repoint_params(bucket: FlatGradBucket) -> torch.Tensor:
     return flat_p
 
 
-class FlatOptimizer:
+class FlatOptimizer(_TorchStateDict):
     """The reference's training.optimizer choices (models/mcat/main.py:284-300) as ONE HIP pass over flat buffers
     (mpo_optim_step_flat): 'adam' | 'adamax' | 'adadelta' | 'sgd', torch.optim 2.x single-tensor arithmetic in fp32.
     Parameters are re-pointed at slices of a flat buffer as in FlatAdam.
@@ -194,6 +348,9 @@ class FlatOptimizer:
     def state_tensors(self):
         """Every tensor a step writes (what a warm-up that must not train puts back)."""
         return [t for t in (self.flat_p, self.state1, self.state2, self.t_dev) if t is not None]
+
+    def _moments(self):
+        return [] if self.state1 is None else [self.state1, self.state2]
 
     def l1_value(self) -> torch.Tensor:
         """sum |p| over the flat parameters as a device scalar (deterministic; ops.flat_abs_sum)."""

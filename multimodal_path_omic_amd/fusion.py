@@ -38,6 +38,10 @@ class GatedConcatFusion(nn.Module):
     a reference checkpoint -- which has no gate entries -- still loads strictly: missing `gates.*` keys keep their
     freshly initialised values, which is what the reference model had."""
 
+    # sub-modules whose parameters the reference model does not register: a checkpoint keeps them (and their optimiser
+    # state) out of the two dicts the reference reads (dp.package_only_parameter_names, checkpoint.py)
+    package_only_parameters = ("gates",)
+
     def __init__(self, dims: list, hidden_size: int = 256, output_size: int = 256):
         super().__init__()
         self.gates = nn.ModuleList([nn.Sequential(nn.Linear(dim, 1), nn.Sigmoid()) for dim in dims])

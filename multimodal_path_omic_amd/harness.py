@@ -235,14 +235,20 @@ class GraphedWindowStep:
 
     def __init__(self, model, bucket, window, grad_acc_step: int, opt=None, warmup: int = 2, pool=None,
                  split_patch_grad: bool = False, prime: bool = True, loss: str = "ces", alpha: float = 0.75,
-                 lambda_reg: float = 0.01, l1: "float | None" = None):
+                 lambda_reg: float = 0.01, l1: "float | None" = None, rng_base: "int | None" = None):
         """split_patch_grad (data-parallel steps, opt=None): the patch layer's weight gradient -- a 0.3 ms GEMM nobody
         downstream waits for -- is captured into a SECOND graph, `replay_tail()`.  The caller replays the main graph,
         starts the all-reduce of every other gradient (bucket.all_reduce_mean_async(lo=head)), replays the tail while
         that collective runs, then reduces the head slice: the exchange step hides behind compute.
         loss / alpha / lambda_reg / l1: train_window's (TrainOptions.train_kwargs()); l1 defaults to the optimiser's
-        l1_lambda, whose gradient fold the captured opt.step() applies for this window's slides."""
+        l1_lambda, whose gradient fold the captured opt.step() applies for this window's slides.
+        rng_base: the value of the dropout generator's host counter the capture starts from (default: wherever the
+        counter stands after the warm-up).  The capture bakes stream offsets taken from that counter into the graph, so
+        a step re-captured in another process at the `rng_base` the original reports (self.rng_base, stored by
+        checkpoint.save) draws the masks the original would have drawn, whatever ran before; on return the counter
+        stands at the larger of its value on entry and the end of the captured streams."""
         from . import ops
+        calls_on_entry = ops._rng_calls
         self.model, self.bucket, self.opt = model, bucket, opt
         self.l1 = float(getattr(opt, "l1_lambda", 0.0) if l1 is None else l1)
         self.train_kwargs = dict(loss=loss, alpha=alpha, lambda_reg=lambda_reg, l1=self.l1)
@@ -277,6 +283,9 @@ class GraphedWindowStep:
             self.epoch.copy_(keep_epoch)
         torch.cuda.current_stream(dev).wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
+        if rng_base is not None:
+            ops._rng_calls = int(rng_base)
+        self.rng_base = ops._rng_calls
         bag_data = window[0].data
         self._fp32_window_version = bag_data._version if bag_data.dtype == torch.float32 else None
         # thread_local: other threads (RCCL's watchdog under torch.distributed) may issue HIP calls meanwhile
@@ -288,6 +297,8 @@ class GraphedWindowStep:
             self.tail_graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.tail_graph, pool=self.graph.pool(), capture_error_mode="thread_local"):
                 ops.flush_patch_weight_grads()
+        if rng_base is not None:
+            ops._rng_calls = max(calls_on_entry, ops._rng_calls)
         # The FIRST replay of a captured graph pays for its upload (2-4 ms against a 1.2 ms step, measured): pay it here,
         # with the state it touches put back, so that a caller's first step is a step like any other.
         if prime:

@@ -1323,6 +1323,31 @@ def next_dropout_stream(n_elements: int):
     return seed, offset
 
 
+def rng_state() -> dict:
+    """The dropout generator's three values: {'seed': torch.initial_seed(), 'calls': the host counter the stream offsets
+    are carved from, 'epoch': the device epoch scalar's value, None while none is installed}.  One host sync when an
+    epoch tensor is installed."""
+    epoch = None if _rng_epoch_tensor is None else int(_rng_epoch_tensor)
+    return {"seed": int(torch.initial_seed()), "calls": int(_rng_calls), "epoch": epoch}
+
+
+def set_rng_state(state: dict, device=None):
+    """Put rng_state() back.  The epoch tensor is written IN PLACE (a captured step holds its address); with none
+    installed and a stored epoch, one is created on `device` and installed.  A stored epoch of None zeroes an installed
+    tensor (no tensor and epoch 0 draw the same masks).  The seed is re-seeded only where it differs."""
+    global _rng_calls
+    if int(state["seed"]) != torch.initial_seed():
+        torch.manual_seed(int(state["seed"]))
+    _rng_calls = int(state["calls"])
+    epoch = state.get("epoch")
+    if _rng_epoch_tensor is not None:
+        _rng_epoch_tensor.fill_(0 if epoch is None else int(epoch))
+    elif epoch is not None:
+        if device is None:
+            raise ValueError("set_rng_state: no epoch tensor is installed; name the device to create one on")
+        set_rng_epoch(torch.full((1,), int(epoch), dtype=torch.int64, device=device))
+
+
 # False: the patch-side gradient of K2 as library GEMM + mpo_nacagat_patch_grad (the r02 path; kept for the small model and as
 # the cross-check of csrc/k2_patchgrad.hip in tools/gpu_diag_nacagat.py)
 k2_fused_patch_grad = True
