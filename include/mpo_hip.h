@@ -30,6 +30,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
+/* What mpo_abi_version() of a library built from this header returns.  The Python host compares the two when it loads the
+ * library, so a stale build is refused instead of being called through newer signatures. */
+#define MPO_ABI_VERSION 14
+
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -1,137 +1,106 @@
 """ctypes binding of libmpo_hip.so (C ABI: include/mpo_hip.h).
 
-There is deliberately no fallback: if the shared library is missing, or a call returns
-non-zero, a RuntimeError is raised.  Tensors cross the boundary as raw device pointers
+Signatures, enum values and the ABI version are read from that header when the module is imported; nothing
+here states them a second time.  There is deliberately no fallback: if the shared library is missing or stale,
+or a call returns non-zero, a RuntimeError is raised.  Tensors cross the boundary as raw device pointers
 (`tensor.data_ptr()`), sizes, and the current HIP stream of the tensor's device.
 """
 from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_size_t, c_uint64, c_void_p  # noqa: F401
+import re
+from ctypes import c_char_p, c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmpo_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mpo_hip.h")
 
-MPO_F32, MPO_BF16 = 0, 1
-OPTIM = {"adam": 0, "adamax": 1, "adadelta": 2, "sgd": 3}      # MPO_OPTIM_* of include/mpo_hip.h
+# The closed map from the header's scalar parameter types; a new scalar type in the header needs a new line here.
+_SCALARS = {"int": c_int, "int32_t": c_int, "int64_t": c_int64, "uint64_t": c_uint64, "size_t": c_size_t, "float": c_float,
+            "mpo_stream_t": c_void_p}
+_DECL = re.compile(r"^[ \t]*([\w \t*]+?)[ \t]*\b(mpo_\w+)[ \t]*\(([^()]*)\)\s*;", re.M)
+
+
+def _ctype(entry: str, decl: str):
+    """ctypes type of one parameter (or scalar return type) as the header spells it, name optional."""
+    if "*" in decl or decl.rstrip().endswith("]"):
+        return c_void_p
+    words = [w for w in decl.split() if w != "const"]
+    if not 1 <= len(words) <= 2 or words[0] not in _SCALARS:
+        raise RuntimeError(f"include/mpo_hip.h: {entry}: no ctypes type for '{' '.join(decl.split())}'")
+    return _SCALARS[words[0]]
+
+
+def parse_header(text: str):
+    """C header text -> ({entry: (restype, [argtypes])}, {enum constant: value}, MPO_ABI_VERSION or None).  Strict: every
+    `mpo_*(` must be one whole declaration `ret name(args);` whose types are all in the map above."""
+    version = re.search(r"^[ \t]*#[ \t]*define[ \t]+MPO_ABI_VERSION[ \t]+(\d+)[ \t]*$", text, re.M)
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*|^[ \t]*#.*$", " ", text, flags=re.M)
+    signatures, parsed = {}, set()
+    for m in _DECL.finditer(text):
+        ret, name, args = m.groups()
+        parsed.add(m.start(2))
+        if ret.replace("*", " * ").split() == ["const", "char", "*"]:
+            res = c_char_p
+        elif "*" in ret:
+            raise RuntimeError(f"include/mpo_hip.h: {name}: no ctypes type for the return type '{ret.strip()}'")
+        else:
+            res = _ctype(name, ret)
+        signatures[name] = (res, [] if args.strip() in ("", "void") else [_ctype(name, a) for a in args.split(",")])
+    for m in re.finditer(r"\b(mpo_\w+)\s*\(", text):
+        if m.start(1) not in parsed:
+            raise RuntimeError(f"include/mpo_hip.h: {m.group(1)}: not a whole declaration: "
+                               f"'{' '.join(text[m.start():m.start() + 120].split())}'")
+    constants = {}
+    for body in re.findall(r"\benum\s*\{([^}]*)\}", text):
+        for item in body.split(","):
+            m = re.fullmatch(r"\s*(MPO_\w+)\s*=\s*(\d+)\s*", item)
+            if not m:
+                raise RuntimeError(f"include/mpo_hip.h: enum item '{item.strip()}' is not NAME = integer")
+            constants[m.group(1)] = int(m.group(2))
+    return signatures, constants, int(version.group(1)) if version else None
+
+
+def _read_header():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError(f"{HEADER_PATH} is missing: the package binds libmpo_hip.so from its public header and ships "
+                           "with it (repository layout: include/ beside the package)")
+    with open(HEADER_PATH) as f:
+        signatures, constants, version = parse_header(f.read())
+    if version is None or not signatures:
+        raise RuntimeError(f"{HEADER_PATH}: no MPO_ABI_VERSION / no entry declarations found")
+    return signatures, constants, version
+
+
+# Everything below is what include/mpo_hip.h says: the signatures lib() binds, its enums and the ABI version it describes.
+_signatures, _constants, ABI_VERSION = _read_header()
+MPO_F32, MPO_BF16 = _constants["MPO_F32"], _constants["MPO_BF16"]
+ACT = {k[len("MPO_ACT_"):-1].lower(): v for k, v in _constants.items() if k.startswith("MPO_ACT_")}      # MPO_ACT_RELU_ -> relu
+OPTIM = {k[len("MPO_OPTIM_"):].lower(): v for k, v in _constants.items() if k.startswith("MPO_OPTIM_")}
 
 
 class BagPlanC(ctypes.Structure):
     """mpo_bag_plan of include/mpo_hip.h (host struct; wg_start is a device pointer)."""
     _fields_ = [("wg_start", c_void_p), ("n_wg", ctypes.c_int32), ("rows_per_wg", ctypes.c_int32)]
-ACT = {"none": 0, "relu": 1, "elu": 2, "tanh": 3, "sigmoid": 4}
 
+
+_REBUILD = "run `python -c 'import __graft_entry__ as g; g.build()'`"
 _lib = None
-
-_P = c_void_p
-_SIGNATURES = {
-    "mpo_abi_version": (c_int, []),
-    "mpo_last_error": (c_char_p, []),
-    "mpo_linear_forward": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_float, c_int, _P]),
-    "mpo_linear_backward_input": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, c_int, _P]),
-    "mpo_linear_backward_weight": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_float, _P]),
-    "mpo_coattn_splits": (c_int, [c_int, c_int]),
-    "mpo_coattn_target_workgroups": (c_int, []),
-    "mpo_map_block_dot": (c_int, [_P, _P, _P, c_int, c_int, _P, _P]),
-    "mpo_map_block_scale": (c_int, [_P, _P, _P, c_int, c_int, _P, _P]),
-    "mpo_key_projection": (c_int, [_P, ctypes.c_int64, c_int, _P, _P, _P, _P]),
-    "mpo_nacagat_fwd_bagpass": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, c_int, c_int, _P, _P]),
-    "mpo_coattn_fwd_bagpass": (c_int, [_P, c_int, _P, c_int, c_int, _P, _P, _P, _P, c_int, c_int, _P, _P]),
-    "mpo_coattn_bwd_bagpass": (c_int, [_P, c_int, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P]),
-    "mpo_coattn_saved_floats": (c_size_t, [c_int, c_int, c_int]),
-    "mpo_coattn_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "mpo_coattn_mcat_forward": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, _P, _P, _P, _P,
-                                        _P, _P, _P, _P, _P, c_size_t, _P]),
-    "mpo_patch_coattn_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "mpo_patch_coattn_mcat_forward": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, c_float, c_uint64, c_uint64, _P,
-                                              _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "mpo_patch_coattn_fwd_bagpass": (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_float, c_uint64, c_uint64,
-                                             _P, _P]),
-    "mpo_pack_patch_weight": (c_int, [_P, _P, c_int, c_int, _P]),
-    "mpo_patch_fc_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "mpo_patch_fc_f32_workspace_bytes": (c_size_t, [c_int]),
-    "mpo_patch_fc_f32_forward": (c_int, [_P, ctypes.c_int64, c_int, _P, _P, c_int, c_float, c_uint64, c_uint64, _P, c_float, _P, _P, c_size_t, _P]),
-    "mpo_patch_fc_f32_backward": (c_int, [_P, _P, _P, ctypes.c_int64, c_int, c_int, c_float, _P, _P, _P, c_size_t, _P]),
-    "mpo_patch_fc_forward": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, c_int, c_float, c_uint64, c_uint64, _P, _P, _P,
-                                     _P, c_size_t, _P]),
-    "mpo_coattn_mcat_backward": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, _P, _P, _P, _P,
-                                         _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, c_float, _P, _P, c_size_t, _P]),
-    "mpo_colsum_bf16": (c_int, [_P, _P, ctypes.c_int64, c_int, _P]),
-    "mpo_patch_weight_grad_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "mpo_patch_weight_grad": (c_int, [_P, _P, ctypes.c_int64, c_int, c_int, _P, c_int, _P, c_size_t, _P]),
-    "mpo_adam_step_flat": (c_int, [_P, _P, _P, _P, ctypes.c_int64, c_float, c_float, c_float, c_float, c_float, c_int, _P, _P]),
-    "mpo_patch_epilogue_forward": (c_int, [_P, _P, ctypes.c_int64, c_int, c_float, c_uint64, c_uint64, _P, _P]),
-    "mpo_patch_epilogue_backward_workspace_bytes": (c_size_t, [ctypes.c_int64, c_int]),
-    "mpo_patch_epilogue_backward": (c_int, [_P, _P, _P, ctypes.c_int64, c_int, c_float, _P, _P, c_size_t, _P]),
-    "mpo_nacagat_saved_floats": (c_size_t, [c_int, c_int, c_int]),
-    "mpo_nacagat_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "mpo_coattn_nacagat_forward": (c_int, [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, _P, _P, _P, _P,
-                                           c_float, c_uint64, c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "mpo_coattn_nacagat_backward": (c_int, [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, _P, _P, _P,
-                                            c_float, c_uint64, c_uint64, _P, _P, _P, _P, _P, _P, _P,
-                                            _P, c_int, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "mpo_nacagat_patch_grad": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_float, _P, _P, _P, c_size_t, _P]),
-    "mpo_nacagat_patch_grad_fused": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_float, _P, _P, _P,
-                                             c_size_t, _P]),
-    "mpo_survival_head_forward": (c_int, [_P, c_int, c_int, _P, _P, _P, _P]),
-    "mpo_survival_head_backward": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P]),
-    "mpo_ces_loss_forward": (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, c_float, _P, _P, _P]),
-    "mpo_ces_loss_backward": (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, c_float, _P, c_int, _P, _P, _P]),
-    "mpo_encoder_saved_floats": (c_size_t, [c_int] * 6),
-    "mpo_encoder_workspace_bytes": (c_size_t, [c_int] * 4),
-    "mpo_encoder_rng_span": (c_uint64, [c_int] * 5),
-    "mpo_encoder_forward": (c_int, [_P] + [c_int] * 7 + [_P, c_float, c_uint64, c_uint64, _P, _P, _P, _P]),
-    "mpo_encoder_backward": (c_int, [_P] + [c_int] * 7 + [_P, c_float, c_uint64, c_uint64, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "mpo_bag_self_attention_saved_floats": (c_size_t, [c_int] * 4),
-    "mpo_bag_self_attention_workspace_bytes": (c_size_t, [c_int] * 4),
-    "mpo_set_bag_self_attention_bf16x3": (c_int, [c_int]),
-    "mpo_bag_self_attention_forward": (c_int, [_P, c_int, c_int, c_int, c_int, c_float, c_uint64, c_uint64, _P, _P, _P, _P, _P]),
-    "mpo_bag_self_attention_backward": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_uint64, c_uint64, _P, _P, _P, c_size_t, _P]),
-    "mpo_gated_pool_saved_floats": (c_size_t, [c_int] * 3),
-    "mpo_gated_pool_workspace_bytes": (c_size_t, [c_int] * 3),
-    "mpo_gated_pool_rng_span": (c_uint64, [c_int] * 3),
-    "mpo_gated_pool_forward": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_float, c_float, c_uint64, c_uint64, _P, _P, _P, c_int, _P, _P]),
-    "mpo_gated_pool_backward": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_float, c_float, _P, _P, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
-    "mpo_fusion_head_saved_floats": (c_size_t, [c_int] * 4),
-    "mpo_fusion_head_workspace_bytes": (c_size_t, [c_int] * 4),
-    "mpo_fusion_head_forward": (c_int, [_P] + [c_int] * 5 + [_P, _P, _P, _P, _P, _P]),
-    "mpo_fusion_head_backward": (c_int, [_P] + [c_int] * 5 + [_P] * 10 + [_P, c_size_t, _P]),
-    "mpo_fusion_head_loss_saved_floats": (c_size_t, [c_int] * 4),
-    "mpo_fusion_head_loss_forward": (c_int, [_P] + [c_int] * 5 + [_P, _P, _P, _P, c_float, c_float] + [_P] * 6 + [_P]),
-    "mpo_fusion_head_loss_backward": (c_int, [_P] + [c_int] * 5 + [_P, _P, _P, _P] + [_P, c_size_t, _P]),
-    "mpo_step_counters_bump": (c_int, [_P, _P, _P]),
-    "mpo_sct_loss_forward": (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, _P]),
-    "mpo_sct_loss_backward": (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, c_int, _P, _P]),
-    "mpo_fusion_head_sct_loss_forward": (c_int, [_P] + [c_int] * 5 + [_P, _P, _P, _P, c_float] + [_P] * 6 + [_P]),
-    "mpo_ge_head_loss_forward": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
-    "mpo_ge_head_loss_backward": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
-    "mpo_optim_step_flat": (c_int, [c_int, _P, _P, _P, _P, ctypes.c_int64, c_float, _P, c_float, c_float, c_float, c_float,
-                                    c_float, c_int, _P, _P]),
-    "mpo_abs_sum_flat_workspace_bytes": (c_size_t, [ctypes.c_int64]),
-    "mpo_abs_sum_flat": (c_int, [_P, ctypes.c_int64, _P, _P, c_size_t, _P]),
-    "mpo_set_gemm_fast_path": (c_int, [c_int]),
-    "mpo_set_coattn_bwd_two_wave": (c_int, [c_int]),
-    "mpo_set_nacagat_one_pass_key_grad": (c_int, [c_int]),
-    "mpo_set_coattn_bwd_f32_vector": (c_int, [c_int]),
-    "mpo_omic_snn_saved_floats": (c_size_t, [c_int] * 3),
-    "mpo_omic_snn_workspace_bytes": (c_size_t, [c_int] * 3),
-    "mpo_omic_snn_rng_span": (c_uint64, [c_int] * 3),
-    "mpo_omic_snn_forward": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_float, c_uint64, c_uint64, _P, _P, _P, _P]),
-    "mpo_omic_snn_backward": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_float, c_uint64, c_uint64, _P, _P, _P, _P, _P,
-                                      _P, c_size_t, _P]),
-    "mpo_cag_saved_floats": (c_size_t, [c_int] * 2),
-    "mpo_cag_workspace_bytes": (c_size_t, [c_int] * 2),
-    "mpo_cag_forward": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
-    "mpo_cag_backward": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, _P, c_size_t, _P]),
-}
 
 
 def exported_symbols():
-    """Names every build of the library must export (checked by the CPU test-suite)."""
-    return list(_SIGNATURES)
+    """Names every build of the library must export (checked by the CPU test-suite): the header's entries."""
+    return list(_signatures)
+
+
+def check_abi_version(found: int, expected: int):
+    if found != expected:
+        raise RuntimeError(f"{LIB_PATH} reports ABI version {found}, include/mpo_hip.h describes {expected}: the library is "
+                           f"stale ({_REBUILD}). There is no CPU fallback.")
 
 
 def lib():
@@ -139,15 +108,20 @@ def lib():
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(
-                f"{LIB_PATH} is missing: the HIP extension has not been built "
-                "(run `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback.")
+                f"{LIB_PATH} is missing: the HIP extension has not been built ({_REBUILD}). There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in _signatures.items():
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args
+        check_abi_version(handle.mpo_abi_version(), ABI_VERSION)
         _lib = handle
     return _lib
+
+
+def call(name: str, *args):
+    """Call the status-returning entry `name`; a non-zero status raises, naming that entry."""
+    check(getattr(lib(), name)(*args), name)
 
 
 def check(rc: int, what: str):

@@ -280,9 +280,9 @@ class FlatAdam(_TorchStateDict):
         if bump:
             self.t_dev += 1
         b = self.bucket
-        L.check(L.lib().mpo_adam_step_flat(L.ptr(self.flat_p), L.ptr(b.flat), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-                                           self.flat_p.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
-                                           0, L.ptr(self.t_dev), L.stream_of(self.flat_p)), "mpo_adam_step_flat")
+        L.call("mpo_adam_step_flat", L.ptr(self.flat_p), L.ptr(b.flat), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
+               self.flat_p.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+               0, L.ptr(self.t_dev), L.stream_of(self.flat_p))
 
     def state_tensors(self):
         """Every tensor a step writes (what a warm-up that must not train puts back)."""

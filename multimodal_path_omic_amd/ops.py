@@ -168,9 +168,8 @@ class LinearFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias, act: str = "none"):
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
         y = torch.empty(x2.shape[0], weight.shape[0], device=x.device, dtype=torch.float32)
-        L.check(L.lib().mpo_linear_forward(L.ptr(x2), L.ptr(weight), L.ptr(bias), L.ptr(y), x2.shape[0],
-                                           weight.shape[1], weight.shape[0], 1.0, L.ACT[act], L.stream_of(x)),
-                "mpo_linear_forward")
+        L.call("mpo_linear_forward", L.ptr(x2), L.ptr(weight), L.ptr(bias), L.ptr(y), x2.shape[0],
+               weight.shape[1], weight.shape[0], 1.0, L.ACT[act], L.stream_of(x))
         ctx.save_for_backward(x2, weight, y)
         ctx.act = act
         ctx.has_bias = bias is not None
@@ -196,10 +195,8 @@ class LinearFn(torch.autograd.Function):
         db = torch.empty(O, device=dy.device, dtype=torch.float32) if ctx.has_bias else None
         s = L.stream_of(dy)
         if dx is not None:
-            L.check(L.lib().mpo_linear_backward_input(L.ptr(dy), L.ptr(weight), L.ptr(dx), R, I, O, 1.0, 0, s),
-                    "mpo_linear_backward_input")
-        L.check(L.lib().mpo_linear_backward_weight(L.ptr(dy), L.ptr(x2), L.ptr(dw), L.ptr(db), R, I, O, 1.0, s),
-                "mpo_linear_backward_weight")
+            L.call("mpo_linear_backward_input", L.ptr(dy), L.ptr(weight), L.ptr(dx), R, I, O, 1.0, 0, s)
+        L.call("mpo_linear_backward_weight", L.ptr(dy), L.ptr(x2), L.ptr(dw), L.ptr(db), R, I, O, 1.0, s)
         return (dx.view(ctx.xshape) if dx is not None else None), dw, db, None
 
 
@@ -227,11 +224,10 @@ class CoAttnMCATFn(torch.autograd.Function):
         amap = torch.empty(n_q * batch.total_rows, device=dev, dtype=torch.float32) if need_weights else None
         saved = torch.empty(lib.mpo_coattn_saved_floats(n_slides, n_q, E), device=dev, dtype=torch.float32)
         ws = _workspace(lib.mpo_coattn_workspace_bytes(n_slides, n_q, E, batch.max_rows), dev)
-        L.check(lib.mpo_coattn_mcat_forward(
+        L.call("mpo_coattn_mcat_forward",
             L.ptr(bag_data), L.bag_dtype_code(bag_data), L.ptr(batch.cu), n_slides, batch.total_rows, batch.max_rows,
             L.ptr(query), n_q, E, L.ptr(in_w), L.ptr(in_b), L.ptr(out_w), L.ptr(out_b),
-            L.ptr(out), L.ptr(amap), L.ptr(saved), batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(query)),
-            "mpo_coattn_mcat_forward")
+            L.ptr(out), L.ptr(amap), L.ptr(saved), batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(query))
         ctx.save_for_backward(query, bag_data, in_w, out_w, saved, amap)
         ctx.param_refs = (in_w, in_b, out_w, out_b)
         ctx.batch = batch
@@ -255,12 +251,11 @@ class CoAttnMCATFn(torch.autograd.Function):
         colsum = _bias_grad_slot(ctx.bag_bias, E, dev) if ctx.bag_relu_gate != 0.0 else None
         d_in_w, d_in_b, d_out_w, d_out_b = (grad_out(p) for p in ctx.param_refs)
         ws = _workspace(lib.mpo_coattn_workspace_bytes(batch.n_slides, n_q, E, batch.max_rows), dev)
-        L.check(lib.mpo_coattn_mcat_backward(
+        L.call("mpo_coattn_mcat_backward",
             L.ptr(bag_data), L.bag_dtype_code(bag_data), L.ptr(batch.cu), batch.n_slides, batch.total_rows,
             batch.max_rows, L.ptr(query), n_q, E, L.ptr(in_w), L.ptr(out_w), L.ptr(saved), L.ptr(amap),
             L.ptr(d_out), L.ptr(d_map), L.ptr(d_query), 0, L.ptr(d_bag), L.ptr(colsum), L.ptr(d_in_w), L.ptr(d_in_b),
-            L.ptr(d_out_w), L.ptr(d_out_b), ctx.bag_relu_gate, batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(query)),
-            "mpo_coattn_mcat_backward")
+            L.ptr(d_out_w), L.ptr(d_out_b), ctx.bag_relu_gate, batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(query))
         if colsum is not None:
             d_bag._mpo_colsum = colsum
         return d_query, d_bag, d_in_w, d_in_b, d_out_w, d_out_b, None, None, None
@@ -345,10 +340,9 @@ class PatchFcFn(torch.autograd.Function):
         h = torch.empty(x.shape[0], weight.shape[0], device=x.device, dtype=torch.bfloat16)
         seed, off = _reserve(h.numel() // 16 + 2) if drop_p > 0 else (0, 0)
         ws = _workspace(lib.mpo_patch_fc_workspace_bytes(weight.shape[0], weight.shape[1]), x.device)
-        L.check(lib.mpo_patch_fc_forward(L.ptr(x), L.ptr(batch.cu), batch.n_slides, batch.total_rows, batch.max_rows,
-                                         x.shape[1], L.ptr(weight), L.ptr(bias), weight.shape[0], float(drop_p), seed, off,
-                                         _epoch(), L.ptr(h), batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(x)),
-                "mpo_patch_fc_forward")
+        L.call("mpo_patch_fc_forward", L.ptr(x), L.ptr(batch.cu), batch.n_slides, batch.total_rows, batch.max_rows,
+               x.shape[1], L.ptr(weight), L.ptr(bias), weight.shape[0], float(drop_p), seed, off,
+               _epoch(), L.ptr(h), batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(x))
         drop_p = _realised_drop(drop_p) if drop_p > 0 else 0.0
         ctx.save_for_backward(x, h)
         ctx.param_refs = (weight, bias)
@@ -368,9 +362,8 @@ class PatchFcFn(torch.autograd.Function):
         if g is None:                       # ReLU/dropout derivative + the bias gradient (column sums) in one pass
             g = torch.empty_like(dh)
             ws = _workspace(lib.mpo_patch_epilogue_backward_workspace_bytes(g.numel(), g.shape[1]), g.device)
-            L.check(lib.mpo_patch_epilogue_backward(L.ptr(h), L.ptr(dh), L.ptr(g), g.numel(), g.shape[1], ctx.drop_p,
-                                                    L.ptr(db), L.ptr(ws), ws.numel(), L.stream_of(g)),
-                    "mpo_patch_epilogue_backward")
+            L.call("mpo_patch_epilogue_backward", L.ptr(h), L.ptr(dh), L.ptr(g), g.numel(), g.shape[1], ctx.drop_p,
+                   L.ptr(db), L.ptr(ws), ws.numel(), L.stream_of(g))
         else:
             ready = getattr(dh, "_mpo_colsum", None)
             if ready is not None and ready.shape == db.shape:
@@ -411,8 +404,8 @@ def patch_weight_grad(g: torch.Tensor, x: torch.Tensor, out: torch.Tensor) -> to
     wgs = int(wgrad_workgroups or 0)
     if wgs and k != 1024:
         wgs = 0                                        # (the setting is for the patch layer's own gradient, patch_dim 1024)
-    L.check(lib.mpo_patch_weight_grad(L.ptr(g), L.ptr(x), g.shape[0], e, k, L.ptr(out), wgs, L.ptr(ws), ws.numel(),
-                                      L.stream_of(g)), "mpo_patch_weight_grad")
+    L.call("mpo_patch_weight_grad", L.ptr(g), L.ptr(x), g.shape[0], e, k, L.ptr(out), wgs, L.ptr(ws), ws.numel(),
+           L.stream_of(g))
     return out
 
 
@@ -428,10 +421,9 @@ class PatchFcF32Fn(torch.autograd.Function):
         h = torch.empty(x.shape[0], weight.shape[0], device=x.device, dtype=torch.float32)
         seed, off = _reserve(h.numel() // 16 + 2) if drop_p > 0 else (0, 0)
         ws = _workspace(lib.mpo_patch_fc_f32_workspace_bytes(0), x.device)
-        L.check(lib.mpo_patch_fc_f32_forward(L.ptr(x), x.shape[0], x.shape[1], L.ptr(weight), L.ptr(bias), weight.shape[0],
-                                             float(drop_p), seed, off, _epoch(), feature_scale(x), L.ptr(h), L.ptr(ws), ws.numel(),
-                                             L.stream_of(x)),
-                "mpo_patch_fc_f32_forward")
+        L.call("mpo_patch_fc_f32_forward", L.ptr(x), x.shape[0], x.shape[1], L.ptr(weight), L.ptr(bias), weight.shape[0],
+               float(drop_p), seed, off, _epoch(), feature_scale(x), L.ptr(h), L.ptr(ws), ws.numel(),
+               L.stream_of(x))
         ctx.save_for_backward(x, h)
         ctx.param_refs = (weight, bias)
         ctx.gate = 1.0 / (1.0 - _realised_drop(drop_p)) if drop_p > 0 else 1.0
@@ -444,8 +436,8 @@ class PatchFcF32Fn(torch.autograd.Function):
         dh = dh.contiguous()
         dw, db = (grad_out(p) for p in ctx.param_refs)
         ws = _workspace(lib.mpo_patch_fc_f32_workspace_bytes(1), x.device)
-        L.check(lib.mpo_patch_fc_f32_backward(L.ptr(dh), L.ptr(h), L.ptr(x), x.shape[0], h.shape[1], x.shape[1], ctx.gate, L.ptr(dw),
-                                              L.ptr(db), L.ptr(ws), ws.numel(), L.stream_of(x)), "mpo_patch_fc_f32_backward")
+        L.call("mpo_patch_fc_f32_backward", L.ptr(dh), L.ptr(h), L.ptr(x), x.shape[0], h.shape[1], x.shape[1], ctx.gate, L.ptr(dw),
+               L.ptr(db), L.ptr(ws), ws.numel(), L.stream_of(x))
         return None, dw, db, None
 
 
@@ -513,11 +505,10 @@ class PatchCoAttnMCATFn(torch.autograd.Function):
         saved = torch.empty(lib.mpo_coattn_saved_floats(n_slides, n_q, E), device=dev, dtype=torch.float32)
         ws = _workspace(lib.mpo_patch_coattn_workspace_bytes(n_slides, n_q, E, x.shape[1]), dev)
         seed, off = _reserve(T * E // 16 + 2) if drop_p > 0 else (0, 0)
-        L.check(lib.mpo_patch_coattn_mcat_forward(
+        L.call("mpo_patch_coattn_mcat_forward",
             L.ptr(x), L.ptr(batch.cu), n_slides, T, batch.max_rows, x.shape[1], L.ptr(patch_w), L.ptr(patch_b), float(drop_p),
             seed, off, _epoch(), L.ptr(query), n_q, E, L.ptr(in_w), L.ptr(in_b), L.ptr(out_w), L.ptr(out_b),
-            L.ptr(h_bag), L.ptr(out), L.ptr(amap), L.ptr(saved), batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(query)),
-            "mpo_patch_coattn_mcat_forward")
+            L.ptr(h_bag), L.ptr(out), L.ptr(amap), L.ptr(saved), batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(query))
         ctx.save_for_backward(x, h_bag, query, in_w, out_w, saved, amap)
         ctx.param_refs = (patch_w, patch_b, in_w, in_b, out_w, out_b)
         ctx.batch, ctx.n_q = batch, n_q
@@ -543,11 +534,11 @@ class PatchCoAttnMCATFn(torch.autograd.Function):
         d_pw, d_pb = grad_out(patch_w), grad_out(patch_b)
         d_in_w, d_in_b, d_out_w, d_out_b = (grad_out(p) for p in (p_in_w, p_in_b, p_out_w, p_out_b))
         ws = _workspace(lib.mpo_coattn_workspace_bytes(batch.n_slides, n_q, E, batch.max_rows), dev)
-        L.check(lib.mpo_coattn_mcat_backward(
+        L.call("mpo_coattn_mcat_backward",
             L.ptr(h_bag), L.MPO_BF16, L.ptr(batch.cu), batch.n_slides, batch.total_rows, batch.max_rows, L.ptr(query), n_q, E,
             L.ptr(in_w), L.ptr(out_w), L.ptr(saved), L.ptr(amap), L.ptr(d_out), L.ptr(d_map), L.ptr(d_query), int(accumulate),
             L.ptr(g), L.ptr(d_pb), L.ptr(d_in_w), L.ptr(d_in_b), L.ptr(d_out_w), L.ptr(d_out_b), ctx.gate, batch.plan(),
-            L.ptr(ws), ws.numel(), L.stream_of(query)), "mpo_coattn_mcat_backward")
+            L.ptr(ws), ws.numel(), L.stream_of(query))
         stats["colsum_handoffs"] += 1
         _patch_weight_grad_now_or_deferred(g, x, d_pw, patch_w)
         return None, d_pw, d_pb, d_query, d_in_w, d_in_b, d_out_w, d_out_b, None, None, None, None, None
@@ -623,6 +614,9 @@ def patch_fc(x_bf16, weight, bias, drop_p: float, pre_gated_grad: bool = False, 
 import torch.nn.functional as F  # noqa: E402
 
 
+_rng_calls = 0          # counters handed out so far: the one place the dropout generator's counter space is carved
+
+
 def _reserve(span: int):
     """Reserve `span` counters of the dropout generator for one C-ABI call's streams."""
     global _rng_calls
@@ -665,8 +659,8 @@ class CagFn(torch.autograd.Function):
             residual = residual.contiguous()
             # dest = (TokenPair, slot): a non-tensor argument -- the slot's view is created here, so autograd sees a fresh output
             total = dest[0].slot(dest[1], (rows, hidden)) if dest is not None else torch.empty_like(c)
-        L.check(lib.mpo_cag_forward(L.ptr(q), L.ptr(q_hat), rows, dim, hidden, pa, L.ptr(c), L.ptr(saved), L.ptr(residual),
-                                    L.ptr(total), L.stream_of(q)), "mpo_cag_forward")
+        L.call("mpo_cag_forward", L.ptr(q), L.ptr(q_hat), rows, dim, hidden, pa, L.ptr(c), L.ptr(saved), L.ptr(residual),
+               L.ptr(total), L.stream_of(q))
         ctx.save_for_backward(q, q_hat, c, saved, *params)
         ctx.param_refs = params
         ctx.has_residual = residual is not None
@@ -687,9 +681,9 @@ class CagFn(torch.autograd.Function):
         grads = [grad_out(p) for p in ctx.param_refs]
         ws = _workspace(lib.mpo_cag_workspace_bytes(rows, hidden), q.device)
         pa, ga = L.ptr_array(params), L.ptr_array(grads)
-        L.check(lib.mpo_cag_backward(L.ptr(q), L.ptr(q_hat), rows, dim, hidden, pa, L.ptr(saved), L.ptr(c),
-                                     L.ptr(dc), L.ptr(dq), int(accumulate), L.ptr(dqh), ga, L.ptr(ws), ws.numel(),
-                                     L.stream_of(q)), "mpo_cag_backward")
+        L.call("mpo_cag_backward", L.ptr(q), L.ptr(q_hat), rows, dim, hidden, pa, L.ptr(saved), L.ptr(c),
+               L.ptr(dc), L.ptr(dq), int(accumulate), L.ptr(dqh), ga, L.ptr(ws), ws.numel(),
+               L.stream_of(q))
         return (dq, dqh, dc if ctx.has_residual else None, None, None, *grads)
 
 
@@ -717,8 +711,8 @@ class EncoderFn(torch.autograd.Function):
                             dtype=torch.float32)
         seed, off = _reserve(lib.mpo_encoder_rng_span(branches * n_slides, T, d, ff, layers)) if drop_p > 0 else (0, 0)
         pa = L.ptr_array(params)
-        L.check(lib.mpo_encoder_forward(L.ptr(x), branches, n_slides, T, d, ff, heads, layers, pa, float(drop_p), seed, off,
-                                        _epoch(), L.ptr(y), L.ptr(saved), L.stream_of(x)), "mpo_encoder_forward")
+        L.call("mpo_encoder_forward", L.ptr(x), branches, n_slides, T, d, ff, heads, layers, pa, float(drop_p), seed, off,
+               _epoch(), L.ptr(y), L.ptr(saved), L.stream_of(x))
         ctx.save_for_backward(x, saved, *params)
         ctx.param_refs = params
         ctx.geom, ctx.drop = geom, (float(drop_p), seed, off)
@@ -735,9 +729,9 @@ class EncoderFn(torch.autograd.Function):
         ws = _workspace(lib.mpo_encoder_workspace_bytes(branches * n_slides, T, d, ff), x.device)
         pa, ga = L.ptr_array(params), L.ptr_array(grads)
         dy = dy.contiguous()
-        L.check(lib.mpo_encoder_backward(
+        L.call("mpo_encoder_backward",
             L.ptr(x), branches, n_slides, T, d, ff, heads, layers, pa, drop_p, seed, off, _epoch(), L.ptr(saved), L.ptr(dy),
-            L.ptr(dx), ga, L.ptr(ws), ws.numel(), L.stream_of(x)), "mpo_encoder_backward")
+            L.ptr(dx), ga, L.ptr(ws), ws.numel(), L.stream_of(x))
         return (dx, None, None, *grads)
 
 
@@ -796,8 +790,8 @@ class BagSelfAttentionFn(torch.autograd.Function):
         saved = torch.empty(lib.mpo_bag_self_attention_saved_floats(n_bags, m, d, heads), device=qkv.device, dtype=torch.float32)
         amap = torch.empty((n_bags, m, m), device=qkv.device, dtype=torch.float32) if need_map else None
         seed, off = _reserve(1) if drop_p > 0 else (0, 0)
-        L.check(lib.mpo_bag_self_attention_forward(L.ptr(qkv), n_bags, m, d, heads, float(drop_p), seed, off, _epoch(), L.ptr(out),
-                                                   L.ptr(saved), L.ptr(amap), L.stream_of(qkv)), "mpo_bag_self_attention_forward")
+        L.call("mpo_bag_self_attention_forward", L.ptr(qkv), n_bags, m, d, heads, float(drop_p), seed, off, _epoch(), L.ptr(out),
+               L.ptr(saved), L.ptr(amap), L.stream_of(qkv))
         ctx.save_for_backward(qkv, out, saved)
         ctx.geom, ctx.drop = (n_bags, m, d, heads), (float(drop_p), seed, off)
         if amap is not None:
@@ -813,9 +807,8 @@ class BagSelfAttentionFn(torch.autograd.Function):
         d_qkv = torch.empty_like(qkv)
         ws = _workspace(lib.mpo_bag_self_attention_workspace_bytes(n_bags, m, d, heads), qkv.device)
         d_out = d_out.contiguous()
-        L.check(lib.mpo_bag_self_attention_backward(L.ptr(qkv), L.ptr(out), L.ptr(saved), L.ptr(d_out), n_bags, m, d, heads, drop_p,
-                                                    seed, off, _epoch(), L.ptr(d_qkv), L.ptr(ws), ws.numel(), L.stream_of(qkv)),
-                "mpo_bag_self_attention_backward")
+        L.call("mpo_bag_self_attention_backward", L.ptr(qkv), L.ptr(out), L.ptr(saved), L.ptr(d_out), n_bags, m, d, heads, drop_p,
+               seed, off, _epoch(), L.ptr(d_qkv), L.ptr(ws), ws.numel(), L.stream_of(qkv))
         return d_qkv, None, None, None
 
 
@@ -851,9 +844,8 @@ class GatedPoolFn(torch.autograd.Function):
         saved = torch.empty(lib.mpo_gated_pool_saved_floats(bt, Lr, d), device=x.device, dtype=torch.float32)
         seed, off = _reserve(lib.mpo_gated_pool_rng_span(bt, Lr, d)) if (head_p > 0 or rho_p > 0) else (0, 0)
         pa = L.ptr_array(params)
-        L.check(lib.mpo_gated_pool_forward(L.ptr(x), branches, n_slides, Lr, d, pa, float(head_p), float(rho_p), seed, off,
-                                           _epoch(), L.ptr(scores), L.ptr(h), int(interleave), L.ptr(saved), L.stream_of(x)),
-                "mpo_gated_pool_forward")
+        L.call("mpo_gated_pool_forward", L.ptr(x), branches, n_slides, Lr, d, pa, float(head_p), float(rho_p), seed, off,
+               _epoch(), L.ptr(scores), L.ptr(h), int(interleave), L.ptr(saved), L.stream_of(x))
         ctx.save_for_backward(x, saved, h, *params)
         ctx.param_refs = params
         ctx.geom, ctx.drop, ctx.interleave = geom, (float(head_p), float(rho_p)), bool(interleave)
@@ -873,9 +865,9 @@ class GatedPoolFn(torch.autograd.Function):
         pa, ga = L.ptr_array(params), L.ptr_array(grads)
         dh = dh.contiguous()
         d_sc = d_scores.contiguous() if d_scores is not None else None
-        L.check(lib.mpo_gated_pool_backward(
+        L.call("mpo_gated_pool_backward",
             L.ptr(x), branches, n_slides, Lr, d, pa, head_p, rho_p, L.ptr(saved), L.ptr(h), L.ptr(dh), int(ctx.interleave),
-            L.ptr(d_sc), L.ptr(dx), ga, L.ptr(ws), ws.numel(), L.stream_of(x)), "mpo_gated_pool_backward")
+            L.ptr(d_sc), L.ptr(dx), ga, L.ptr(ws), ws.numel(), L.stream_of(x))
         return (dx, None, None, None, None, *grads)
 
 
@@ -928,8 +920,8 @@ class OmicSnnFn(torch.autograd.Function):
         saved = torch.empty(lib.mpo_omic_snn_saved_floats(n_slides, n_groups, d), device=dev, dtype=torch.float32)
         seed, off = _reserve(lib.mpo_omic_snn_rng_span(n_slides, n_groups, d)) if drop_p > 0 else (0, 0)
         xa, pa = L.ptr_array(xs), L.ptr_array(params)
-        L.check(lib.mpo_omic_snn_forward(xa, widths, n_groups, n_slides, d, pa, float(drop_p), seed, off, _epoch(),
-                                         L.ptr(g_bag), L.ptr(saved), L.stream_of(g_bag)), "mpo_omic_snn_forward")
+        L.call("mpo_omic_snn_forward", xa, widths, n_groups, n_slides, d, pa, float(drop_p), seed, off, _epoch(),
+               L.ptr(g_bag), L.ptr(saved), L.stream_of(g_bag))
         ctx.save_for_backward(g_bag, saved, *xs, *params)
         ctx.param_refs, ctx.n_groups, ctx.drop = params, n_groups, (float(drop_p), seed, off)
         return g_bag
@@ -946,9 +938,9 @@ class OmicSnnFn(torch.autograd.Function):
         grads = [grad_out(p) for p in ctx.param_refs]
         ws = _workspace(lib.mpo_omic_snn_workspace_bytes(n_slides, n, d), g_bag.device)
         xa, pa, ga = L.ptr_array(xs), L.ptr_array(params), L.ptr_array(grads)
-        L.check(lib.mpo_omic_snn_backward(xa, widths, n, n_slides, d, pa, drop_p, seed, off, _epoch(), L.ptr(g_bag),
-                                          L.ptr(saved), L.ptr(d_g.contiguous()), ga, L.ptr(ws), ws.numel(),
-                                          L.stream_of(g_bag)), "mpo_omic_snn_backward")
+        L.call("mpo_omic_snn_backward", xa, widths, n, n_slides, d, pa, drop_p, seed, off, _epoch(), L.ptr(g_bag),
+               L.ptr(saved), L.ptr(d_g.contiguous()), ga, L.ptr(ws), ws.numel(),
+               L.stream_of(g_bag))
         return (None, None, None, *([None] * n), *grads)
 
 
@@ -967,11 +959,10 @@ class MapBlockNormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, flat_map, batch: BagBatch, n_q: int):
-        lib = L.lib()
         flat_map = flat_map.contiguous()
         sq = torch.empty(batch.n_slides * n_q, device=flat_map.device, dtype=torch.float32)
-        L.check(lib.mpo_map_block_dot(L.ptr(flat_map), L.ptr(flat_map), L.ptr(batch.cu), batch.n_slides, n_q, L.ptr(sq),
-                                      L.stream_of(flat_map)), "mpo_map_block_dot")
+        L.call("mpo_map_block_dot", L.ptr(flat_map), L.ptr(flat_map), L.ptr(batch.cu), batch.n_slides, n_q, L.ptr(sq),
+               L.stream_of(flat_map))
         norm = sq.view(batch.n_slides, n_q).sum(1).sqrt()
         ctx.save_for_backward(flat_map, norm)
         ctx.batch, ctx.n_q = batch, n_q
@@ -979,12 +970,11 @@ class MapBlockNormFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_norm):
-        lib = L.lib()
         flat_map, norm = ctx.saved_tensors
         scale = (d_norm / norm.clamp_min(1e-30)).contiguous()
         d_map = torch.empty_like(flat_map)
-        L.check(lib.mpo_map_block_scale(L.ptr(flat_map), L.ptr(scale), L.ptr(ctx.batch.cu), ctx.batch.n_slides, ctx.n_q,
-                                        L.ptr(d_map), L.stream_of(flat_map)), "mpo_map_block_scale")
+        L.call("mpo_map_block_scale", L.ptr(flat_map), L.ptr(scale), L.ptr(ctx.batch.cu), ctx.batch.n_slides, ctx.n_q,
+               L.ptr(d_map), L.stream_of(flat_map))
         return d_map, None, None
 
 
@@ -998,25 +988,22 @@ class SurvivalHeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits):
-        lib = L.lib()
         ctx.set_materialize_grads(False)
         logits = logits.contiguous()
         b, c = logits.shape
         hz, sv, y = (torch.empty_like(logits) for _ in range(3))
-        L.check(lib.mpo_survival_head_forward(L.ptr(logits), b, c, L.ptr(hz), L.ptr(sv), L.ptr(y), L.stream_of(logits)),
-                "mpo_survival_head_forward")
+        L.call("mpo_survival_head_forward", L.ptr(logits), b, c, L.ptr(hz), L.ptr(sv), L.ptr(y), L.stream_of(logits))
         ctx.save_for_backward(hz, sv, y)
         return hz, sv, y
 
     @staticmethod
     def backward(ctx, dhz, dsv, dy):
-        lib = L.lib()
         hz, sv, y = ctx.saved_tensors
         b, c = hz.shape
         dhz, dsv, dy = (t.contiguous() if t is not None else None for t in (dhz, dsv, dy))
         dl = torch.empty_like(hz)
-        L.check(lib.mpo_survival_head_backward(L.ptr(hz), L.ptr(sv), L.ptr(y), L.ptr(dhz), L.ptr(dsv), L.ptr(dy), b, c,
-                                               L.ptr(dl), L.stream_of(hz)), "mpo_survival_head_backward")
+        L.call("mpo_survival_head_backward", L.ptr(hz), L.ptr(sv), L.ptr(y), L.ptr(dhz), L.ptr(dsv), L.ptr(dy), b, c,
+               L.ptr(dl), L.stream_of(hz))
         return dl
 
 
@@ -1030,7 +1017,6 @@ class CesLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, hazards, survs, label, censorship, alpha, eps):
-        lib = L.lib()
         ctx.set_materialize_grads(False)        # an unused output must not cost a zero-fill launch in backward
         hazards, survs = hazards.contiguous(), survs.contiguous()
         label = label.view(-1).to(torch.int64).contiguous()
@@ -1038,8 +1024,8 @@ class CesLossFn(torch.autograd.Function):
         b, c = hazards.shape
         loss = torch.empty(b, device=hazards.device, dtype=torch.float32)
         risk = torch.empty(b, device=hazards.device, dtype=torch.float32)
-        L.check(lib.mpo_ces_loss_forward(L.ptr(hazards), L.ptr(survs), L.ptr(label), L.ptr(censorship), b, c, float(alpha),
-                                         float(eps), L.ptr(loss), L.ptr(risk), L.stream_of(hazards)), "mpo_ces_loss_forward")
+        L.call("mpo_ces_loss_forward", L.ptr(hazards), L.ptr(survs), L.ptr(label), L.ptr(censorship), b, c, float(alpha),
+               float(eps), L.ptr(loss), L.ptr(risk), L.stream_of(hazards))
         ctx.save_for_backward(hazards, survs, label, censorship)
         ctx.cfg = (float(alpha), float(eps))
         ctx.mark_non_differentiable(risk)
@@ -1047,7 +1033,6 @@ class CesLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_loss, _d_risk):
-        lib = L.lib()
         if d_loss is None:
             return None, None, None, None, None, None
         hazards, survs, label, censorship = ctx.saved_tensors
@@ -1057,9 +1042,8 @@ class CesLossFn(torch.autograd.Function):
         scalar = d_loss.stride(0) == 0 and b > 1
         d_loss = d_loss.as_strided((1,), (1,)) if scalar else d_loss.contiguous()
         d_hz, d_sv = torch.empty_like(hazards), torch.empty_like(survs)
-        L.check(lib.mpo_ces_loss_backward(L.ptr(hazards), L.ptr(survs), L.ptr(label), L.ptr(censorship), b, c, alpha, eps,
-                                          L.ptr(d_loss), int(scalar), L.ptr(d_hz), L.ptr(d_sv), L.stream_of(hazards)),
-                "mpo_ces_loss_backward")
+        L.call("mpo_ces_loss_backward", L.ptr(hazards), L.ptr(survs), L.ptr(label), L.ptr(censorship), b, c, alpha, eps,
+               L.ptr(d_loss), int(scalar), L.ptr(d_hz), L.ptr(d_sv), L.stream_of(hazards))
         return d_hz, d_sv, None, None, None, None
 
 
@@ -1074,22 +1058,20 @@ class SctLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, label, censorship, eps):
-        lib = L.lib()
         ctx.set_materialize_grads(False)
         y = y.contiguous()
         label = label.view(-1).to(torch.int64).contiguous()
         censorship = censorship.view(-1).to(torch.float32).contiguous()
         b, c = y.shape
         loss = torch.empty(b, device=y.device, dtype=torch.float32)
-        L.check(lib.mpo_sct_loss_forward(L.ptr(y), L.ptr(label), L.ptr(censorship), b, c, float(eps), L.ptr(loss),
-                                         L.stream_of(y)), "mpo_sct_loss_forward")
+        L.call("mpo_sct_loss_forward", L.ptr(y), L.ptr(label), L.ptr(censorship), b, c, float(eps), L.ptr(loss),
+               L.stream_of(y))
         ctx.save_for_backward(y, label, censorship)
         ctx.eps = float(eps)
         return loss
 
     @staticmethod
     def backward(ctx, d_loss):
-        lib = L.lib()
         if d_loss is None:
             return None, None, None, None
         y, label, censorship = ctx.saved_tensors
@@ -1097,8 +1079,8 @@ class SctLossFn(torch.autograd.Function):
         scalar = d_loss.stride(0) == 0 and b > 1          # loss.sum().backward(): one broadcast value
         d_loss = d_loss.as_strided((1,), (1,)) if scalar else d_loss.contiguous()
         d_y = torch.empty_like(y)
-        L.check(lib.mpo_sct_loss_backward(L.ptr(y), L.ptr(label), L.ptr(censorship), b, c, ctx.eps, L.ptr(d_loss), int(scalar),
-                                          L.ptr(d_y), L.stream_of(y)), "mpo_sct_loss_backward")
+        L.call("mpo_sct_loss_backward", L.ptr(y), L.ptr(label), L.ptr(censorship), b, c, ctx.eps, L.ptr(d_loss), int(scalar),
+               L.ptr(d_y), L.stream_of(y))
         return d_y, None, None, None
 
 
@@ -1116,7 +1098,7 @@ def flat_abs_sum(x) -> torch.Tensor:
     x = x.detach().contiguous().view(-1)
     out = torch.empty(1, device=x.device, dtype=torch.float32)
     ws = _workspace(lib.mpo_abs_sum_flat_workspace_bytes(x.numel()), x.device)
-    L.check(lib.mpo_abs_sum_flat(L.ptr(x), x.numel(), L.ptr(out), L.ptr(ws), ws.numel(), L.stream_of(x)), "mpo_abs_sum_flat")
+    L.call("mpo_abs_sum_flat", L.ptr(x), x.numel(), L.ptr(out), L.ptr(ws), ws.numel(), L.stream_of(x))
     return out
 
 
@@ -1127,10 +1109,9 @@ def optim_step_flat(algorithm: str, params, grads, state1, state2, lr: float, lr
     'sgd' (state1 = state2 = None).  lr_dev (fp32 (1,)) / step_dev (int32 (1,)) override lr / step on the device."""
     if algorithm not in L.OPTIM:
         raise ValueError(f"unknown flat optimiser '{algorithm}' ({' | '.join(L.OPTIM)})")
-    L.check(L.lib().mpo_optim_step_flat(L.OPTIM[algorithm], L.ptr(params), L.ptr(grads), L.ptr(state1), L.ptr(state2),
-                                        params.numel(), float(lr), L.ptr(lr_dev), float(beta1), float(beta2), float(eps),
-                                        float(weight_decay), float(l1), int(step), L.ptr(step_dev), L.stream_of(params)),
-            "mpo_optim_step_flat")
+    L.call("mpo_optim_step_flat", L.OPTIM[algorithm], L.ptr(params), L.ptr(grads), L.ptr(state1), L.ptr(state2),
+           params.numel(), float(lr), L.ptr(lr_dev), float(beta1), float(beta2), float(eps),
+           float(weight_decay), float(l1), int(step), L.ptr(step_dev), L.stream_of(params))
 
 
 class FusionHeadFn(torch.autograd.Function):
@@ -1147,8 +1128,8 @@ class FusionHeadFn(torch.autograd.Function):
         sv, y = torch.empty_like(hz), torch.empty_like(hz)
         saved = torch.empty(lib.mpo_fusion_head_saved_floats(b, hidden, dout, c), device=hcat.device, dtype=torch.float32)
         pa = L.ptr_array(params)
-        L.check(lib.mpo_fusion_head_forward(L.ptr(hcat), b, din, hidden, dout, c, pa, L.ptr(hz), L.ptr(sv), L.ptr(y),
-                                            L.ptr(saved), L.stream_of(hcat)), "mpo_fusion_head_forward")
+        L.call("mpo_fusion_head_forward", L.ptr(hcat), b, din, hidden, dout, c, pa, L.ptr(hz), L.ptr(sv), L.ptr(y),
+               L.ptr(saved), L.stream_of(hcat))
         ctx.save_for_backward(hcat, saved, hz, sv, y, *params)
         ctx.param_refs = params
         return hz, sv, y
@@ -1164,9 +1145,9 @@ class FusionHeadFn(torch.autograd.Function):
         ws = _workspace(lib.mpo_fusion_head_workspace_bytes(b, hidden, dout, c), hcat.device)
         pa, ga = L.ptr_array(params), L.ptr_array(grads)
         dhz, dsv, dy = (t.contiguous() if t is not None else None for t in (dhz, dsv, dy))
-        L.check(lib.mpo_fusion_head_backward(
+        L.call("mpo_fusion_head_backward",
             L.ptr(hcat), b, din, hidden, dout, c, pa, L.ptr(saved), L.ptr(hz), L.ptr(sv), L.ptr(y), L.ptr(dhz), L.ptr(dsv),
-            L.ptr(dy), L.ptr(d_hcat), ga, L.ptr(ws), ws.numel(), L.stream_of(hcat)), "mpo_fusion_head_backward")
+            L.ptr(dy), L.ptr(d_hcat), ga, L.ptr(ws), ws.numel(), L.stream_of(hcat))
         return (d_hcat, *grads)
 
 
@@ -1206,15 +1187,15 @@ class FusionHeadLossFn(torch.autograd.Function):
         risk = torch.empty(b, device=dev, dtype=torch.float32)
         saved = torch.empty(lib.mpo_fusion_head_loss_saved_floats(b, hidden, dout, c), device=dev, dtype=torch.float32)
         if kind == "ces":
-            L.check(lib.mpo_fusion_head_loss_forward(
+            L.call("mpo_fusion_head_loss_forward",
                 L.ptr(hcat), b, din, hidden, dout, c, L.ptr_array(params), L.ptr(label), L.ptr(censorship), L.ptr(slide_weight),
                 float(alpha), float(eps), L.ptr(hz), L.ptr(sv), L.ptr(y), L.ptr(loss), L.ptr(risk), L.ptr(saved),
-                L.stream_of(hcat)), "mpo_fusion_head_loss_forward")
+                L.stream_of(hcat))
         else:                                   # 'sct' (fusion_head_loss_cat checked the name)
-            L.check(lib.mpo_fusion_head_sct_loss_forward(
+            L.call("mpo_fusion_head_sct_loss_forward",
                 L.ptr(hcat), b, din, hidden, dout, c, L.ptr_array(params), L.ptr(label), L.ptr(censorship), L.ptr(slide_weight),
                 float(eps), L.ptr(hz), L.ptr(sv), L.ptr(y), L.ptr(loss), L.ptr(risk), L.ptr(saved),
-                L.stream_of(hcat)), "mpo_fusion_head_sct_loss_forward")
+                L.stream_of(hcat))
         stats["head_loss_" + kind] += 1
         ctx.save_for_backward(hcat, saved, slide_weight, *params)
         ctx.param_refs = params
@@ -1235,9 +1216,9 @@ class FusionHeadLossFn(torch.autograd.Function):
         d_hcat = torch.empty_like(hcat)
         grads = [grad_out(p) for p in ctx.param_refs]
         ws = _workspace(lib.mpo_fusion_head_workspace_bytes(b, hidden, dout, c), hcat.device)
-        L.check(lib.mpo_fusion_head_loss_backward(
+        L.call("mpo_fusion_head_loss_backward",
             L.ptr(hcat), b, din, hidden, dout, c, L.ptr_array(params), L.ptr(saved), L.ptr(d_hcat), L.ptr_array(grads),
-            L.ptr(ws), ws.numel(), L.stream_of(hcat)), "mpo_fusion_head_loss_backward")
+            L.ptr(ws), ws.numel(), L.stream_of(hcat))
         return (d_hcat, None, None, None, None, None, None, *grads)
 
 
@@ -1263,7 +1244,6 @@ class GeHeadLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, label, weight, bias):
-        lib = L.lib()
         ctx.set_materialize_grads(False)
         h = h.contiguous()
         b, d = h.shape
@@ -1273,8 +1253,8 @@ class GeHeadLossFn(torch.autograd.Function):
             raise ValueError(f"ge_head_loss: {label.numel()} labels for {b} bags")
         y = torch.empty(b, c, device=h.device, dtype=torch.float32)
         loss = torch.empty(b, device=h.device, dtype=torch.float32)
-        L.check(lib.mpo_ge_head_loss_forward(L.ptr(h), b, d, c, L.ptr_array((weight, bias)), L.ptr(label), L.ptr(y), L.ptr(loss),
-                                             L.stream_of(h)), "mpo_ge_head_loss_forward")
+        L.call("mpo_ge_head_loss_forward", L.ptr(h), b, d, c, L.ptr_array((weight, bias)), L.ptr(label), L.ptr(y), L.ptr(loss),
+               L.stream_of(h))
         stats["head_loss_ce"] += 1
         ctx.save_for_backward(h, label, weight, bias)
         ctx.param_refs = (weight, bias)
@@ -1283,7 +1263,6 @@ class GeHeadLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_loss, _d_y):
-        lib = L.lib()
         h, label, weight, bias = ctx.saved_tensors
         if d_loss is None:
             return None, None, None, None
@@ -1291,9 +1270,8 @@ class GeHeadLossFn(torch.autograd.Function):
         d_loss = d_loss.to(torch.float32).contiguous()          # (loss.sum().backward() hands a stride-0 expansion)
         d_h = torch.empty_like(h)
         grads = [grad_out(p) for p in ctx.param_refs]
-        L.check(lib.mpo_ge_head_loss_backward(L.ptr(h), b, d, weight.shape[0], L.ptr_array((weight, bias)), L.ptr(label),
-                                              L.ptr(d_loss), L.ptr(d_h), L.ptr_array(grads), L.stream_of(h)),
-                "mpo_ge_head_loss_backward")
+        L.call("mpo_ge_head_loss_backward", L.ptr(h), b, d, weight.shape[0], L.ptr_array((weight, bias)), L.ptr(label),
+               L.ptr(d_loss), L.ptr(d_h), L.ptr_array(grads), L.stream_of(h))
         return (d_h, None, *grads)
 
 
@@ -1306,21 +1284,14 @@ def ge_head_loss(h, classifier, label):
 def bump_step_counters(rng_epoch=None, adam_step=None):
     """rng_epoch (int64[1]) += 1 and adam_step (int32[1]) += 1 in one launch (either may be None)."""
     t = rng_epoch if rng_epoch is not None else adam_step
-    L.check(L.lib().mpo_step_counters_bump(L.ptr(rng_epoch), L.ptr(adam_step), L.stream_of(t)), "mpo_step_counters_bump")
+    L.call("mpo_step_counters_bump", L.ptr(rng_epoch), L.ptr(adam_step), L.stream_of(t))
 
 
 # ------------------------------------------------------------------------------------ K2
-_rng_calls = 0
-
-
 def next_dropout_stream(n_elements: int):
     """(seed, offset) for one dropout mask of n_elements: the generator's counter space is carved sequentially per
     process, the seed follows torch.initial_seed() (so torch.manual_seed(rank-dependent) de-correlates ranks)."""
-    global _rng_calls
-    seed = torch.initial_seed() & 0xFFFFFFFFFFFFFFFF
-    offset = _rng_calls
-    _rng_calls += (n_elements + 3) // 4 + 1
-    return seed, offset
+    return _reserve((n_elements + 3) // 4)          # (one counter per four elements)
 
 
 def rng_state() -> dict:
@@ -1355,9 +1326,9 @@ k2_fused_patch_grad = True
 
 class CoAttnNaCAGaTFn(torch.autograd.Function):
     """NaCAGaT narrow-gated attention core over a ragged window (models/blocks.py:114-206).
-    Returns (q_proj, attn_out, post-dropout map).  K = H W_k^T + b_k is a plain GEMM done here with
-    torch (rocBLAS/hipBLASLt), like the model's patch layer; everything else is HIP.  K is always fp32,
-    also for a bf16-stored bag: the gate multiplies k's rounding error (hard part 4)."""
+    Returns (q_proj, attn_out, post-dropout map).  K = H W_k^T + b_k is formed here first, by mpo_key_projection
+    (bf16 bag, embed 256) or mpo_linear_forward (everything else).  K is always fp32, also for a bf16-stored bag: the
+    gate multiplies k's rounding error (hard part 4)."""
 
     @staticmethod
     def forward(ctx, query, bag_data, in_w, in_b, out_w, out_b, batch: BagBatch, drop_p: float, bag_relu_gate: float = 0.0,
@@ -1381,22 +1352,21 @@ class CoAttnNaCAGaTFn(torch.autograd.Function):
             # HIP key projection: bf16 bag (exact) x fp32 weights split into three bf16 terms, fp32 accumulate and output
             kbag = torch.empty(T, E, device=dev, dtype=torch.float32)
             w_k, b_k = in_w[E:2 * E], in_b[E:2 * E]
-            L.check(lib.mpo_key_projection(L.ptr(bag_data), T, E, L.ptr(w_k), L.ptr(b_k), L.ptr(kbag), L.stream_of(query)),
-                    "mpo_key_projection")
+            L.call("mpo_key_projection", L.ptr(bag_data), T, E, L.ptr(w_k), L.ptr(b_k), L.ptr(kbag), L.stream_of(query))
         elif big:
             # 'big' (models/nacagat/nacagat.py:17-18): both bags in the split-halves layout [2][T][256] of include/mpo_hip.h --
             # K half h straight out of its own GEMM (rows 256 h .. of W_k), the bag as one strided copy
             xf = bag_data.float().contiguous()
             kbag = torch.empty(2, T, 256, device=dev, dtype=torch.float32)
             for h in range(2):
-                L.check(lib.mpo_linear_forward(L.ptr(xf), L.ptr(in_w[E + 256 * h:E + 256 * (h + 1)]), L.ptr(in_b[E + 256 * h:E + 256 * (h + 1)]),
-                                               L.ptr(kbag[h]), T, E, 256, 1.0, L.ACT["none"], L.stream_of(query)), "mpo_linear_forward")
+                L.call("mpo_linear_forward", L.ptr(xf), L.ptr(in_w[E + 256 * h:E + 256 * (h + 1)]), L.ptr(in_b[E + 256 * h:E + 256 * (h + 1)]),
+                       L.ptr(kbag[h]), T, E, 256, 1.0, L.ACT["none"], L.stream_of(query))
             hb = bag_data.view(T, 2, 256).permute(1, 0, 2).contiguous()
         else:
             # fp32 bag (or the small model's bf16 bag): the exact-fp32 MFMA GEMM of the token tail in its many-row form
             kbag = torch.empty(T, E, device=dev, dtype=torch.float32)
-            L.check(lib.mpo_linear_forward(L.ptr(bag_data.float().contiguous()), L.ptr(in_w[E:2 * E]), L.ptr(in_b[E:2 * E]), L.ptr(kbag),
-                                           T, E, E, 1.0, L.ACT["none"], L.stream_of(query)), "mpo_linear_forward")
+            L.call("mpo_linear_forward", L.ptr(bag_data.float().contiguous()), L.ptr(in_w[E:2 * E]), L.ptr(in_b[E:2 * E]), L.ptr(kbag),
+                   T, E, E, 1.0, L.ACT["none"], L.stream_of(query))
         q_proj = torch.empty(R, E, device=dev, dtype=torch.float32)
         out = torch.empty(R, E, device=dev, dtype=torch.float32)
         amap = torch.empty(n_q * T, device=dev, dtype=torch.float32)
@@ -1404,11 +1374,11 @@ class CoAttnNaCAGaTFn(torch.autograd.Function):
         saved = torch.empty(lib.mpo_nacagat_saved_floats(n_slides, n_q, E), device=dev, dtype=torch.float32)
         ws = _workspace(lib.mpo_nacagat_workspace_bytes(n_slides, n_q, E, batch.max_rows, T), dev)
         seed, offset = next_dropout_stream(n_q * T) if drop_p > 0 else (0, 0)
-        L.check(lib.mpo_coattn_nacagat_forward(
+        L.call("mpo_coattn_nacagat_forward",
             L.ptr(kbag), L.MPO_F32, L.ptr(hb), L.bag_dtype_code(bag_data), L.ptr(batch.cu), n_slides, T, batch.max_rows,
             L.ptr(query), n_q, E, L.ptr(in_w), L.ptr(in_b), L.ptr(out_w), L.ptr(out_b), float(drop_p), seed, offset,
             _epoch(), L.ptr(q_proj), L.ptr(out), L.ptr(amap), L.ptr(score_maps), L.ptr(saved),
-            batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(query)), "mpo_coattn_nacagat_forward")
+            batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(query))
         ctx.save_for_backward(query, bag_data, kbag, in_w, in_b, out_w, saved, score_maps, amap)
         ctx.hb = hb if big else None                  # (the split-halves copy of the bag: kept for the backward)
         ctx.param_refs = (in_w, in_b, out_w, out_b)
@@ -1440,12 +1410,12 @@ class CoAttnNaCAGaTFn(torch.autograd.Function):
         d_ctx = torch.empty(R, E, device=dev, dtype=torch.float32) if fused_patch else None
         d_in_w, d_in_b, d_out_w, d_out_b = (grad_out(p) for p in ctx.param_refs)
         ws = _workspace(lib.mpo_nacagat_workspace_bytes(batch.n_slides, n_q, E, batch.max_rows, T), dev)
-        L.check(lib.mpo_coattn_nacagat_backward(
+        L.call("mpo_coattn_nacagat_backward",
             L.ptr(kbag), L.MPO_F32, L.ptr(hb), L.bag_dtype_code(bag_data), L.ptr(batch.cu), batch.n_slides, T,
             batch.max_rows, L.ptr(query), n_q, E, L.ptr(in_w), L.ptr(in_b), L.ptr(out_w), drop_p, seed, offset,
             _epoch(), L.ptr(saved), L.ptr(score_maps), L.ptr(amap), L.ptr(d_out), L.ptr(d_map), L.ptr(d_qproj),
             L.ptr(d_query), int(accumulate), L.ptr(d_k), L.bag_dtype_code(d_k), L.ptr(d_in_b[E:2 * E]), L.ptr(d_h), L.ptr(d_ctx), L.ptr(d_in_w), L.ptr(d_in_b), L.ptr(d_out_w),
-            L.ptr(d_out_b), batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(query)), "mpo_coattn_nacagat_backward")
+            L.ptr(d_out_b), batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(query))
         # back through the caller-side GEMM  K = H W_k^T + b_k.  The forward K stays fp32 (the gate amplifies its
         # rounding); its GRADIENT goes through bf16 operands with fp32 accumulation for a bf16 bag: dW_k as a
         # batched split-K product (one 480 000-deep fp32 contraction took 1.19 ms in rocBLAS), dH += dK W_k as a
@@ -1457,18 +1427,16 @@ class CoAttnNaCAGaTFn(torch.autograd.Function):
             if E == 256 and k2_fused_patch_grad:
                 # dH = (dK W_k + A_drop^T dctx) (.) gate in ONE hand-written pass (no library GEMM): csrc/k2_patchgrad.hip
                 d_h = torch.empty_like(d_k)
-                L.check(lib.mpo_nacagat_patch_grad_fused(L.ptr(batch.cu), batch.n_slides, T, batch.max_rows, n_q, E, L.ptr(amap),
-                                                         L.ptr(d_ctx), L.ptr(d_k), L.ptr(w_k), L.ptr(bag_data), L.ptr(d_h), gate,
-                                                         L.ptr(colsum), batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(query)),
-                        "mpo_nacagat_patch_grad_fused")
+                L.call("mpo_nacagat_patch_grad_fused", L.ptr(batch.cu), batch.n_slides, T, batch.max_rows, n_q, E, L.ptr(amap),
+                       L.ptr(d_ctx), L.ptr(d_k), L.ptr(w_k), L.ptr(bag_data), L.ptr(d_h), gate,
+                       L.ptr(colsum), batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(query))
             else:                                  # the small model (E = 128): dK W_k on the fp32 MFMA GEMM (many-row form), then the one-pass epilogue
                 dhf = torch.empty(T, E, device=dev, dtype=torch.float32)
-                L.check(lib.mpo_linear_backward_input(L.ptr(d_k.float()), L.ptr(w_k), L.ptr(dhf), T, E, E, 1.0, 0, L.stream_of(query)),
-                        "mpo_linear_backward_input")
+                L.call("mpo_linear_backward_input", L.ptr(d_k.float()), L.ptr(w_k), L.ptr(dhf), T, E, E, 1.0, 0, L.stream_of(query))
                 d_h = dhf.to(torch.bfloat16)
-                L.check(lib.mpo_nacagat_patch_grad(L.ptr(batch.cu), batch.n_slides, T, batch.max_rows, n_q, E, L.ptr(amap),
-                                                   L.ptr(d_ctx), L.ptr(d_h), L.ptr(bag_data), L.ptr(d_h), gate, L.ptr(colsum),
-                                                   batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(query)), "mpo_nacagat_patch_grad")
+                L.call("mpo_nacagat_patch_grad", L.ptr(batch.cu), batch.n_slides, T, batch.max_rows, n_q, E, L.ptr(amap),
+                       L.ptr(d_ctx), L.ptr(d_h), L.ptr(bag_data), L.ptr(d_h), gate, L.ptr(colsum),
+                       batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(query))
             if colsum is not None:
                 d_h._mpo_colsum = colsum          # the producing layer's bias gradient (PatchFcFn.backward picks it up)
             patch_weight_grad(d_k, bag_data, d_in_w[E:2 * E])     # dW_k = d_k^T H_bag (hand-written for 256 x 256, bf16)
@@ -1478,16 +1446,15 @@ class CoAttnNaCAGaTFn(torch.autograd.Function):
             s_ = L.stream_of(query)
             dkf = d_k.permute(1, 0, 2).reshape(T, E).float().contiguous()
             dhf = d_h.permute(1, 0, 2).reshape(T, E).float().contiguous()
-            L.check(lib.mpo_linear_backward_input(L.ptr(dkf), L.ptr(w_k), L.ptr(dhf), T, E, E, 1.0, 1, s_), "mpo_linear_backward_input")
-            L.check(lib.mpo_linear_backward_weight(L.ptr(dkf), L.ptr(bag_data.float().contiguous()), L.ptr(d_in_w[E:2 * E]), None, T, E, E,
-                                                   1.0, s_), "mpo_linear_backward_weight")
+            L.call("mpo_linear_backward_input", L.ptr(dkf), L.ptr(w_k), L.ptr(dhf), T, E, E, 1.0, 1, s_)
+            L.call("mpo_linear_backward_weight", L.ptr(dkf), L.ptr(bag_data.float().contiguous()), L.ptr(d_in_w[E:2 * E]), None, T, E, E,
+                   1.0, s_)
             d_h = dhf.to(bag_data.dtype)
         else:
             # fp32 bag: d_h += d_k W_k and dW_k = d_k^T H on the fp32 MFMA GEMMs (many-row / long-K forms)
             s_ = L.stream_of(query)
-            L.check(lib.mpo_linear_backward_input(L.ptr(d_k), L.ptr(w_k), L.ptr(d_h), T, E, E, 1.0, 1, s_), "mpo_linear_backward_input")
-            L.check(lib.mpo_linear_backward_weight(L.ptr(d_k), L.ptr(bag_data), L.ptr(d_in_w[E:2 * E]), None, T, E, E, 1.0, s_),
-                    "mpo_linear_backward_weight")
+            L.call("mpo_linear_backward_input", L.ptr(d_k), L.ptr(w_k), L.ptr(d_h), T, E, E, 1.0, 1, s_)
+            L.call("mpo_linear_backward_weight", L.ptr(d_k), L.ptr(bag_data), L.ptr(d_in_w[E:2 * E]), None, T, E, E, 1.0, s_)
         # (d_in_b[E:2E], the key bias gradient = column sums of d_k, came out of the kernel that wrote d_k)
         return d_query, d_h, d_in_w, d_in_b, d_out_w, d_out_b, None, None, None, None
 

@@ -3,7 +3,6 @@ host logic (ragged batches, slide assignment, C-index, ces loss) and the product
 without a GPU.  No kernel is launched here."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -18,9 +17,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "mpo_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(mpo_[a-z0-9_]+)\s*\(", text)))
+    """The header's entries, through the package's own (strict) parser: a `mpo_*(` it cannot read as a declaration raises."""
+    with open(os.path.join(ROOT, "include", "mpo_hip.h")) as f:
+        return sorted(L.parse_header(f.read())[0])
 
 
 def test_library_exports_every_declared_symbol():
