@@ -1,5 +1,5 @@
-// Generic single-pass bag kernels + N x M map kernels: the building blocks of K2, NaCAGaT's
-// narrow-gated co-attention (models/blocks.py:114-206), in its first, modular form.
+// NaCAGaT's bag passes on the matrix pipe: the building blocks of K2, the narrow-gated co-attention
+// (models/blocks.py:114-206), in its first, modular form.
 //
 //   S[n][m] = (q~[n].k[m]) * (tanh(q)[n].tanh(k)[m] + 1) / 2,  A = softmax_m(S),  A_drop = dropout(A)
 //   ctx[n]  = sum_m A_drop[n][m] H[m]          (value projection folded out: A v = (A H) W_v^T + b_v sum_m A)
@@ -10,7 +10,8 @@
 //   bag_rowdot   : map[n][m]  = sum_e X[m][e] r[n][e]                 (a = qs.K, g = tq.TK, dA = dctx.H)
 //   bag_colacc   : acc[n][e]  = sum_m W[n][m] X[m][e]   (split-M)     (ctx = A.H, dq~ = ds1.K, dtq = dg.TK)
 //   bag_outer    : dX[m][e]   = sum_n W1[n][m] Z1[n][e] + W2[n][m] Z2[n][e]   (dK, dTK, dH)
-//   map kernels  : gated softmax statistics / apply (+ dropout) / backward.
+// The kernels over the maps themselves (gated softmax statistics / apply (+ dropout) / backward) and the query-side
+// glue are in bag_maps.hip.
 // The same MFMA orientation rules as K1 apply (query index on the MFMA column).  A fully fused K2
 // (in-kernel K projection, one pass) is the planned successor; this form is parity-complete.
 #include <type_traits>
@@ -1021,388 +1022,7 @@ void bag_key_grad_kernel(const float* __restrict__ kbag, const int* __restrict__
         }
 }
 
-// ------------------------------------------------------------------ map kernels (one workgroup per (query, slide))
-constexpr int kMapThreads = 512;                               // 8 waves per (query, slide) row
-__device__ __forceinline__ float block_max(float v, float* red) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = red[0];
-#pragma unroll
-    for (int w = 1; w < kMapThreads / 64; ++w) r = fmaxf(r, red[w]);
-    return r;
-}
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = red[0];
-#pragma unroll
-    for (int w = 1; w < kMapThreads / 64; ++w) r += red[w];
-    return r;
-}
-
-// The map kernels walk a (query, slide) row of the ragged map in ALIGNED GROUPS of four elements (absolute index
-// 4G .. 4G+3): one float4 access per array and ONE draw per group (the dropout counter is index >> 2), with
-// the group's first/last elements masked at the row ends.  (Element-wise they drew once per element: 53 / 106 us.)
-struct MapRow {
-    size_t base;       // absolute index of the row's first element
-    int m_rows;
-    size_t g0;         // first group
-    int n_groups;
-    __device__ __forceinline__ MapRow(const int* cu, int n_q, int q, int b) {
-        const int row_begin = cu[b];
-        m_rows = cu[b + 1] - row_begin;
-        base = (size_t)n_q * row_begin + (size_t)q * m_rows;
-        g0 = base >> 2;
-        n_groups = (int)(((base + m_rows + 3) >> 2) - g0);
-    }
-    // lanes of group G that belong to the row: bit j set <=> element 4G + j is inside
-    __device__ __forceinline__ unsigned live(size_t G) const {
-        unsigned m = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const size_t i = 4 * G + j;
-            if (i >= base && i < base + m_rows) m |= 1u << j;
-        }
-        return m;
-    }
-};
-__device__ __forceinline__ f32x4 map_load4(const float* __restrict__ p, size_t G, unsigned live) {
-    if (live == 0xFu) return *reinterpret_cast<const f32x4*>(p + 4 * G);
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) if (live >> j & 1) v[j] = p[4 * G + j];
-    return v;
-}
-__device__ __forceinline__ void map_store4(float* __restrict__ p, size_t G, unsigned live, const f32x4& v) {
-    if (live == 0xFu) { *reinterpret_cast<f32x4*>(p + 4 * G) = v; return; }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) if (live >> j & 1) p[4 * G + j] = v[j];
-}
-// keep-scales of the four elements of group G (same draw as dropout_keep(seed, offset, 4G + j, ...))
-__device__ __forceinline__ f32x4 map_keep4(unsigned long long seed, unsigned long long offset, size_t G, float p, float inv_keep) {
-    const unsigned long long ctr = offset + G;
-    const uint4 r = draw4x32((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-    f32x4 k;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) k[j] = (float)(w[j] >> 8) * (1.0f / 16777216.0f) >= p ? inv_keep : 0.0f;
-    return k;
-}
-
-// a: log2-unit half-logits (qs2.k), g: gate dot (tq.tk).  S2 = a (g + 1).
-// Writes lse2[b][q], the (post-dropout) map A_drop in place of `amap`, and asum[b][q] = sum_m A_drop.
-__global__ __launch_bounds__(kMapThreads)
-void gated_softmax_fwd_kernel(const float* __restrict__ amap_a, const float* __restrict__ gmap, const int* __restrict__ cu,
-                              float* __restrict__ out_map, float* __restrict__ lse2, float* __restrict__ asum,
-                              int n_q, float drop_p, unsigned long long seed, unsigned long long offset_,
-                              const unsigned long long* epoch) {
-    __shared__ float red[kMapThreads / 64];
-    const unsigned long long offset = epoch_offset(offset_, epoch);
-    const int q = blockIdx.x, b = blockIdx.y;
-    const MapRow row(cu, n_q, q, b);
-    float mx = -INFINITY;
-    for (int i = threadIdx.x; i < row.n_groups; i += kMapThreads) {
-        const size_t G = row.g0 + i;
-        const unsigned lv = row.live(G);
-        const f32x4 a = map_load4(amap_a, G, lv), g = map_load4(gmap, G, lv);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if (lv >> j & 1) mx = fmaxf(mx, a[j] * (g[j] + 1.0f));
-    }
-    mx = block_max(mx, red);
-    float l = 0.f;
-    for (int i = threadIdx.x; i < row.n_groups; i += kMapThreads) {
-        const size_t G = row.g0 + i;
-        const unsigned lv = row.live(G);
-        const f32x4 a = map_load4(amap_a, G, lv), g = map_load4(gmap, G, lv);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if (lv >> j & 1) l += __builtin_amdgcn_exp2f(a[j] * (g[j] + 1.0f) - mx);
-    }
-    l = block_sum(l, red);
-    const float lse = mx + __builtin_amdgcn_logf(l);
-    const float inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
-    float s = 0.f;
-    for (int i = threadIdx.x; i < row.n_groups; i += kMapThreads) {
-        const size_t G = row.g0 + i;
-        const unsigned lv = row.live(G);
-        const f32x4 a = map_load4(amap_a, G, lv), g = map_load4(gmap, G, lv);
-        f32x4 v;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = __builtin_amdgcn_exp2f(a[j] * (g[j] + 1.0f) - lse);
-        if (drop_p > 0.f) {
-            const f32x4 k = map_keep4(seed, offset, G, drop_p, inv_keep);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] *= k[j];
-        }
-        map_store4(out_map, G, lv, v);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if (lv >> j & 1) s += v[j];
-    }
-    s = block_sum(s, red);
-    if (threadIdx.x == 0) {
-        lse2[(size_t)b * n_q + q] = lse;
-        asum[(size_t)b * n_q + q] = s;
-    }
-}
-
-// Backward of the gated softmax.  da_map holds dctx.H (from bag_rowdot) on entry; d_ext (nullable) is the
-// gradient arriving on the returned (post-dropout) map; dasum[b][q] the gradient of the row sums.
-// On exit: ds1_map[n][m] = dS (g+1)/2 (natural units, for q~.k) and dg_map[n][m] = dS * s1/2.
-__global__ __launch_bounds__(kMapThreads)
-void gated_softmax_bwd_kernel(const float* __restrict__ amap_a, const float* __restrict__ gmap, const int* __restrict__ cu,
-                              const float* __restrict__ lse2, const float* __restrict__ dasum,
-                              const float* __restrict__ d_ext, float* __restrict__ da_map /* in: dctx.H, out: ds1 */,
-                              float* __restrict__ dg_map, int n_q, float drop_p, unsigned long long seed,
-                              unsigned long long offset_, const unsigned long long* epoch) {
-    __shared__ float red[kMapThreads / 64];
-    const unsigned long long offset = epoch_offset(offset_, epoch);
-    const int q = blockIdx.x, b = blockIdx.y;
-    const MapRow row(cu, n_q, q, b);
-    const float lse = lse2[(size_t)b * n_q + q];
-    const float das = dasum[(size_t)b * n_q + q];
-    const float inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
-    float delta = 0.f;
-    for (int i = threadIdx.x; i < row.n_groups; i += kMapThreads) {
-        const size_t G = row.g0 + i;
-        const unsigned lv = row.live(G);
-        const f32x4 ah = map_load4(amap_a, G, lv), gg = map_load4(gmap, G, lv), dd = map_load4(da_map, G, lv);
-        const f32x4 de = d_ext ? map_load4(d_ext, G, lv) : f32x4{0.f, 0.f, 0.f, 0.f};
-        const f32x4 ks = drop_p > 0.f ? map_keep4(seed, offset, G, drop_p, inv_keep) : f32x4{1.f, 1.f, 1.f, 1.f};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (lv >> j & 1) {
-                const float a = __builtin_amdgcn_exp2f(ah[j] * (gg[j] + 1.0f) - lse);
-                delta += a * ks[j] * (dd[j] + das + de[j]);
-            }
-        }
-    }
-    delta = block_sum(delta, red);
-    for (int i = threadIdx.x; i < row.n_groups; i += kMapThreads) {
-        const size_t G = row.g0 + i;
-        const unsigned lv = row.live(G);
-        const f32x4 ah = map_load4(amap_a, G, lv), gg = map_load4(gmap, G, lv), dd = map_load4(da_map, G, lv);
-        const f32x4 de = d_ext ? map_load4(d_ext, G, lv) : f32x4{0.f, 0.f, 0.f, 0.f};
-        const f32x4 ks = drop_p > 0.f ? map_keep4(seed, offset, G, drop_p, inv_keep) : f32x4{1.f, 1.f, 1.f, 1.f};
-        f32x4 o1, o2;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float a = __builtin_amdgcn_exp2f(ah[j] * (gg[j] + 1.0f) - lse);
-            const float ds = a * (ks[j] * (dd[j] + das + de[j]) - delta);
-            o1[j] = ds * (gg[j] + 1.0f) * 0.5f;      // d/d(q~.k)
-            o2[j] = ds * ah[j] * kLn2;               // dS * s1/2 with s1/2 = ah / log2(e)
-        }
-        map_store4(da_map, G, lv, o1);
-        map_store4(dg_map, G, lv, o2);
-    }
-}
-
-// elementwise over a bag-shaped tensor: y = tanh(x)  /  dx += dy * (1 - y^2)
-template <typename T>
-__global__ void bag_tanh_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float v = (float)x[i];
-        const float e = __builtin_amdgcn_exp2f(v * (2.0f * kLog2e));
-        y[i] = (T)(1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f));
-    }
-}
-template <typename T>
-__global__ void bag_tanh_bwd_kernel(const T* __restrict__ y, const T* __restrict__ dy, T* __restrict__ dx, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float t = (float)y[i];
-        dx[i] = (T)((float)dx[i] + (float)dy[i] * (1.0f - t * t));
-    }
-}
-
-// q-side preparation: q [R][E] -> qt = q / sqrt(E), qs2 = qt * log2e / 2, tq = tanh(q)
-__global__ void qprep_kernel(const float* __restrict__ q, float* __restrict__ qt, float* __restrict__ qs2,
-                             float* __restrict__ tq, int n, float c_nat) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float v = q[i];
-    qt[i] = v * c_nat;
-    qs2[i] = v * c_nat * (0.5f * kLog2e);
-    tq[i] = tanhf(v);
-}
-// dq = dqt * c_nat + dtq * (1 - tq^2) [+ d_ext]
-__global__ void qprep_bwd_kernel(const float* __restrict__ dqt, const float* __restrict__ dtq, const float* __restrict__ tq,
-                                 const float* __restrict__ d_ext, float* __restrict__ dq, int n, float c_nat) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float t = tq[i];
-    dq[i] = dqt[i] * c_nat + dtq[i] * (1.0f - t * t) + (d_ext ? d_ext[i] : 0.f);
-}
-
-// y[r][:] += s[r] * b[:]      (value-bias term  b_v * sum_m A_drop)
-__global__ void row_scaled_bias_kernel(float* __restrict__ y, const float* __restrict__ s, const float* __restrict__ bias,
-                                       int rows, int cols) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows * cols) return;
-    y[i] += s[i / cols] * bias[i % cols];
-}
-
-// patch-layer epilogue: h = drop(relu(h + bias)), bf16 in place, 8 elements (16 bytes) per lane.
-// The launch guarantees (total threads) % (cols / 8) == 0, so a thread meets the same 8 columns on every
-// grid-stride iteration and keeps their biases in registers (8 scalar, poorly coalesced bias loads per
-// iteration made the first version 3x slower than a plain element-wise pass).
-__global__ void bias_relu_dropout_bf16_kernel(bf16x8* __restrict__ h, const float* __restrict__ bias, size_t n8, int cols,
-                                              float drop_p, unsigned long long seed, unsigned long long offset_,
-                                              const unsigned long long* epoch) {
-    const float inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
-    const unsigned long long offset = epoch_offset(offset_, epoch);
-    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int c0 = (int)((tid * 8) % (size_t)cols);
-    const f32x4 b0 = *reinterpret_cast<const f32x4*>(bias + c0), b1 = *reinterpret_cast<const f32x4*>(bias + c0 + 4);
-    const float bv[8] = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
-    const uint32_t thr = (uint32_t)(drop_p * 65536.0f);
-    for (size_t i = tid; i < n8; i += (size_t)gridDim.x * blockDim.x) {
-        bf16x8 v = h[i];
-        // one Philox call per 8 elements: 16 random bits each (keep iff u16 >= p * 65536)
-        uint4 r0 = {0, 0, 0, 0};
-        if (drop_p > 0.f)
-            r0 = philox4x32((uint32_t)(offset + i), (uint32_t)((offset + i) >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
-        const uint32_t rw[4] = {r0.x, r0.y, r0.z, r0.w};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float x = fmaxf((float)v[j] + bv[j], 0.f);
-            if (drop_p > 0.f) x = (((rw[j >> 1] >> (16 * (j & 1))) & 0xFFFFu) >= thr) ? x * inv_keep : 0.f;
-            v[j] = (__bf16)x;
-        }
-        h[i] = v;
-    }
-}
-// g = dy * (h > 0 ? 1/(1-p) : 0).  part_colsum (nullable, [gridDim.x][cols]): per-workgroup column sums of g -- the bias
-// gradient of the layer -- from the same pass (a thread keeps one 8-column group: the grid stride is a multiple of a row).
-__global__ __launch_bounds__(256)
-void relu_dropout_bwd_bf16_kernel(const bf16x8* __restrict__ h, const bf16x8* __restrict__ dy, bf16x8* __restrict__ g,
-                                  size_t n8, float inv_keep, int cols, float* __restrict__ part_colsum) {
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (size_t)gridDim.x * blockDim.x) {
-        const bf16x8 hv = h[i], d = dy[i];
-        bf16x8 o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (float)hv[j] > 0.f ? (__bf16)((float)d[j] * inv_keep) : (__bf16)0.f;
-        g[i] = o;
-        if (part_colsum != nullptr) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[j] += (float)o[j];
-        }
-    }
-    if (part_colsum != nullptr) {
-        __shared__ float red[256][9];
-        const int tpr = cols / 8, c8 = threadIdx.x % tpr, rl = threadIdx.x / tpr;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) red[threadIdx.x][j] = acc[j];
-        __syncthreads();
-        if (rl == 0) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float t = 0.f;
-                for (int k = 0; k < 256 / tpr; ++k) t += red[k * tpr + c8][j];
-                part_colsum[(size_t)blockIdx.x * cols + 8 * c8 + j] = t;
-            }
-        }
-    }
-}
-
-// out[c] = sum_r x[r][c] over a bf16 [rows][cols] tensor (cols = 8 * a divisor of 256): the patch layer's bias gradient.
-// Each thread owns 8 fixed columns (16-byte loads), workgroups take row chunks, fp32 atomics merge them.
-__global__ __launch_bounds__(256)
-void colsum_bf16_kernel(const bf16x8* __restrict__ x, float* __restrict__ out, size_t rows, int cols) {
-    const int tpr = cols / 8;                       // threads per row
-    const int rpb = 256 / tpr;                      // rows per block-iteration
-    const int c8 = threadIdx.x % tpr, rl = threadIdx.x / tpr;
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (size_t r = (size_t)blockIdx.x * rpb + rl; r < rows; r += (size_t)gridDim.x * rpb) {
-        const bf16x8 v = x[r * tpr + c8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] += (float)v[j];
-    }
-    __shared__ float red[256][8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) red[threadIdx.x][j] = acc[j];
-    __syncthreads();
-    if (rl == 0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float t = 0.f;
-            for (int k = 0; k < rpb; ++k) t += red[k * tpr + c8][j];
-            atomicAdd(out + 8 * c8 + j, t);
-        }
-    }
-}
-
-// torch.optim.Adam semantics (L2 weight decay folded into the gradient), one pass over the flat buffers
-__global__ void adam_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                 size_t n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                                 const int* __restrict__ step_dev) {
-    if (step_dev) {                                     // graph replay: the step count lives on the device
-        const float t = (float)(*step_dev);
-        bc1 = 1.0f - powf(b1, t);
-        bc2_sqrt = sqrtf(1.0f - powf(b2, t));
-    }
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float pi = p[i];
-        const float gi = g[i] + wd * pi;
-        const float mi = b1 * m[i] + (1.0f - b1) * gi;
-        const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        p[i] = pi - (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
-    }
-}
-
 }  // namespace
-
-int mpo_launch_adam_flat(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps,
-                         float wd, int step, const int* step_dev, hipStream_t stream) {
-    const float bc1 = 1.0f - powf(b1, (float)step), bc2s = sqrtf(1.0f - powf(b2, (float)step));
-    const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
-    adam_flat_kernel<<<blocks, 256, 0, stream>>>(p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2s, step_dev);
-    MPO_LAUNCH_CHECK();
-    return 0;
-}
-
-int mpo_launch_colsum_bf16(const void* x, float* out, size_t rows, int cols, hipStream_t stream) {
-    MPO_CHECK(cols % 8 == 0 && 256 % (cols / 8) == 0, "bf16 column sum: width %d must be 8 * a divisor of 256", cols);
-    MPO_HIP(hipMemsetAsync(out, 0, (size_t)cols * sizeof(float), stream));
-    const size_t rpb = 256 / (cols / 8);
-    size_t blocks = (rows + rpb - 1) / rpb;
-    if (blocks > 2048) blocks = 2048;
-    colsum_bf16_kernel<<<(int)blocks, 256, 0, stream>>>((const bf16x8*)x, out, rows, cols);
-    MPO_LAUNCH_CHECK();
-    return 0;
-}
-
-int mpo_launch_bias_relu_dropout_bf16(void* h, const float* bias, size_t rows, int cols, float drop_p,
-                                      unsigned long long seed, unsigned long long offset, const unsigned long long* epoch,
-                                      hipStream_t stream) {
-    MPO_CHECK(cols % 8 == 0 && 256 % (cols / 8) == 0, "patch epilogue: width %d must be 8 * a divisor of 256", cols);
-    const size_t n8 = rows * (size_t)cols / 8;
-    const int blocks = (int)((n8 + 255) / 256 < 8192 ? (n8 + 255) / 256 : 8192);   // blocks * 256 is a multiple of cols / 8
-    bias_relu_dropout_bf16_kernel<<<blocks, 256, 0, stream>>>((bf16x8*)h, bias, n8, cols, drop_p, seed, offset, epoch);
-    MPO_LAUNCH_CHECK();
-    return 0;
-}
-int mpo_relu_dropout_bwd_blocks(size_t n, int with_colsum) {
-    const size_t n8 = n / 8;
-    const size_t cap = with_colsum ? 512 : 8192;           // column sums: fewer, longer workgroups (one partial row each)
-    return (int)((n8 + 255) / 256 < cap ? (n8 + 255) / 256 : cap);
-}
-int mpo_launch_relu_dropout_bwd_bf16(const void* h, const void* dy, void* g, size_t n, float drop_p, int cols,
-                                     float* part_colsum /* nullable [blocks][cols] */, hipStream_t stream) {
-    MPO_CHECK(n % 8 == 0, "patch epilogue backward: %zu elements not a multiple of 8", n);
-    MPO_CHECK(!part_colsum || (cols >= 8 && cols % 8 == 0 && 256 % (cols / 8) == 0 && n % (size_t)cols == 0),
-              "patch epilogue backward: column sums need cols in {8,..,2048} dividing 2048 (got %d)", cols);
-    const size_t n8 = n / 8;
-    const int blocks = mpo_relu_dropout_bwd_blocks(n, part_colsum != nullptr);
-    relu_dropout_bwd_bf16_kernel<<<blocks, 256, 0, stream>>>((const bf16x8*)h, (const bf16x8*)dy, (bf16x8*)g, n8,
-                                                             drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f, cols, part_colsum);
-    MPO_LAUNCH_CHECK();
-    return 0;
-}
 
 // ---------------------------------------------------------------------------- host launchers
 #define MPO_E_SWITCH(embed, CALL)                                                     \
@@ -1522,55 +1142,6 @@ int mpo_launch_bag_outer_gated(const float* kbag, const int* cu, int n_slides, i
     } else {
         MPO_E_SWITCH(embed, (bag_outer_gated_kernel<EV, true><<<grid, 256, 0, stream>>>(kbag, cu, w1, z1, w2, z2, dk, part_colsum, n_q, plan)))
     }
-    MPO_LAUNCH_CHECK();
-    return 0;
-}
-
-int mpo_launch_gated_softmax_fwd(const float* amap_a, const float* gmap, const int* cu, float* out_map, float* lse2,
-                                 float* asum, int n_slides, int n_q, float drop_p, unsigned long long seed,
-                                 unsigned long long offset, const unsigned long long* epoch, hipStream_t stream) {
-    gated_softmax_fwd_kernel<<<dim3(n_q, n_slides), kMapThreads, 0, stream>>>(amap_a, gmap, cu, out_map, lse2, asum, n_q, drop_p, seed, offset, epoch);
-    MPO_LAUNCH_CHECK();
-    return 0;
-}
-
-int mpo_launch_gated_softmax_bwd(const float* amap_a, const float* gmap, const int* cu, const float* lse2,
-                                 const float* dasum, const float* d_ext, float* da_map, float* dg_map, int n_slides,
-                                 int n_q, float drop_p, unsigned long long seed, unsigned long long offset,
-                                 const unsigned long long* epoch, hipStream_t stream) {
-    gated_softmax_bwd_kernel<<<dim3(n_q, n_slides), kMapThreads, 0, stream>>>(amap_a, gmap, cu, lse2, dasum, d_ext, da_map, dg_map, n_q,
-                                                                      drop_p, seed, offset, epoch);
-    MPO_LAUNCH_CHECK();
-    return 0;
-}
-
-int mpo_launch_bag_tanh_fwd(const void* x, void* y, size_t n, int f32, hipStream_t stream) {
-    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    if (f32) bag_tanh_fwd_kernel<float><<<blocks, 256, 0, stream>>>((const float*)x, (float*)y, n);
-    else bag_tanh_fwd_kernel<__bf16><<<blocks, 256, 0, stream>>>((const __bf16*)x, (__bf16*)y, n);
-    MPO_LAUNCH_CHECK();
-    return 0;
-}
-int mpo_launch_bag_tanh_bwd(const void* y, const void* dy, void* dx, size_t n, int f32, hipStream_t stream) {
-    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    if (f32) bag_tanh_bwd_kernel<float><<<blocks, 256, 0, stream>>>((const float*)y, (const float*)dy, (float*)dx, n);
-    else bag_tanh_bwd_kernel<__bf16><<<blocks, 256, 0, stream>>>((const __bf16*)y, (const __bf16*)dy, (__bf16*)dx, n);
-    MPO_LAUNCH_CHECK();
-    return 0;
-}
-int mpo_launch_qprep(const float* q, float* qt, float* qs2, float* tq, int n, float c_nat, hipStream_t stream) {
-    qprep_kernel<<<(n + 255) / 256, 256, 0, stream>>>(q, qt, qs2, tq, n, c_nat);
-    MPO_LAUNCH_CHECK();
-    return 0;
-}
-int mpo_launch_qprep_bwd(const float* dqt, const float* dtq, const float* tq, const float* d_ext, float* dq, int n,
-                         float c_nat, hipStream_t stream) {
-    qprep_bwd_kernel<<<(n + 255) / 256, 256, 0, stream>>>(dqt, dtq, tq, d_ext, dq, n, c_nat);
-    MPO_LAUNCH_CHECK();
-    return 0;
-}
-int mpo_launch_row_scaled_bias(float* y, const float* s, const float* bias, int rows, int cols, hipStream_t stream) {
-    row_scaled_bias_kernel<<<(rows * cols + 255) / 256, 256, 0, stream>>>(y, s, bias, rows, cols);
     MPO_LAUNCH_CHECK();
     return 0;
 }

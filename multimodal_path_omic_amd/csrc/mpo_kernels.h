@@ -206,13 +206,14 @@ int mpo_launch_map_block_scale(const float* a_map, const float* scale, const int
 int mpo_launch_map_rowdot(const float* a_map, const float* da_map, const int* cu, float* delta, int n_slides, int n_q,
                           int accumulate, hipStream_t stream);
 
-// ---- generic bag / map kernels (bagops.hip): the modular form of K2
+// ---- the modular form of K2: bag passes (bagops.hip)
 int mpo_launch_bag_rowdot(const void* bag, int bag_f32, const int* cu, int n_slides, int embed, const float* r,
                           float* map, float alpha, int n_q, const BagPlan& plan, hipStream_t stream);
 int mpo_launch_bag_colacc(const void* bag, int bag_f32, const int* cu, int n_slides, int embed, const float* wmap,
                           float* part, int n_q, const BagPlan& plan, hipStream_t stream);
 int mpo_launch_bag_outer(const int* cu, int n_slides, int embed, const float* w1, const float* z1, const float* w2,
                          const float* z2, void* dx, int out_f32, int n_q, const BagPlan& plan, hipStream_t stream);
+// ---- kernels over its ragged maps and the query-side glue (bag_maps.hip)
 int mpo_launch_gated_softmax_fwd(const float* amap_a, const float* gmap, const int* cu, float* out_map, float* lse2,
                                  float* asum, int n_slides, int n_q, float drop_p, unsigned long long seed,
                                  unsigned long long offset, const unsigned long long* epoch, hipStream_t stream);
@@ -220,8 +221,6 @@ int mpo_launch_gated_softmax_bwd(const float* amap_a, const float* gmap, const i
                                  const float* dasum, const float* d_ext, float* da_map, float* dg_map, int n_slides,
                                  int n_q, float drop_p, unsigned long long seed, unsigned long long offset,
                                  const unsigned long long* epoch, hipStream_t stream);
-int mpo_launch_bag_tanh_fwd(const void* x, void* y, size_t n, int f32, hipStream_t stream);
-int mpo_launch_bag_tanh_bwd(const void* y, const void* dy, void* dx, size_t n, int f32, hipStream_t stream);
 int mpo_launch_qprep(const float* q, float* qt, float* qs2, float* tq, int n, float c_nat, hipStream_t stream);
 int mpo_launch_qprep_bwd(const float* dqt, const float* dtq, const float* tq, const float* d_ext, float* dq, int n,
                          float c_nat, hipStream_t stream);
@@ -241,10 +240,6 @@ int mpo_launch_ln_fwd_br(const float* x, const LnBranches& p, float* y, float* s
 // what: 1 = dx, 2 = parameter gradients, 3 = both in one launch
 int mpo_launch_ln_bwd_br(const float* dy, const float* x, const float* stats, const LnBranches& p, float* dx, int rows, int d,
                          int accumulate, int what, hipStream_t s);
-int mpo_launch_ln_fwd(const float* x, const float* w, const float* b, float* y, float* stats, int rows, int d, float eps,
-                      hipStream_t s);
-int mpo_launch_ln_bwd(const float* dy, const float* x, const float* stats, const float* w, float* dx, float* dw, float* db,
-                      int rows, int d, int accumulate, hipStream_t s);
 int mpo_launch_ln_bwd_params_only(const float* dy, const float* x, const float* stats, float* dw, float* db, int rows, int d,
                                   hipStream_t s);
 // longest token axis the LDS-resident attention kernels of tail.hip take; longer axes (the rows of a bag) run bag_selfattn.hip
@@ -308,7 +303,7 @@ int mpo_launch_cag_mid_bwd(const float* dm, const float* t1, const float* t3, co
                            const float* gw, const float* ew, const float* stats_g, const float* stats_e, float* dG, float* dE,
                            float* ds12, float* ds3, int rows, int d, hipStream_t s);
 
-// h = drop(relu(h + bias)) in place on a bf16 [rows][cols] tensor (the patch layer's epilogue)
+// h = drop(relu(h + bias)) in place on a bf16 [rows][cols] tensor (the patch layer's epilogue, patch_epilogue.hip)
 int mpo_launch_bias_relu_dropout_bf16(void* h, const float* bias, size_t rows, int cols, float drop_p,
                                       unsigned long long seed, unsigned long long offset, const unsigned long long* epoch,
                                       hipStream_t stream);
@@ -316,7 +311,9 @@ int mpo_launch_bias_relu_dropout_bf16(void* h, const float* bias, size_t rows, i
 int mpo_relu_dropout_bwd_blocks(size_t n, int with_colsum);
 int mpo_launch_relu_dropout_bwd_bf16(const void* h, const void* dy, void* g, size_t n, float drop_p, int cols,
                                      float* part_colsum /* nullable [blocks][cols] */, hipStream_t stream);
+int mpo_launch_colsum_bf16(const void* x, float* out, size_t rows, int cols, hipStream_t stream);
 
+// the headline step's Adam (optim.hip)
 int mpo_launch_adam_flat(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps,
                          float wd, int step, const int* step_dev, hipStream_t stream);
 // flat optimiser family (optim.hip): algorithm = MPO_OPTIM_*; state1/state2 per algorithm (see include/mpo_hip.h)
@@ -325,9 +322,8 @@ int mpo_launch_optim_flat(int algorithm, float* p, const float* g, float* s1, fl
                           const int* step_dev, hipStream_t stream);
 size_t mpo_abs_sum_partials(size_t n);
 int mpo_launch_abs_sum(const float* x, size_t n, float* partials, float* out, hipStream_t stream);
-int mpo_launch_colsum_bf16(const void* x, float* out, size_t rows, int cols, hipStream_t stream);
 
-// gated (tanh on the fly) single-pass variants for K2 (bagops.hip)
+// gated (tanh on the fly) single-pass bag passes for K2 (bagops.hip)
 int mpo_launch_bag_rowdot_gated(const void* bag, int bag_f32, const int* cu, int n_slides, int embed, const float* r1,
                                 const float* r2, float* a_map, float* g_map, int n_q, const BagPlan& plan, hipStream_t stream);
 int mpo_launch_bag_colacc_gated(const void* bag, int bag_f32, const int* cu, int n_slides, int embed, const float* w1map,

@@ -87,6 +87,29 @@ void optim_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float
     }
 }
 
+// The benchmark's headline optimiser (mpo_adam_step_flat, dp.FlatAdam): the same Adam rule element by element, without the
+// L1 fold, the device learning rate and the 16-byte accesses of optim_flat_kernel<MPO_OPTIM_ADAM>.  The two agree to a few
+// ulps, not bit for bit, so it stays a kernel of its own.
+// torch.optim.Adam semantics (L2 weight decay folded into the gradient), one pass over the flat buffers
+__global__ void adam_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                 size_t n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
+                                 const int* __restrict__ step_dev) {
+    if (step_dev) {                                     // graph replay: the step count lives on the device
+        const float t = (float)(*step_dev);
+        bc1 = 1.0f - powf(b1, t);
+        bc2_sqrt = sqrtf(1.0f - powf(b2, t));
+    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const float pi = p[i];
+        const float gi = g[i] + wd * pi;
+        const float mi = b1 * m[i] + (1.0f - b1) * gi;
+        const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+        m[i] = mi;
+        v[i] = vi;
+        p[i] = pi - (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
+    }
+}
+
 // sum |x|, stage 1: a fixed grid (a function of n only) of per-block partial sums, no atomics
 constexpr int kAbsThreads = 256, kAbsMaxBlocks = 1024;
 __global__ __launch_bounds__(kAbsThreads)
@@ -126,6 +149,15 @@ void abs_sum_final_kernel(const float* __restrict__ partials, int n_part, float*
 inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
 
 }  // namespace
+
+int mpo_launch_adam_flat(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps,
+                         float wd, int step, const int* step_dev, hipStream_t stream) {
+    const float bc1 = 1.0f - powf(b1, (float)step), bc2s = sqrtf(1.0f - powf(b2, (float)step));
+    const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+    adam_flat_kernel<<<blocks, 256, 0, stream>>>(p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2s, step_dev);
+    MPO_LAUNCH_CHECK();
+    return 0;
+}
 
 int mpo_launch_optim_flat(int algorithm, float* p, const float* g, float* s1, float* s2, size_t n, float lr,
                           const float* lr_dev, float b1, float b2, float eps, float wd, float l1, int step,

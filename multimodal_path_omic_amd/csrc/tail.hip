@@ -944,14 +944,6 @@ static LnBranches one_branch(const float* w, const float* b, float* dw, float* d
     p.n = 1; p.rows_per_branch = rows; p.w[0] = w; p.b[0] = b; p.dw[0] = dw; p.db[0] = db;
     return p;
 }
-int mpo_launch_ln_fwd(const float* x, const float* w, const float* b, float* y, float* stats, int rows, int d, float eps,
-                      hipStream_t s) {
-    return mpo_launch_ln_fwd_br(x, one_branch(w, b, nullptr, nullptr, rows), y, stats, rows, d, eps, s);
-}
-int mpo_launch_ln_bwd(const float* dy, const float* x, const float* stats, const float* w, float* dx, float* dw, float* db,
-                      int rows, int d, int accumulate, hipStream_t s) {
-    return mpo_launch_ln_bwd_br(dy, x, stats, one_branch(w, nullptr, dw, db, rows), dx, rows, d, accumulate, dw ? 3 : 1, s);
-}
 int mpo_launch_ln_bwd_params_only(const float* dy, const float* x, const float* stats, float* dw, float* db, int rows, int d,
                                   hipStream_t s) {
     return mpo_launch_ln_bwd_br(dy, x, stats, one_branch(nullptr, nullptr, dw, db, rows), nullptr, rows, d, 0, 2, s);

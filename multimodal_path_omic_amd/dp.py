@@ -86,7 +86,6 @@ class FlatGradBucket:
                 dist.all_reduce(self.flat, op=dist.ReduceOp.SUM, group=group)
                 self.flat.div_(dist.get_world_size(group))
 
-
     def all_reduce_mean_async(self, lo: int = 0, hi: int = None, group=None):
         """Start the mean all-reduce of flat[lo:hi] and return a handle whose wait() orders the current stream behind it
         (None when there is nothing to reduce): lets the caller keep computing into OTHER slices of the bucket meanwhile."""
@@ -132,7 +131,7 @@ def _host_clone(t: torch.Tensor) -> torch.Tensor:
 
 class _TorchStateDict:
     """state_dict() / load_state_dict() of the flat optimisers in the format of the torch.optim class they restate, so that
-    either side continues a run of the other.  Expects bucket, algorithm, lr, betas, eps, wd, t_dev and _moments()."""
+    either side continues a run of the other.  Expects lr, betas, eps, wd and what _FlatState holds."""
 
     def _param_group(self, n_params: int) -> dict:
         """The one param group as the installed torch.optim class writes it: its own key set and flag defaults."""
@@ -254,57 +253,69 @@ class _TorchStateDict:
             self.betas, self.eps = (float(group["rho"]), 0.0), float(group["eps"])
 
 
-class FlatAdam(_TorchStateDict):
-    """torch.optim.Adam(lr, betas, eps, weight_decay) (the reference's default optimiser,
-    models/mcat/main.py:284-300) as ONE HIP kernel over flat buffers: parameters are re-pointed at slices of
-    a flat fp32 buffer laid out like the gradient bucket; exp_avg / exp_avg_sq are flat too."""
-
-    algorithm = "adam"
-
-    def __init__(self, bucket: FlatGradBucket, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        self.bucket, self.lr, self.betas, self.eps, self.wd = bucket, lr, betas, eps, weight_decay
-        self.flat_p = torch.zeros_like(bucket.flat)
-        for p, off in zip(bucket.params, bucket.offsets):
-            sl = self.flat_p[off:off + p.numel()].view_as(p)
-            sl.copy_(p.data)
-            p.data = sl
-        self.exp_avg = torch.zeros_like(self.flat_p)
-        self.exp_avg_sq = torch.zeros_like(self.flat_p)
-        self.t_dev = torch.zeros(1, dtype=torch.int32, device=self.flat_p.device)   # step count, device-resident
-
-    def step(self, bump: bool = True):
-        """One update.  The step count is incremented and read on the device, so the call can sit inside a
-        captured HIP graph and still apply the right bias correction on every replay.  bump=False: the caller has
-        advanced t_dev already (ops.bump_step_counters, one launch for it and the dropout epoch)."""
-        from . import _lib as L
-        if bump:
-            self.t_dev += 1
-        b = self.bucket
-        L.call("mpo_adam_step_flat", L.ptr(self.flat_p), L.ptr(b.flat), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-               self.flat_p.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
-               0, L.ptr(self.t_dev), L.stream_of(self.flat_p))
-
-    def state_tensors(self):
-        """Every tensor a step writes (what a warm-up that must not train puts back)."""
-        return [self.flat_p, self.exp_avg, self.exp_avg_sq, self.t_dev]
-
-    def _moments(self):
-        return [self.exp_avg, self.exp_avg_sq]
-
-
-def _repoint_params(bucket: FlatGradBucket) -> torch.Tensor:
+def _repoint_params(bucket: FlatGradBucket, tag: bool) -> torch.Tensor:
     """Flat fp32 parameter buffer laid out like the gradient bucket; every parameter is re-pointed at its slice (the padding
-    between slices stays zero, and every update below keeps it zero)."""
+    between slices stays zero, and every update below keeps it zero).  tag: mark each parameter with its buffer
+    (`_mpo_flat_param_base`): harness.weights_abs_sum then reduces the buffer once instead of every parameter."""
     flat_p = torch.zeros_like(bucket.flat)
     for p, off in zip(bucket.params, bucket.offsets):
         sl = flat_p[off:off + p.numel()].view_as(p)
         sl.copy_(p.data)
         p.data = sl
-        p._mpo_flat_param_base = flat_p
+        if tag:
+            p._mpo_flat_param_base = flat_p
     return flat_p
 
 
-class FlatOptimizer(_TorchStateDict):
+class _FlatState(_TorchStateDict):
+    """What the flat optimisers share: parameters re-pointed into `flat_p`, the two flat moments of `algorithm` (`state1`,
+    `state2`; None for sgd) and the step count `t_dev`.  The count is incremented and read on the device, so a step can sit
+    inside a captured HIP graph and still apply the right bias correction on every replay."""
+
+    def _allocate(self, bucket: FlatGradBucket, tag_params: bool):
+        self.bucket = bucket
+        self.flat_p = _repoint_params(bucket, tag_params)
+        stateful = self.algorithm != "sgd"
+        self.state1 = torch.zeros_like(self.flat_p) if stateful else None
+        self.state2 = torch.zeros_like(self.flat_p) if stateful else None
+        self.t_dev = torch.zeros(1, dtype=torch.int32, device=self.flat_p.device)
+
+    def _advance(self, bump: bool):
+        """bump=False: the caller has advanced t_dev already (ops.bump_step_counters: one launch for it and the epoch)."""
+        if bump:
+            self.t_dev += 1
+
+    def _moments(self):
+        return [] if self.state1 is None else [self.state1, self.state2]
+
+    def state_tensors(self):
+        """Every tensor a step writes (what a warm-up that must not train puts back)."""
+        return [self.flat_p, *self._moments(), self.t_dev]
+
+
+class FlatAdam(_FlatState):
+    """torch.optim.Adam(lr, betas, eps, weight_decay) (the reference's default optimiser,
+    models/mcat/main.py:284-300) as ONE HIP kernel over flat buffers (mpo_adam_step_flat): parameters are re-pointed at
+    slices of a flat fp32 buffer laid out like the gradient bucket; exp_avg / exp_avg_sq are flat too.  Its parameters
+    carry no `_mpo_flat_param_base`: an L1 penalty on a FlatAdam run is summed parameter by parameter, as it always was."""
+
+    algorithm = "adam"
+
+    def __init__(self, bucket: FlatGradBucket, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
+        self._allocate(bucket, tag_params=False)
+        self.exp_avg, self.exp_avg_sq = self.state1, self.state2
+
+    def step(self, bump: bool = True):
+        """One update (bump: see _advance)."""
+        from . import _lib as L
+        self._advance(bump)
+        L.call("mpo_adam_step_flat", L.ptr(self.flat_p), L.ptr(self.bucket.flat), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
+               self.flat_p.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+               0, L.ptr(self.t_dev), L.stream_of(self.flat_p))
+
+
+class FlatOptimizer(_FlatState):
     """The reference's training.optimizer choices (models/mcat/main.py:284-300) as ONE HIP pass over flat buffers
     (mpo_optim_step_flat): 'adam' | 'adamax' | 'adadelta' | 'sgd', torch.optim 2.x single-tensor arithmetic in fp32.
     Parameters are re-pointed at slices of a flat buffer as in FlatAdam.
@@ -324,33 +335,21 @@ class FlatOptimizer(_TorchStateDict):
         if algorithm not in self.DEFAULTS:
             raise ValueError(f"unknown flat optimiser '{algorithm}' ({' | '.join(self.DEFAULTS)})")
         d = self.DEFAULTS[algorithm]
-        self.bucket, self.algorithm = bucket, algorithm
+        self.algorithm = algorithm
         self.betas = tuple(betas) if betas is not None else d["betas"]
         if algorithm == "adadelta":
             self.betas = (0.9 if rho is None else float(rho), 0.0)
         self.eps = d["eps"] if eps is None else float(eps)
         self.wd = float(weight_decay)
         self.l1_lambda = float(l1_lambda or 0.0)
-        self.flat_p = _repoint_params(bucket)
-        dev = self.flat_p.device
-        stateful = algorithm != "sgd"
-        self.state1 = torch.zeros_like(self.flat_p) if stateful else None
-        self.state2 = torch.zeros_like(self.flat_p) if stateful else None
-        self.t_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._allocate(bucket, tag_params=True)
         self.lr = float(lr)
-        self.lr_dev = torch.full((1,), self.lr, dtype=torch.float32, device=dev)
+        self.lr_dev = torch.full((1,), self.lr, dtype=torch.float32, device=self.flat_p.device)
 
     def set_lr(self, lr: float):
         """New learning rate (host value and the device scalar a captured step reads).  Call outside graph capture."""
         self.lr = float(lr)
         self.lr_dev.fill_(self.lr)
-
-    def state_tensors(self):
-        """Every tensor a step writes (what a warm-up that must not train puts back)."""
-        return [t for t in (self.flat_p, self.state1, self.state2, self.t_dev) if t is not None]
-
-    def _moments(self):
-        return [] if self.state1 is None else [self.state1, self.state2]
 
     def l1_value(self) -> torch.Tensor:
         """sum |p| over the flat parameters as a device scalar (deterministic; ops.flat_abs_sum)."""
@@ -358,13 +357,12 @@ class FlatOptimizer(_TorchStateDict):
         return ops.flat_abs_sum(self.flat_p)
 
     def step(self, bump: bool = True, l1_slides: "int | None" = None):
-        """One update.  bump=False: the caller advanced t_dev already (ops.bump_step_counters).  l1_slides: the number of
-        slides whose losses carried the L1 penalty since the last step (all ranks); required when l1_lambda > 0."""
+        """One update (bump: see _advance).  l1_slides: the number of slides whose losses carried the L1 penalty since the
+        last step (all ranks); required when l1_lambda > 0."""
         from . import ops
         if self.l1_lambda and l1_slides is None:
             raise ValueError("FlatOptimizer.step: l1_lambda > 0 needs l1_slides (slides of the window over all ranks)")
-        if bump:
-            self.t_dev += 1
+        self._advance(bump)
         l1 = self.l1_lambda * l1_slides if self.l1_lambda else 0.0
         ops.optim_step_flat(self.algorithm, self.flat_p, self.bucket.flat, self.state1, self.state2, self.lr, self.lr_dev,
                             self.betas[0], self.betas[1], self.eps, self.wd, l1, 1, self.t_dev)

@@ -1,4 +1,4 @@
-"""The optimiser of every training step, mpo_adam_step_flat (csrc/bagops.hip adam_flat_kernel) and its wrapper dp.FlatAdam,
+"""The optimiser of every training step, mpo_adam_step_flat (csrc/optim.hip adam_flat_kernel) and its wrapper dp.FlatAdam,
 against fp64 torch.optim.Adam driven by the same gradient sequence: 20 steps, gradients spanning 1e-6 .. 1e2 with exact
 zeros, with and without weight decay, both step-count paths (the device counter FlatAdam and captured graphs use, a
 host step >= 1), and a parameter count past the launch's 2048 x 256 threads (the grid-stride loop)."""
