@@ -231,6 +231,24 @@ int mpo_abs_sum_flat(const float* x, int64_t n, float* out, void* workspace, siz
  * are bit-identical.  enabled = 0 sends everything through the general body.  Returns the previous setting (default 1). */
 int mpo_set_gemm_fast_path(int enabled);
 
+/* Verification hooks (tests): which body the fp32 GEMM launcher (csrc/gemm_f32.hip) picked.  Plain host ints written while
+ * the launcher routes a product: no device work, no effect on any result.  Like the selectors they are process-global and
+ * NOT thread-safe: a test reads them on the thread that made the call, with no other thread inside the library.
+ *   mpo_gemm_last_route()         the body of the most recent single-product launch (mpo_linear_* and every product an
+ *                                 entry launches on its own): one MPO_GEMM_ROUTE_* code; MPO_GEMM_ROUTE_NONE before the first.
+ *   mpo_gemm_last_group_routes()  grouped launches: bit (1 << code) for every body used -- one bit per member that left the
+ *                                 group for the rows or long-K body, one for the body that ran the remainder.  An entry makes
+ *                                 several grouped launches per call, so the mask collects (ORs) over all of them since the
+ *                                 previous call of this getter, which returns it and clears it: read once to discard, run the
+ *                                 entry, read again.
+ * general-nb4 / -nb8: the guarded body with 4 / 8 k-blocks in flight per wave; fast: the branch-free body; rows: 32 x 64 tiles
+ * for products with many rows; longk: K cut into slices, partial blocks added atomically.  DESIGN.md ("fp32 GEMM routing")
+ * has the predicates; tests/test_gpu_gemm_routes.py pins the expected code of every edge.  Additive to ABI 14. */
+enum { MPO_GEMM_ROUTE_NONE = 0, MPO_GEMM_ROUTE_GENERAL_NB4 = 1, MPO_GEMM_ROUTE_GENERAL_NB8 = 2, MPO_GEMM_ROUTE_FAST = 3,
+       MPO_GEMM_ROUTE_ROWS = 4, MPO_GEMM_ROUTE_LONGK = 5 };
+int mpo_gemm_last_route(void);
+int mpo_gemm_last_group_routes(void);
+
 /* Verification hook (tests): K1's backward bag pass has a two-waves-per-SIMD kernel for a bf16 bag at embed_dim 256 with at most 8
  * queries and no gradient on the map (csrc/coattn_bwd8.hip) and a general kernel for everything else (csrc/coattn_bwd.hip).
  * enabled = 0 sends every geometry through the general kernel.  Returns the previous setting (default 1).  ABI v11. */

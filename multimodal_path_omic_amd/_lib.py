@@ -81,6 +81,7 @@ _signatures, _constants, ABI_VERSION = _read_header()
 MPO_F32, MPO_BF16 = _constants["MPO_F32"], _constants["MPO_BF16"]
 ACT = {k[len("MPO_ACT_"):-1].lower(): v for k, v in _constants.items() if k.startswith("MPO_ACT_")}      # MPO_ACT_RELU_ -> relu
 OPTIM = {k[len("MPO_OPTIM_"):].lower(): v for k, v in _constants.items() if k.startswith("MPO_OPTIM_")}
+GEMM_ROUTE = {k[len("MPO_GEMM_ROUTE_"):].lower(): v for k, v in _constants.items() if k.startswith("MPO_GEMM_ROUTE_")}
 
 
 class BagPlanC(ctypes.Structure):

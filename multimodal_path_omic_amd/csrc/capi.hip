@@ -726,6 +726,8 @@ int mpo_abs_sum_flat(const float* x, int64_t n, float* out, void* workspace, siz
 // Verification hook: the small-row GEMMs have a branch-free body for regular products and a general body; both must
 // give the same bits.  enabled = 0 routes every product through the general body.  Returns the previous setting.
 int mpo_set_gemm_fast_path(int enabled) { return mpo_gemm_fast_path(enabled); }
+int mpo_gemm_last_route(void) { return mpo_gemm_route_last(); }
+int mpo_gemm_last_group_routes(void) { return mpo_gemm_route_group_take(); }
 int mpo_set_coattn_bwd_two_wave(int enabled) { return mpo_coattn_bwd8_enable(enabled); }
 // verification hook: 0 = fp32 bags take the general (matrix-pipe) K1 backward
 int mpo_set_coattn_bwd_f32_vector(int enabled) { return mpo_coattn_bwd_f32_enable(enabled); }

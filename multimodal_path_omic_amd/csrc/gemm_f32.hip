@@ -13,6 +13,7 @@
 //
 // The kernels live in gemm_f32_direct.h (16 x 16 outputs per workgroup, the four waves split K, fragments
 // straight from L2); this file holds the launchers and the bias-gradient column sum.
+#include "../../include/mpo_hip.h"          // MPO_GEMM_ROUTE_*
 #include "mpo_common.h"
 #include "mpo_kernels.h"
 #include "gemm_f32_gate.h"
@@ -35,6 +36,9 @@ inline int direct_nbmax(int k) { return k <= 256 ? 4 : DMAXB; }
 // A product the branch-free body (gemm_f32_fast.h) can run: whole tiles, whole k-blocks per wave, vector-loadable
 // operands, a gate it knows at compile time.  Everything else goes through the general body.
 bool g_fast_path = true;                   // mpo_set_gemm_fast_path(): verification hook, on in production
+// mpo_gemm_last_route() / mpo_gemm_last_group_routes(): verification hooks, plain host ints (not thread-safe, like g_fast_path)
+int g_last_route = MPO_GEMM_ROUTE_NONE;    // body of the most recent single-product launch
+int g_group_routes = 0;                    // 1 << route of every body grouped launches used since the mask was last read
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // -> gate class of a product (0 none, 1 value gate, 2 regenerated dropout, 3 AlphaDropout + ELU derivative), or -1: a gate the
 // special bodies do not know, or a value gate that is missing (or, where the body loads it as vectors, not 16-byte aligned)
@@ -75,13 +79,13 @@ inline void launch_longk(const GemmArgs& g, int gate_class, hipStream_t stream) 
 }
 void launch_direct_single(const GemmArgs& g, int layout, dim3 grid, hipStream_t stream) {
     const int rc = rows_class(g, layout);
-    if (rc >= 0) { mpo_rows_single(g, layout, rc, stream); return; }
+    if (rc >= 0) { g_last_route = MPO_GEMM_ROUTE_ROWS; mpo_rows_single(g, layout, rc, stream); return; }
     const int lc = longk_class(g, layout);
-    if (lc >= 0) { launch_longk(g, lc, stream); return; }
+    if (lc >= 0) { g_last_route = MPO_GEMM_ROUTE_LONGK; launch_longk(g, lc, stream); return; }
     const int fc = fast_class(g);
-    if (fc >= 0) { mpo_fast_single(g, layout, fc, direct_nbmax(g.K), grid, stream); return; }
-    if (direct_nbmax(g.K) == 4) mpo_direct_single_nb4(g, layout, grid, stream);
-    else mpo_direct_single_nb8(g, layout, grid, stream);
+    if (fc >= 0) { g_last_route = MPO_GEMM_ROUTE_FAST; mpo_fast_single(g, layout, fc, direct_nbmax(g.K), grid, stream); return; }
+    if (direct_nbmax(g.K) == 4) { g_last_route = MPO_GEMM_ROUTE_GENERAL_NB4; mpo_direct_single_nb4(g, layout, grid, stream); }
+    else { g_last_route = MPO_GEMM_ROUTE_GENERAL_NB8; mpo_direct_single_nb8(g, layout, grid, stream); }
 }
 // grid over the largest member of a group; false: no member has an output
 inline bool group_extent(const GemmGroup& grp, dim3& grid) {
@@ -97,8 +101,8 @@ void launch_direct_group(const GemmGroup& all, dim3 grid, hipStream_t stream) {
     grp.n = 0;
     for (int i = 0; i < all.n; ++i) {
         const int rc = rows_class(all.g[i], all.g[i].layout), lc = longk_class(all.g[i], all.g[i].layout);
-        if (rc >= 0) mpo_rows_single(all.g[i], all.g[i].layout, rc, stream);
-        else if (lc >= 0) launch_longk(all.g[i], lc, stream);
+        if (rc >= 0) { g_group_routes |= 1 << MPO_GEMM_ROUTE_ROWS; mpo_rows_single(all.g[i], all.g[i].layout, rc, stream); }
+        else if (lc >= 0) { g_group_routes |= 1 << MPO_GEMM_ROUTE_LONGK; launch_longk(all.g[i], lc, stream); }
         else grp.g[grp.n++] = all.g[i];
     }
     if (grp.n == 0) return;
@@ -116,6 +120,7 @@ void launch_direct_group(const GemmGroup& all, dim3 grid, hipStream_t stream) {
     // footprint (more workgroups per CU) then beats having all of K in flight at once
     const size_t wgs = (size_t)grid.x * grid.y * grid.z;
     const int nb = (wgs > 1024 || direct_nbmax(kmax) == 4) ? 4 : DMAXB;
+    g_group_routes |= 1 << (fast ? MPO_GEMM_ROUTE_FAST : nb == 4 ? MPO_GEMM_ROUTE_GENERAL_NB4 : MPO_GEMM_ROUTE_GENERAL_NB8);
     if (fast) { mpo_fast_group(grp, classes >> 3 ? 3 : classes >> 2 ? 2 : 1, nb, grid, stream); return; }
     if (nb == 4) mpo_direct_group_nb4(grp, grid, stream);
     else mpo_direct_group_nb8(grp, grid, stream);
@@ -146,6 +151,13 @@ void colsum_kernel(const float* __restrict__ x, float* __restrict__ out, int M, 
 int mpo_gemm_fast_path(int enabled) {
     const int was = g_fast_path ? 1 : 0;
     g_fast_path = enabled != 0;
+    return was;
+}
+
+int mpo_gemm_route_last() { return g_last_route; }
+int mpo_gemm_route_group_take() {
+    const int was = g_group_routes;
+    g_group_routes = 0;
     return was;
 }
 

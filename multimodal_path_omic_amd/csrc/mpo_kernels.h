@@ -181,6 +181,10 @@ int mpo_launch_k2_patch_grad(const int* cu, const void* dk_bf16, const float* w_
                              const void* hbag_bf16, void* out_bf16, float gate, float* part_colsum, int n_q, int embed,
                              const BagPlan& plan, hipStream_t stream);
 int mpo_gemm_fast_path(int enabled);   // gemm_f32.hip: returns the previous setting
+// which body the launchers of gemm_f32.hip picked, as MPO_GEMM_ROUTE_* of include/mpo_hip.h (host-side bookkeeping behind
+// mpo_gemm_last_route() and mpo_gemm_last_group_routes())
+int mpo_gemm_route_last();
+int mpo_gemm_route_group_take();       // the mask since the previous call, which it clears
 // dW_H = g^T X of the patch layer, hand-written (patch_wgrad.hip): part = mpo_patch_wgrad_partial_floats() floats
 size_t mpo_patch_wgrad_partial_floats(int embed, int patch_dim);
 int mpo_launch_patch_wgrad(const void* g_bf16, const void* x_bf16, int64_t total_rows, int embed, int patch_dim, float* part,

@@ -72,11 +72,11 @@ def epoch_tensor(dev):
 
 
 # ------------------------------------------------------------------------------------------- encoder
-def _encoder_setup(dev, nb, ns, T, d, seed):
+def _encoder_setup(dev, nb, ns, T, d, seed, ff=FF):
     sds, encs = [], []
     for br in range(nb):
-        sd = syn.fill_state_dict(C.encoder_shapes("enc", d=d, ff=FF), seed + br)
-        enc = make_set_transformer(d, P, nhead=HEADS, dim_feedforward=FF, num_layers=LAYERS)
+        sd = syn.fill_state_dict(C.encoder_shapes("enc", d=d, ff=ff), seed + br)
+        enc = make_set_transformer(d, P, nhead=HEADS, dim_feedforward=ff, num_layers=LAYERS)
         enc.load_state_dict({k[len("enc."):]: v for k, v in sd.items()}, strict=True)
         sds.append(sd)
         encs.append(enc.to(dev).train())
@@ -110,16 +110,16 @@ def _encoder_oracle(sds, x, probe, keeps):
     return torch.stack(ys), torch.stack(dxs), gs
 
 
-def _encoder_check(dev, nb, ns, T, d, seed, epoch=0):
-    sds, encs, x, probe = _encoder_setup(dev, nb, ns, T, d, seed)
+def _encoder_check(dev, nb, ns, T, d, seed, epoch=0, ff=FF):
+    sds, encs, x, probe = _encoder_setup(dev, nb, ns, T, d, seed, ff)
     y, dx, grads = _encoder_gpu(dev, sds, encs, x, probe)
-    keeps = R.encoder_keeps(SEED, OFF, nb, ns, T, d, FF, HEADS, LAYERS, P, epoch)
+    keeps = R.encoder_keeps(SEED, OFF, nb, ns, T, d, ff, HEADS, LAYERS, P, epoch)
     yo, dxo, go = _encoder_oracle(sds, x, probe, keeps)
     e_y, e_dx = relerr(y, yo), grad_errs([dx], [dxo])[0]
     e_g = grad_errs(grads, go)
     names = [f"br{br}.{k}" for br, sd in enumerate(sds) for k in sd]
     worst = int(np.argmax(e_g))
-    print(f"encoder nb={nb} ns={ns} T={T} d={d} epoch={epoch}: y {e_y:.1e} dx {e_dx:.1e} "
+    print(f"encoder nb={nb} ns={ns} T={T} d={d} ff={ff} epoch={epoch}: y {e_y:.1e} dx {e_dx:.1e} "
           f"grads max {e_g[worst]:.1e} ({names[worst]})")
     assert e_y < FWD_TOL, e_y
     assert e_dx < GRAD_TOL, e_dx
@@ -150,6 +150,16 @@ def test_encoder_bag_rows_training_equals_fp64_oracle(dev, T):
         _encoder_check(dev, 2 if T < 2050 else 1, 1, T, 256, 300 + T)
     finally:
         L.lib().mpo_set_bag_self_attention_bf16x3(was)
+
+
+@pytest.mark.parametrize("ff", [100, 102])
+def test_encoder_irregular_ff_training_equals_fp64_oracle(dev, ff):
+    """FFN widths off the 4- and 16-grid at d = 128, 5 slides x 6 tokens (30 rows: the general GEMM body throughout).
+    ff = 100: K % 16 != 0 in linear2 and its gradients, leading dimension still % 4 == 0 (whole-quad draws).  ff = 102:
+    lda % 4 != 0, so linear1's epilogue dropout and the regenerated gate of linear2's backward pair draw per element,
+    and no operand row of width ff is 16-byte aligned.  mpo_encoder_forward has no check on ff: both widths run, at the
+    bars of the ff = 512 cases."""
+    _encoder_check(dev, 2, 5, C.N_OMIC, 128, 1200 + ff, ff=ff)
 
 
 def test_encoder_refuses_narrow_heads_in_training(dev):
