@@ -94,7 +94,8 @@ int mpo_coattn_mcat_forward(const void* bag, int bag_dtype, const int32_t* cu_ro
  * scores / online softmax / context, and mpo_coattn_mcat_backward takes `saved` and h_bag exactly as after
  * mpo_coattn_mcat_forward.
  *   patches [total_rows, patch_dim] bf16;  patch_weight [embed, patch_dim] fp32 (rounded to bf16 operands inside),
- *   patch_bias [embed] fp32.  Built for patch_dim 1024, embed 256 ('medium'), n_q <= 8.
+ *   patch_bias [embed] fp32.  Built for patch_dim 1024, embed 256 ('medium'), n_q <= 8: the one-call form stays at the
+ *   reference's geometry; other feature widths go through mpo_patch_fc_forward + mpo_coattn_mcat_forward.
  * Dropout: counter hash of (seed, offset [+ *rng_epoch << 40]), one draw per 16 elements, 8 random bits each: the realised drop
  * probability is round(256 p) / 256 (exact for the reference's 0.25) and the keep scale follows it; reserve
  * total_rows * embed / 16 + 1 counters. */
@@ -111,8 +112,10 @@ int mpo_patch_coattn_mcat_forward(const void* patches, const int32_t* cu_rows, i
 /* The patch layer alone: h_bag [total_rows, embed] bf16 = dropout(relu(patches W^T + b)) (models/mcat/mcat.py:24-29,87), one
  * pass of the patch-layer kernel (NaCAGaT needs H_bag for more than one product; MCAT outside the 1024 -> 256
  * configuration).  Same dropout stream and realised rate as mpo_patch_coattn_mcat_forward.
- * patch_dim 1024; embed 128 / 256 / 512 = model_size small / medium / big (models/mcat/mcat.py:16-21) on the one kernel:
- * 128 as a 256-column block whose upper half is not stored, 512 as one pass per 256-column half.  Other widths: error. */
+ * patch_dim 512 / 1024 / 2048 (the reference's truncated ResNet-50 gives 1024; the kernel's K schedule is built per width);
+ * embed 128 / 256 / 512 = model_size small / medium / big (models/mcat/mcat.py:16-21) on the one kernel:
+ * 128 as a 256-column block whose upper half is not stored, 512 as one pass per 256-column half.  Other widths: error
+ * (768, 1280 and 1536 among them: the weight gradient's column-block tiling has no form for them). */
 size_t mpo_patch_fc_workspace_bytes(int embed, int patch_dim);
 int mpo_patch_fc_forward(const void* patches, const int32_t* cu_rows, int n_slides, int total_rows, int max_rows, int patch_dim,
                          const float* patch_weight, const float* patch_bias, int embed, float drop_p, uint64_t seed,
@@ -138,8 +141,8 @@ int mpo_patch_fc_f32_backward(const float* d_h_bag, const float* h_bag /* nullab
                               size_t workspace_bytes, mpo_stream_t stream);
 
 /* The fused bag pass alone (measurement): w_packed = embed * patch_dim bf16 values from mpo_pack_patch_weight (the weight
- * in the fragment order of the kernel's GEMM waves; one 512-KiB block per 256 rows of W_H, embed 128: one block whose upper
- * half is zero), qk2 [n_slides*n_q, embed].  The bag pass is the embed-256 form. */
+ * in the fragment order of the kernel's GEMM waves; one block of 256 x patch_dim bf16 per 256 rows of W_H, embed 128: one
+ * block whose upper half is zero; patch_dim 512 / 1024 / 2048), qk2 [n_slides*n_q, embed].  The bag pass is the 1024 -> 256 form. */
 int mpo_patch_coattn_fwd_bagpass(const void* patches, const void* w_packed, const float* bias, const int32_t* cu_rows, int n_slides,
                                  const float* qk2, void* h_bag, float* part_ml, float* part_ctx, int n_q, int max_rows,
                                  float drop_p, uint64_t seed, uint64_t offset, const mpo_bag_plan* plan /* nullable */,

@@ -187,7 +187,7 @@ static int k1_forward(const void* bag, int bag_f32, const PatchStep* patch, cons
     // qk2 = log2(e) * qs W_k     (fold of the key projection into the query; key bias cancels in softmax)
     RC(mpo_linear_bwd_input(S.qs, in_w + (size_t)E * E, S.qk2, R, E, E, kLog2e, 0, stream));
     if (patch) {
-        RC(mpo_launch_patch_fc_fwd(patch->patches, ws.w_bf16, patch->bias, cu_rows, patch->h_bag, E, patch->drop_p, patch->seed,
+        RC(mpo_launch_patch_fc_fwd(patch->patches, ws.w_bf16, patch->bias, cu_rows, patch->h_bag, E, patch->patch_dim, patch->drop_p, patch->seed,
                                    patch->offset, reinterpret_cast<const unsigned long long*>(patch->rng_epoch), plan, stream));
         bag = patch->h_bag;
     }
@@ -246,15 +246,16 @@ int mpo_patch_coattn_mcat_forward(const void* patches, const int32_t* cu_rows, i
 
 // The patch layer alone, H_bag = dropout(relu(X W_H^T + b_H)) (models/mcat/mcat.py:24-29,87), as ONE pass of the same
 // kernel: for the models whose co-attention needs more than H_bag (NaCAGaT's key projection) and for MCAT outside the
-// 1024 -> 256 configuration.  Workspace: the packed bf16 copy of the weight.
+// 1024 -> 256 configuration.  patch_dim 512, 1024 or 2048 (the kernel's schedule is built per width).  Workspace: the packed
+// bf16 copy of the weight.
 size_t mpo_patch_fc_workspace_bytes(int embed, int patch_dim) { return one_block_workspace_bytes(patch_weight_floats(embed, patch_dim)); }
 int mpo_patch_fc_forward(const void* patches, const int32_t* cu_rows, int n_slides, int total_rows, int max_rows, int patch_dim,
                          const float* patch_weight, const float* patch_bias, int embed, float drop_p, uint64_t seed,
                          uint64_t offset, const uint64_t* rng_epoch, void* h_bag, const mpo_bag_plan* plan_, void* workspace,
                          size_t workspace_bytes, mpo_stream_t stream) {
     RC(check_common(MPO_BF16, n_slides, total_rows, max_rows, 1, embed));
-    MPO_CHECK((embed == 128 || embed == 256 || embed == 512) && patch_dim == 1024,
-              "patch layer kernel is built for 1024 -> 128, 256 or 512 (got %d -> %d)", patch_dim, embed);
+    MPO_CHECK((embed == 128 || embed == 256 || embed == 512) && (patch_dim == 512 || patch_dim == 1024 || patch_dim == 2048),
+              "patch layer kernel is built for patch_dim in {512, 1024, 2048} -> embed in {128, 256, 512} (got %d -> %d)", patch_dim, embed);
     MPO_CHECK((int64_t)max_rows * embed * 2 < ((int64_t)1 << 31), "patch layer: a slide's H_bag of 2 GiB or more (%d rows)", max_rows);
     const BagPlan plan = make_plan(plan_, n_slides, max_rows);
     RC(check_plan(plan, n_slides));
@@ -262,7 +263,7 @@ int mpo_patch_fc_forward(const void* patches, const int32_t* cu_rows, int n_slid
     float* w_bf16 = ws.floats(patch_weight_floats(embed, patch_dim));
     MPO_CHECK(ws.ok(), "patch layer: workspace too small (%zu bytes)", workspace_bytes);
     RC(mpo_launch_pack_patch_weight(patch_weight, w_bf16, embed, patch_dim, stream));
-    return mpo_launch_patch_fc_fwd(patches, w_bf16, patch_bias, cu_rows, h_bag, embed, drop_p, seed, offset,
+    return mpo_launch_patch_fc_fwd(patches, w_bf16, patch_bias, cu_rows, h_bag, embed, patch_dim, drop_p, seed, offset,
                                    reinterpret_cast<const unsigned long long*>(rng_epoch), plan, stream);
 }
 
@@ -299,7 +300,7 @@ int mpo_patch_coattn_fwd_bagpass(const void* patches, const void* w_packed, cons
                                  float drop_p, uint64_t seed, uint64_t offset, const mpo_bag_plan* plan_, mpo_stream_t stream) {
     const BagPlan plan = make_plan(plan_, n_slides, max_rows);
     RC(check_plan(plan, n_slides));
-    RC(mpo_launch_patch_fc_fwd(patches, w_packed, bias, cu_rows, h_bag, 256, drop_p, seed, offset, nullptr, plan, stream));
+    RC(mpo_launch_patch_fc_fwd(patches, w_packed, bias, cu_rows, h_bag, 256, 1024, drop_p, seed, offset, nullptr, plan, stream));
     if (qk2 == nullptr) return 0;
     return mpo_launch_coattn_fwd_partial(h_bag, 0, cu_rows, n_slides, 256, qk2, part_ml, part_ctx, nullptr, n_q, plan, stream);
 }

@@ -138,10 +138,10 @@ inline int mpo_gemm_together(hipStream_t s, const GemmArgs& a, const GemmArgs& b
 // ---- K1/K2 long-bag cross-attention (coattn_fwd.hip / coattn_bwd.hip)
 struct BagPlan;
 extern "C" int mpo_coattn_splits(int n_slides, int max_rows);
-// rows H2 / f1: the patch layer of a bf16 window, 1024 -> 256, one pass over the raw patch matrix (patch_fc_fwd.hip)
+// rows H2 / f1: the patch layer of a bf16 window, {512, 1024, 2048} -> {128, 256, 512}, one pass over the raw patch matrix (patch_fc_fwd.hip)
 int mpo_launch_pack_patch_weight(const float* w, void* out, int embed, int patch_dim, hipStream_t stream);
-int mpo_launch_patch_fc_fwd(const void* x, const void* w_packed, const float* bias, const int* cu, void* h_out, int embed, float drop_p,
-                            unsigned long long seed, unsigned long long offset, const unsigned long long* epoch,
+int mpo_launch_patch_fc_fwd(const void* x, const void* w_packed, const float* bias, const int* cu, void* h_out, int embed, int patch_dim,
+                            float drop_p, unsigned long long seed, unsigned long long offset, const unsigned long long* epoch,
                             const BagPlan& plan, hipStream_t stream);
 int mpo_launch_coattn_fwd_partial(const void* bag, int bag_f32, const int* cu, int n_slides, int embed,
                                   const float* qk2, float* part_ml, float* part_ctx, float* s_out,

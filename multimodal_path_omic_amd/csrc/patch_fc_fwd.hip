@@ -1,6 +1,7 @@
 // The patch layer of a bf16-stored window, H_bag = Dropout(ReLU(X W_H^T + b_H))   (models/mcat/mcat.py:24-29,87;
 // models/nacagat/nacagat.py the same layer), X [rows, 1024] bf16, W_H [256, 1024], H_bag [rows, 256] bf16: ONE pass over the
-// raw patch matrix, H_bag written once.  Row H2 / f1 of SURVEY.md section 8.
+// raw patch matrix, H_bag written once.  Row H2 / f1 of SURVEY.md section 8.  The text below speaks of the reference's
+// width, 1024; the kernel is also built for patch features 512 and 2048 wide (Sched<PK>: the same schedule, NK = PK / 32).
 //
 // r02-r03 ran this layer fused with K1's forward (8 GEMM waves on 128-row blocks + 4 loader / co-attention waves: 335-349 us
 // per 32 x 15 000-row window); r04 rebuilt that as one output-stationary 256 x 256 block per workgroup with the co-attention
@@ -45,13 +46,9 @@
 namespace {
 
 constexpr int PE = 256;                         // embed_dim
-constexpr int PK = 1024;                        // patch feature width (models/mcat/mcat.py:25)
 constexpr int CH = 128;                         // patch rows per chunk (one stream's accumulator block)
 constexpr int BK = 32;                          // k per stage (one MFMA k-step)
-constexpr int NK = PK / BK;                     // 32 main stages per chunk
 constexpr int EPI = 8;                          // epilogue stages per chunk: one 16-row patch tile each
-constexpr int PERIOD = NK + EPI;                // 40
-constexpr int SKEW = 20;                        // the second stream's delay: 2 SKEW = EPI (mod 32), see the rotation rule above
 constexpr int X_IMG = CH * 2 * BK * 2;          // 16 KiB: [128 rows][128 B] = TWO k-steps (whole 128-byte lines of X)
 constexpr int W_IMG = PE * BK * 2;              // 16 KiB: [cq 4][dt 4][lane 64][16 B]
 #ifdef MPO_PF_W4
@@ -64,25 +61,45 @@ constexpr int OFF_X = 0;                        // stream s: OFF_X + s * XSLOTS 
 constexpr int OFF_W = 2 * XSLOTS * X_IMG;       // 96 KiB
 constexpr int LDS_TOTAL = OFF_W + WSLOTS * W_IMG;   // 144 KiB
 constexpr int NTHREADS = 512;
-static_assert((2 * SKEW) % NK == EPI % NK && SKEW >= EPI && SKEW % 2 == 0 && EPI % 2 == 0, "rotation rule / disjoint epilogues / even rotations");
 static_assert(LDS_TOTAL <= 160 * 1024, "LDS budget");
 
-// ---- the static schedule of a stream (position p of its 40-stage period; all counts are vector-memory instructions of ONE wave)
+// ---- the static schedule of a stream for patch feature width PK (models/mcat/mcat.py:25 has 1024; 512 and 2048 are the other
+// feature extractors in use): NK = PK / 32 main stages per chunk, a period of NK + 8 stages, the second stream HALF A PERIOD
+// behind the first.  Half a period is the one skew that satisfies the rotation rule at every width -- 2 SKEW = PERIOD = EPI
+// (mod NK) -- and it puts the lagging stream's epilogue at positions (NK - 8) / 2 .. (NK + 8) / 2 of the leading one's main loop.
+//      PK    NK  PERIOD  SKEW   chunk rotation g(c)                    g wraps after
+//      512   16    24     12    8 (c >> 1) + 12 (c & 1) mod 16          4 chunks =  512 rows
+//     1024   32    40     20    8 (c >> 1) + 20 (c & 1) mod 32          8 chunks = 1024 rows
+//     2048   64    72     36    8 (c >> 1) + 36 (c & 1) mod 64         16 chunks = 2048 rows
+// Everything below is in positions relative to the chunk's two ends (0, 1, 2 | pairs | NK - 5 .. NK - 1 | the epilogue), so the
+// request windows and the counts of younger operations keep their shape at every width; all counts are vector-memory
+// instructions of ONE wave.
 // Order inside a stage, right behind its barrier: the W_H request (2: stage + 2), the X request (4: a 16-KiB pair of k-steps, at
-// even positions, for the pair two pairs ahead -- positions 28..34 have none: the chunk's 16 pairs are out, the next chunk's
-// first two pairs go out at 36 and 38); then the stage's work, which in the epilogue ends with two H_bag stores.  (Requests
+// even positions, for the pair two pairs ahead -- positions NK - 4 .. NK + 2 have none (at 1024: 28..34): the chunk's NK / 2
+// pairs are out, the next chunk's first two pairs go out at PERIOD - 4 and PERIOD - 2); then the stage's work, which in the
+// epilogue ends with two H_bag stores.  (Requests
 // behind the work were measured: the memory pipeline then idles for the length of every stage's work -- DMA alone 223 us,
 // matrix work alone 138 us, together 329 us.)
-constexpr int pmod(int p) { return ((p % PERIOD) + PERIOD) % PERIOD; }
-constexpr int x_ops(int p) { return (pmod(p) % 2 == 0 && (pmod(p) <= NK - 6 || pmod(p) >= PERIOD - 4)) ? 4 : 0; }
-constexpr int s_ops(int p) { return pmod(p) >= NK ? 2 : 0; }
+template <int PK>
+struct Sched {
+    static constexpr int NK = PK / BK;          // main stages per chunk
+    static constexpr int PERIOD = NK + EPI;
+    static constexpr int SKEW = PERIOD / 2;     // the second stream's delay
+    static_assert(PK % BK == 0 && (NK & (NK - 1)) == 0 && NK >= 16, "k-steps are taken mod NK with a mask; positions 0 .. 2, one pair and NK - 5 .. NK - 1 are distinct");
+    static_assert((2 * SKEW) % NK == EPI % NK && SKEW >= EPI && SKEW % 2 == 0 && EPI % 2 == 0, "rotation rule / disjoint epilogues / even rotations");
+    static constexpr int pmod(int p) { return ((p % PERIOD) + PERIOD) % PERIOD; }
+    static constexpr int x_ops(int p) { return (pmod(p) % 2 == 0 && (pmod(p) <= NK - 6 || pmod(p) >= PERIOD - 4)) ? 4 : 0; }
+    static constexpr int s_ops(int p) { return pmod(p) >= NK ? 2 : 0; }
 // instructions younger than this wave's W_H pieces of the stage it is about to read (requested first thing two stages before):
 // the rest of that stage, and everything of the stage in between.  (The X pair of the moment was requested earlier still.)
-constexpr int n_younger(int p) {
-    int n = 0;
-    for (int d = 1; d <= WAHEAD; ++d) n += x_ops(p - d) + s_ops(p - d) + (d < WAHEAD ? 2 : 0);
-    return n;
-}
+    static constexpr int n_younger(int p) {
+        int n = 0;
+        for (int d = 1; d <= WAHEAD; ++d) n += x_ops(p - d) + s_ops(p - d) + (d < WAHEAD ? 2 : 0);
+        return n;
+    }
+    // K rotation of chunk c of a slide (see the header)
+    static __device__ __forceinline__ int chunk_rotation(int c) { return (8 * (c >> 1) + SKEW * (c & 1)) & (NK - 1); }
+};
 // the same where there is no epilogue behind the stream yet (its first chunk) and in stages without work of its own: only what
 // is certain to be younger -- the W_H requests of the stages in between (waiting for more than necessary is safe, for less is not)
 constexpr int N_W_ONLY = 2 * (WAHEAD - 1);
@@ -121,9 +138,6 @@ __device__ __forceinline__ uint4 hash16(uint32_t key, uint32_t inc, uint32_t ctr
     }
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
-// K rotation of chunk c of a slide (see the header)
-__device__ __forceinline__ int chunk_rotation(int c) { return (8 * (c >> 1) + SKEW * (c & 1)) & (NK - 1); }
-
 #ifdef MPO_PF_STAMPS
 __device__ float mpo_pf_stamps[1024 * 16];     // per workgroup: wave 0 -> [0..7], wave 4 -> [8..15]
 #endif
@@ -131,9 +145,10 @@ __device__ float mpo_pf_stamps[1024 * 16];     // per workgroup: wave 0 -> [0..7
 // WIDTH = embed_dim of the model (models/mcat/mcat.py:16-21: 128 'small', 256, 512 'big'), the row pitch of H_bag.  The pass
 // always works on a 256-column block of W_H: WIDTH 128 = the block's upper half is zero rows of the packed weight and the
 // waves that own it (cq 2, 3) aim their stores past the buffer's range; WIDTH 512 = two passes, columns col_off = 0 and 256.
-template <int WIDTH>
+// PK = the patch feature width (512, 1024, 2048): the schedule Sched<PK>; nothing else of the kernel depends on it.
+template <int WIDTH, int PK>
 __global__ __launch_bounds__(NTHREADS, 2)
-void patch_fc_fwd_kernel(const __bf16* __restrict__ x,            // [total_rows][1024] patch features
+void patch_fc_fwd_kernel(const __bf16* __restrict__ x,            // [total_rows][PK] patch features
                          const __bf16* __restrict__ wb,           // the pass's 256 rows of W_H as bf16, packed in stage order (pack_patch_weight_kernel)
                          const float* __restrict__ bias,          // [WIDTH]
                          const int* __restrict__ cu,
@@ -141,6 +156,8 @@ void patch_fc_fwd_kernel(const __bf16* __restrict__ x,            // [total_rows
                          int col_off,                             // first embed column of this pass
                          float drop_p, unsigned long long seed, unsigned long long offset_,
                          const unsigned long long* __restrict__ epoch, BagPlan plan) {
+    using S = Sched<PK>;
+    constexpr int NK = S::NK, PERIOD = S::PERIOD, SKEW = S::SKEW;
     constexpr int NCQ = WIDTH < PE ? WIDTH / 64 : 4;              // waves of a stream whose 64 columns exist
     __shared__ __attribute__((aligned(1024))) char lds[LDS_TOTAL];
     const int tid = threadIdx.x;
@@ -171,7 +188,7 @@ void patch_fc_fwd_kernel(const __bf16* __restrict__ x,            // [total_rows
     const int n_ch = (r1 - r0 + CH - 1) / CH;                     // chunks r0 / CH .. : the streams take alternate ones
     const int st = wave >> 2, cq = wave & 3;                      // stream; embed columns 64 cq .. + 63
     const int n_mine = (n_ch - st + 1) >> 1;                      // chunks of this wave's stream
-    const int k0 = chunk_rotation(r0 / CH);
+    const int k0 = S::chunk_rotation(r0 / CH);
     const int n_lead = (n_ch + 1) >> 1, n_lag = n_ch >> 1;
     const int G = max(n_lead * PERIOD, n_lag > 0 ? n_lag * PERIOD + SKEW : 0);      // global stages
 
@@ -361,7 +378,7 @@ void patch_fc_fwd_kernel(const __bf16* __restrict__ x,            // [total_rows
     using std::integral_constant;
     using T = integral_constant<bool, true>;
     using F = integral_constant<bool, false>;
-#define MPO_N(p) integral_constant<int, n_younger(p)>{}
+#define MPO_N(p) integral_constant<int, S::n_younger(p)>{}
     using NW = integral_constant<int, N_W_ONLY>;
     using NF1 = integral_constant<int, N_FIRST_1>;
     using NF2 = integral_constant<int, N_FIRST_2>;
@@ -381,9 +398,9 @@ void patch_fc_fwd_kernel(const __bf16* __restrict__ x,            // [total_rows
         req_x(cj, 2);
         stage(T{}, F{}, F{}, xr, 0, wr, pw, qw, fx);
         adv();
-        static_assert(n_younger(3) == n_younger(5) && n_younger(3) == n_younger(25) && n_younger(4) == n_younger(6) &&
-                      n_younger(4) == n_younger(26), "main loop counts");
-        static_assert(WAHEAD == 2 ? n_younger(2) == N_FIRST_2 : n_younger(2) == N_FIRST_2 + 2, "position 2: the epilogue's last stores are in the window at three ahead");
+        static_assert(S::n_younger(3) == S::n_younger(5) && S::n_younger(3) == S::n_younger(NK - 7) && S::n_younger(4) == S::n_younger(6) &&
+                      S::n_younger(4) == S::n_younger(NK - 6), "main loop counts");
+        static_assert(WAHEAD == 2 ? S::n_younger(2) == N_FIRST_2 : S::n_younger(2) == N_FIRST_2 + 2, "position 2: the epilogue's last stores are in the window at three ahead");
         if (cj == 0) pre(NF1{}); else pre(MPO_N(1));              // (first chunk: no epilogue stores before it)
         MPO_KIND(0)
         req_w();
@@ -395,7 +412,7 @@ void patch_fc_fwd_kernel(const __bf16* __restrict__ x,            // [total_rows
         req_x(cj, 3);
         stage(F{}, F{}, F{}, xr, 0, wr, pw, qw, fx);
         adv();
-        for (int q = 1; q < 13; ++q) {                            // positions 3 .. 26 in pairs (odd, even); even positions request pair q + 3
+        for (int q = 1; q < NK / 2 - 3; ++q) {                    // positions 3 .. NK - 6 in pairs (odd, even); even positions request pair q + 3
             pre(MPO_N(3));
             req_w();
             stage(F{}, F{}, F{}, xr, 1, wr, qw, pw, fx);
@@ -409,15 +426,15 @@ void patch_fc_fwd_kernel(const __bf16* __restrict__ x,            // [total_rows
         }
 #define MPO_MAIN_STAGE(P, LOADSET, USESET) pre(MPO_N(P)); req_w(); stage(F{}, F{}, F{}, xr, (P) & 1, wr, LOADSET, USESET, fx); \
         if ((P) & 1) xr = wrap_inc(xr, XSLOTS); adv();
-        MPO_MAIN_STAGE(27, qw, pw)
-        MPO_MAIN_STAGE(28, pw, qw)                                // (the chunk's last pair, 15, was requested at 26)
-        MPO_MAIN_STAGE(29, qw, pw)
-        MPO_MAIN_STAGE(30, pw, qw)
-        MPO_MAIN_STAGE(31, qw, pw)
+        MPO_MAIN_STAGE(NK - 5, qw, pw)
+        MPO_MAIN_STAGE(NK - 4, pw, qw)                            // (the chunk's last pair, NK / 2 - 1, was requested at NK - 6)
+        MPO_MAIN_STAGE(NK - 3, qw, pw)
+        MPO_MAIN_STAGE(NK - 2, pw, qw)
+        MPO_MAIN_STAGE(NK - 1, qw, pw)
 #undef MPO_MAIN_STAGE
-        // epilogue: position 32 finishes the MFMAs (stage 31 was read into the second W_H set), then one patch tile per stage;
-        // positions 36 and 38 request the next chunk's first two pairs
-        pre(MPO_N(32));
+        // epilogue: position NK finishes the MFMAs (stage NK - 1 was read into the second W_H set), then one patch tile per stage;
+        // positions NK + 4 and NK + 6 request the next chunk's first two pairs
+        pre(MPO_N(NK));
         MPO_KIND(2)
         req_w();
         stage(F{}, T{}, F{}, 0, 0, 0, pw, qw, fx);
@@ -432,13 +449,13 @@ void patch_fc_fwd_kernel(const __bf16* __restrict__ x,            // [total_rows
         MPO_EPI_STAGE(7, )
 #undef MPO_EPI_STAGE
     }
-    if (n_mine > 0 && gs < G) {                                   // the other stream is still at work: stage "40" of the last chunk, ..
+    if (n_mine > 0 && gs < G) {                                   // the other stream is still at work: stage "PERIOD" of the last chunk, ..
         pre(MPO_N(0));
         MPO_KIND(3)
         req_w();
         adv();
         if (gs < G) {
-            pre(integral_constant<int, 4>{});                     // (.. "41": at least the last epilogue stage's stores and the W_H request of "40")
+            pre(integral_constant<int, 4>{});                     // (.. "PERIOD + 1": at least the last epilogue stage's stores and the W_H request of "40")
             req_w();
             adv();
         }
@@ -456,13 +473,14 @@ void patch_fc_fwd_kernel(const __bf16* __restrict__ x,            // [total_rows
 #endif
 }
 
-// W_H [256][1024] fp32 -> bf16 in the stage order of the kernel above: 16-byte fragment t = ((s * 4 + cq) * 4 + dt) * 64 + lane,
+// W_H [256][PK] fp32 -> bf16 in the stage order of the kernel above: 16-byte fragment t = ((s * 4 + cq) * 4 + dt) * 64 + lane,
 // lane (i = lane & 15, g = lane >> 4), holds W_H[64 cq + 32 (dt >> 1) + 8 (i >> 2) + 4 (dt & 1) + (i & 3)][32 s + 8 g .. + 7]: the
 // A operand (row i of embed tile (cq, dt), k-group g) of k-step s, with the tile's rows permuted so that the MFMA result
 // leaves lane group g with embed columns 64 cq + 32 (dt >> 1) + 8 g + 4 (dt & 1) + r.
 // Rows >= rows_valid (the 'small' model: 128 rows of W_H) are packed as zeros.
+template <int PK>
 __global__ void pack_patch_weight_kernel(const float* __restrict__ w, bf16x8* __restrict__ out, int rows_valid) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;          // one 16-byte fragment per thread: 256 * 1024 / 8 of them
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;          // one 16-byte fragment per thread: 256 * PK / 8 of them
     if (t >= PE * PK / 8) return;
     const int lane = t & 63, blk = t >> 6;
     const int dt = blk & 3, cq = (blk >> 2) & 3, s = blk >> 4;
@@ -490,39 +508,59 @@ extern "C" int mpo_debug_patch_fc_stamps(float* host) {
 }
 #endif
 
-// out: one 512-KiB packed block per 256 rows of W_H (embed 128: one block, upper half zero; 512: two blocks)
-int mpo_launch_pack_patch_weight(const float* w, void* out, int embed, int patch_dim, hipStream_t stream) {
-    MPO_CHECK((embed == 128 || embed == 256 || embed == 512) && patch_dim == PK,
-              "patch weight packing is built for {128, 256, 512} x %d (got %d x %d)", PK, embed, patch_dim);
+namespace {
+
+template <int PK>
+int launch_pack(const float* w, void* out, int embed, hipStream_t stream) {
     for (int c0 = 0; c0 < embed; c0 += PE) {
-        pack_patch_weight_kernel<<<PE * PK / 8 / 256, 256, 0, stream>>>(w + (size_t)c0 * PK, reinterpret_cast<bf16x8*>(out) + (size_t)c0 * PK / 8,
-                                                                      min(PE, embed - c0));
+        pack_patch_weight_kernel<PK><<<PE * PK / 8 / 256, 256, 0, stream>>>(w + (size_t)c0 * PK, reinterpret_cast<bf16x8*>(out) + (size_t)c0 * PK / 8,
+                                                                          min(PE, embed - c0));
         MPO_LAUNCH_CHECK();
     }
     return 0;
 }
 
-int mpo_launch_patch_fc_fwd(const void* x, const void* w_packed, const float* bias, const int* cu, void* h_out, int embed, float drop_p,
-                            unsigned long long seed, unsigned long long offset, const unsigned long long* epoch,
+template <int PK>
+int launch_fwd(const __bf16* xb, const __bf16* wp, const float* bias, const int* cu, __bf16* hb, int embed, float drop_p,
+               unsigned long long seed, unsigned long long offset, const unsigned long long* epoch, const BagPlan& plan,
+               hipStream_t stream) {
+    if (embed == 128) {
+        patch_fc_fwd_kernel<128, PK><<<plan_grid(plan), NTHREADS, 0, stream>>>(xb, wp, bias, cu, hb, 0, drop_p, seed, offset, epoch, plan);
+    } else if (embed == 256) {
+        patch_fc_fwd_kernel<256, PK><<<plan_grid(plan), NTHREADS, 0, stream>>>(xb, wp, bias, cu, hb, 0, drop_p, seed, offset, epoch, plan);
+    } else {
+        for (int c0 = 0; c0 < 512; c0 += PE) {                    // (the patch matrix is read once per column half)
+            patch_fc_fwd_kernel<512, PK><<<plan_grid(plan), NTHREADS, 0, stream>>>(xb, wp + (size_t)c0 * PK, bias, cu, hb, c0, drop_p, seed,
+                                                                                  offset, epoch, plan);
+            MPO_LAUNCH_CHECK();
+        }
+    }
+    MPO_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
+// out: one packed block of 256 x patch_dim bf16 per 256 rows of W_H (embed 128: one block, upper half zero; 512: two blocks)
+int mpo_launch_pack_patch_weight(const float* w, void* out, int embed, int patch_dim, hipStream_t stream) {
+    MPO_CHECK((embed == 128 || embed == 256 || embed == 512) && (patch_dim == 512 || patch_dim == 1024 || patch_dim == 2048),
+              "patch weight packing is built for {128, 256, 512} x {512, 1024, 2048} (got %d x %d)", embed, patch_dim);
+    return patch_dim == 512 ? launch_pack<512>(w, out, embed, stream)
+         : patch_dim == 1024 ? launch_pack<1024>(w, out, embed, stream) : launch_pack<2048>(w, out, embed, stream);
+}
+
+int mpo_launch_patch_fc_fwd(const void* x, const void* w_packed, const float* bias, const int* cu, void* h_out, int embed, int patch_dim,
+                            float drop_p, unsigned long long seed, unsigned long long offset, const unsigned long long* epoch,
                             const BagPlan& plan, hipStream_t stream) {
     MPO_CHECK(embed == 128 || embed == 256 || embed == 512, "patch layer: embed_dim %d not in {128, 256, 512}", embed);
+    MPO_CHECK(patch_dim == 512 || patch_dim == 1024 || patch_dim == 2048, "patch layer: patch_dim %d not in {512, 1024, 2048}", patch_dim);
     MPO_CHECK(drop_p >= 0.f && drop_p < 1.f, "patch-layer dropout p must be in [0,1) (got %f)", (double)drop_p);
     MPO_CHECK(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w_packed) | reinterpret_cast<uintptr_t>(h_out)) & 15) == 0,
               "patch layer: operands must be 16-byte aligned");
     const __bf16* xb = reinterpret_cast<const __bf16*>(x);
     const __bf16* wp = reinterpret_cast<const __bf16*>(w_packed);
     __bf16* hb = reinterpret_cast<__bf16*>(h_out);
-    if (embed == 128) {
-        patch_fc_fwd_kernel<128><<<plan_grid(plan), NTHREADS, 0, stream>>>(xb, wp, bias, cu, hb, 0, drop_p, seed, offset, epoch, plan);
-    } else if (embed == 256) {
-        patch_fc_fwd_kernel<256><<<plan_grid(plan), NTHREADS, 0, stream>>>(xb, wp, bias, cu, hb, 0, drop_p, seed, offset, epoch, plan);
-    } else {
-        for (int c0 = 0; c0 < 512; c0 += PE) {                    // (the patch matrix is read once per column half)
-            patch_fc_fwd_kernel<512><<<plan_grid(plan), NTHREADS, 0, stream>>>(xb, wp + (size_t)c0 * PK, bias, cu, hb, c0, drop_p, seed, offset,
-                                                                              epoch, plan);
-            MPO_LAUNCH_CHECK();
-        }
-    }
-    MPO_LAUNCH_CHECK();
-    return 0;
+    return patch_dim == 512 ? launch_fwd<512>(xb, wp, bias, cu, hb, embed, drop_p, seed, offset, epoch, plan, stream)
+         : patch_dim == 1024 ? launch_fwd<1024>(xb, wp, bias, cu, hb, embed, drop_p, seed, offset, epoch, plan, stream)
+                             : launch_fwd<2048>(xb, wp, bias, cu, hb, embed, drop_p, seed, offset, epoch, plan, stream);
 }

@@ -27,16 +27,24 @@ from .transformer import make_set_transformer
 MODEL_SIZES = {"small": [128, 128], "medium": [256, 256], "big": [512, 512]}
 
 
+def _check_patch_dim(patch_dim: int) -> int:
+    """The width of the patch features (the reference fixes 1024: models/mcat/mcat.py:25): one of ops.PATCH_DIMS."""
+    if patch_dim not in ops.PATCH_DIMS:
+        raise ValueError(f"patch_dim {patch_dim}: the patch layer is built for feature widths {set(ops.PATCH_DIMS)}")
+    return int(patch_dim)
+
+
 class _FusionModelBase(nn.Module):
     def __init__(self, omic_sizes: Sequence[int], model_size: str, n_classes: int, dropout: float, fusion: str,
-                 device: str, bag_dtype: torch.dtype):
+                 device: str, bag_dtype: torch.dtype, patch_dim: int = 1024):
         super().__init__()
+        self.patch_dim = _check_patch_dim(patch_dim)
         self.n_classes = n_classes
         self.model_sizes = MODEL_SIZES[model_size]
         d0, d1 = self.model_sizes
         self.bag_dtype = bag_dtype
         # H: patch fully-connected layer (stock modules; fusing it into K1 is SURVEY 8(f) f1)
-        self.H = nn.Sequential(nn.Linear(1024, d0), nn.ReLU(), nn.Dropout(dropout))
+        self.H = nn.Sequential(nn.Linear(self.patch_dim, d0), nn.ReLU(), nn.Dropout(dropout))
         # G: one 2-layer SNN per omic group
         self.G = nn.ModuleList([
             nn.Sequential(
@@ -68,14 +76,21 @@ class _FusionModelBase(nn.Module):
     def _patch_fc(self, bags: BagBatch) -> BagBatch:
         x = bags.data
         lin = self.H[0]
+        self._check_window(bags)
         p = self.H[2].p if self.training else 0.0
         if x.dtype == torch.bfloat16:
             h = ops.patch_fc(x, lin.weight, lin.bias, p, pre_gated_grad=self._fused_bag_gate, batch=bags)
         elif ops.patch_fc_f32_supported(x, lin.weight):
             h = ops.patch_fc_f32(x, lin.weight, lin.bias, p)        # fp32 window, 1024 -> 256: hand-written both ways
-        else:                                                       # fp32 window of the small / big models: the exact-fp32 MFMA GEMM (many-row form)
+        else:                                                       # fp32 window of the small / big models or of patch_dim 512 / 2048: the exact-fp32 MFMA GEMM (many-row form)
             h = F.dropout(ops.linear(x.float(), lin.weight, lin.bias, "relu"), p, self.training)
         return bags.with_data(h)
+
+    def _check_window(self, bags: BagBatch):
+        """The window's feature width is the model's (a kernel reads patch_dim values per row: a mismatch is never passed on)."""
+        x, k = bags.data, self.H[0].in_features
+        if x.dim() != 2 or x.shape[1] != k:
+            raise ValueError(f"patch features {tuple(x.shape)}: this model was built with patch_dim={k}")
 
     def _token_pair(self, bags: BagBatch, omics):
         return None
@@ -102,6 +117,7 @@ class _FusionModelBase(nn.Module):
         The path and the omic set-Transformer / pooling head have identical geometry and run as ONE launch sequence
         with grouped GEMMs (ops.encoder_stacked, ops.gated_pool_stacked): the token tail is a latency-bound chain of
         small launches, so the omic branch rides along in launches the path branch needs anyway."""
+        self._check_window(bags)
         pair = self._token_pair(bags, omics)
         g_bag = self._omic_fc(omics, pair)
         h_coattn, a_coattn, g_tok = self._patch_and_co_attend(g_bag, bags, inference, pair)
@@ -148,11 +164,12 @@ class _FusionModelBase(nn.Module):
 
 
 class MultimodalCoAttentionTransformer(_FusionModelBase):
-    """MCAT (models/mcat/mcat.py:12).  forward(wsi, omics, inference=False)."""
+    """MCAT (models/mcat/mcat.py:12).  forward(wsi, omics, inference=False).  patch_dim: the width of the patch features,
+    512, 1024 (the reference's) or 2048; the window handed to the model must have it."""
 
     def __init__(self, omic_sizes: [], model_size: str = "medium", n_classes: int = 4, dropout: float = 0.25,
-                 fusion: str = "concat", device: str = "cpu", bag_dtype: torch.dtype = torch.float32):
-        super().__init__(omic_sizes, model_size, n_classes, dropout, fusion, device, bag_dtype)
+                 fusion: str = "concat", device: str = "cpu", bag_dtype: torch.dtype = torch.float32, patch_dim: int = 1024):
+        super().__init__(omic_sizes, model_size, n_classes, dropout, fusion, device, bag_dtype, patch_dim)
 
     def _make_co_attention(self, d):
         return CoAttention(embed_dim=d, num_heads=1)
@@ -192,8 +209,8 @@ class NarrowContextualAttentionGateTransformer(_FusionModelBase):
     """NaCAGaT (models/nacagat/nacagat.py:9).  forward(wsi, omics): the map is always returned (:93)."""
 
     def __init__(self, omic_sizes: [], model_size: str = "medium", n_classes: int = 4, dropout: float = 0.25,
-                 fusion: str = "concat", device: str = "cpu", bag_dtype: torch.dtype = torch.float32):
-        super().__init__(omic_sizes, model_size, n_classes, dropout, fusion, device, bag_dtype)
+                 fusion: str = "concat", device: str = "cpu", bag_dtype: torch.dtype = torch.float32, patch_dim: int = 1024):
+        super().__init__(omic_sizes, model_size, n_classes, dropout, fusion, device, bag_dtype, patch_dim)
 
     def _make_co_attention(self, d):
         return PreGatingContextualAttention(embed_dim=d, num_heads=1)
@@ -237,12 +254,13 @@ class GeneExprNarrowContextualAttentionGateTransformer(nn.Module):
     of the 6-token tail called with T = L = M (csrc/tail_api.hip picks the long-axis kernels)."""
 
     def __init__(self, model_size: str = "medium", n_classes: int = 3, dropout: float = 0.25,
-                 bag_dtype: torch.dtype = torch.float32):
+                 bag_dtype: torch.dtype = torch.float32, patch_dim: int = 1024):
         super().__init__()
+        self.patch_dim = _check_patch_dim(patch_dim)
         self.model_sizes = MODEL_SIZES[model_size]
         d0, d1 = self.model_sizes
         self.bag_dtype = bag_dtype
-        self.H = nn.Sequential(nn.Linear(1024, d0), nn.ReLU(), nn.Dropout(dropout))
+        self.H = nn.Sequential(nn.Linear(self.patch_dim, d0), nn.ReLU(), nn.Dropout(dropout))
         self.self_attention = nn.MultiheadAttention(embed_dim=d1, num_heads=1)      # parameter holder
         self.path_transformer = make_set_transformer(d1, dropout)
         self.path_attention_head = AttentionNetGated(n_classes=1, input_dim=d1, hidden_dim=d1)
@@ -250,6 +268,7 @@ class GeneExprNarrowContextualAttentionGateTransformer(nn.Module):
         self.classifier = nn.Linear(d1, n_classes)
 
     _patch_fc = _FusionModelBase._patch_fc
+    _check_window = _FusionModelBase._check_window
     _fused_bag_gate = False
 
     def forward(self, wsi):

@@ -325,7 +325,8 @@ def _patch_weight_grad_now_or_deferred(g, x, dw, weight):
 class PatchFcFn(torch.autograd.Function):
     """H_bag = dropout_p(relu(X W_H^T + b)) for a bf16-stored window (models/mcat/mcat.py:24-29,87).
 
-    Forward: one pass of csrc/patch_fc_fwd.hip (embed 128 / 256 / 512: the same kernel, see its header), the dropout mask kept
+    Forward: one pass of csrc/patch_fc_fwd.hip (patch_dim 512 / 1024 / 2048, embed 128 / 256 / 512: the same kernel, see its
+    header), the dropout mask kept
     in H_bag as zeros.  Backward: the ReLU / dropout derivative (in the consumer's kernel when it can, else one element-wise
     pass) and dW_H = g^T X on csrc/patch_wgrad.hip.  X never needs a gradient (it is data).  Other geometries raise."""
 
@@ -333,8 +334,8 @@ class PatchFcFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias, drop_p: float, pre_gated_grad: bool, batch=None):
         lib = L.lib()
         if not patch_fc_kernel_supported(x, weight):
-            raise ValueError(f"patch layer: built for a contiguous bf16 window through Linear(1024, 128 | 256 | 512) "
-                             f"(got {x.dtype} {tuple(x.shape)} -> {weight.shape[0]})")
+            raise ValueError(f"patch layer: built for a contiguous bf16 window through Linear(512 | 1024 | 2048, 128 | 256 | 512) "
+                             f"(patch_dim in {set(PATCH_DIMS)}; got {x.dtype} {tuple(x.shape)} through a weight {tuple(weight.shape)})")
         if batch is None:                   # a bare patch matrix: one slide
             batch = BagBatch(x, make_cu([x.shape[0]], x.device), [x.shape[0]])
         h = torch.empty(x.shape[0], weight.shape[0], device=x.device, dtype=torch.bfloat16)
@@ -593,13 +594,19 @@ def fused_patch_coattn_supported(x, embed: int, n_q: int) -> bool:
     return x.dtype == torch.bfloat16 and x.shape[1] == 1024 and embed == 256 and n_q <= 8
 
 
+# Patch feature widths the bf16 patch layer is built for, forward (csrc/patch_fc_fwd.hip) and weight gradient
+# (csrc/patch_wgrad.hip): the reference's truncated ResNet-50 (1024), CONCH / ResNet-18 / -34 (512), the full ResNet-50 (2048).
+PATCH_DIMS = (512, 1024, 2048)
+
+
 def patch_fc_kernel_supported(x, weight) -> bool:
-    """mpo_patch_fc_forward: a bf16 window through Linear(1024, 128 | 256 | 512)."""
-    return x.dtype == torch.bfloat16 and x.is_contiguous() and weight.shape[0] in (128, 256, 512) and weight.shape[1] == 1024
+    """mpo_patch_fc_forward: a bf16 window through Linear(512 | 1024 | 2048, 128 | 256 | 512)."""
+    return (x.dtype == torch.bfloat16 and x.is_contiguous() and x.dim() == 2 and weight.shape[0] in (128, 256, 512)
+            and weight.shape[1] in PATCH_DIMS and x.shape[1] == weight.shape[1])
 
 
 def patch_fc(x_bf16, weight, bias, drop_p: float, pre_gated_grad: bool = False, batch: "BagBatch | None" = None):
-    """H_bag = dropout(relu(x W^T + b)), bf16.  batch (the window's row offsets / work plan): lets Linear(1024, 256) run as
+    """H_bag = dropout(relu(x W^T + b)), bf16.  batch (the window's row offsets / work plan): lets the layer run as
     one hand-written pass; the tensor then carries `_mpo_keep_scale` = 1 / (1 - realised dropout rate) for consumers that
     apply the ReLU / dropout derivative themselves."""
     h = PatchFcFn.apply(x_bf16, weight, bias, drop_p, pre_gated_grad, batch)

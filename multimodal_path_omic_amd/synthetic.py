@@ -71,22 +71,22 @@ def slide_lengths(n_slides: int, lo: int, hi: int, seed: int) -> "list[int]":
     return [int(x) for x in gen.integers(lo, hi + 1, size=n_slides)]
 
 
-def make_cohort(n_slides: int, m_lo: int, m_hi: int, omic_sizes, seed: int, n_classes: int = 4):
+def make_cohort(n_slides: int, m_lo: int, m_hi: int, omic_sizes, seed: int, n_classes: int = 4, patch_dim: int = PATCH_DIM):
     """Seeded synthetic survival cohort with a planted signal.
 
-    Returns a list of dicts with keys wsi (M,1024), omics [N x (d_i,)],
+    Returns a list of dicts with keys wsi (M, patch_dim), omics [N x (d_i,)],
     survival_months, survival_class, censorship -- the tuple layout of
     MultimodalDataset.__getitem__ (dataset/dataset.py:119-143).  The event time is
     a noisy monotone function of one direction in patch space and one in omic
     space so that a model can learn a C-index above 0.5.
     """
     gen = rng(seed)
-    w_patch = gen.standard_normal(PATCH_DIM) / np.sqrt(PATCH_DIM)
+    w_patch = gen.standard_normal(patch_dim) / np.sqrt(patch_dim)
     slides = []
     for i in range(n_slides):
         m = int(gen.integers(m_lo, m_hi + 1))
         z = gen.standard_normal()                        # latent risk
-        wsi = gen.standard_normal((m, PATCH_DIM)) + 0.5 * z * w_patch[None, :] * np.sqrt(PATCH_DIM) / 8
+        wsi = gen.standard_normal((m, patch_dim)) + 0.5 * z * w_patch[None, :] * np.sqrt(patch_dim) / 8
         omics = [gen.standard_normal(s) + 0.5 * z for s in omic_sizes]
         months = float(np.exp(3.0 - 0.8 * z + 0.3 * gen.standard_normal()))
         slides.append(dict(
