@@ -6,6 +6,7 @@ For a bf16-stored bag the oracle is fed the same bf16-rounded values (bf16 is a 
 the INPUT; arithmetic stays fp32-accurate through hi/lo operand splitting), the bag gradient is
 rounded to bf16 by construction and gets a bf16-sized tolerance.
 """
+import contextlib
 import math
 
 import pytest
@@ -61,10 +62,18 @@ def test_linear_matches_torch(dev, act, rows, i, o):
 @pytest.mark.parametrize("case", list(C.COATTN_CASES))
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_coattn_forward_backward(dev, golden, case, dtype):
+    check_coattn_forward_backward(dev, golden, case, dtype)
+
+
+def check_coattn_forward_backward(dev, golden, case, dtype, to_dev=None):
+    """The body of test_coattn_forward_backward (tests/test_gpu_plan_cuts.py runs it again under coarser work plans).
+    `to_dev` places the bag on the device (default: a plain copy); returns the worst error per quantity."""
     m, gain, seed = C.COATTN_CASES[case]
     mod, p = make_module(seed, gain, dev)
     q, bag, p_out, p_a = C.coattn_inputs(m, seed + 1)
     bag_in = bag.to(dtype)                                    # what the kernel stores/reads
+    to_dev = to_dev or (lambda t: t.to(dev))
+    worst = {}
     # ---- oracle on exactly the values the kernel sees
     qo = q.clone().requires_grad_(True)
     bo = bag_in.float().clone().requires_grad_(True)
@@ -74,7 +83,7 @@ def test_coattn_forward_backward(dev, golden, case, dtype):
     g0_o = oracle_grads((out_o * p_out).sum(), named)
 
     qd = q.to(dev).requires_grad_(True)
-    bd = bag_in.to(dev).requires_grad_(True)
+    bd = to_dev(bag_in).requires_grad_(True)
     # training-style call (no map), models/mcat/mcat.py:97 with inference=False
     out0, a0 = mod(query=qd, key=bd, value=bd, need_weights=False)
     assert a0 is None
@@ -82,6 +91,7 @@ def test_coattn_forward_backward(dev, golden, case, dtype):
     assert a1.shape == (C.N_OMIC, m)
     assert relerr(out0, out_o) < 1e-4, relerr(out0, out_o)
     assert relerr(out1, out_o) < 1e-4
+    worst["out"] = max(relerr(out0, out_o), relerr(out1, out_o))
     # attention map: relative, element-wise
     rel_a = ((a1.detach().cpu() - a_o.detach()).abs() / a_o.detach().clamp_min(1e-30)).max().item()
     # The score operand enters the MFMA in THREE bf16 terms (all 24 mantissa bits; two terms left the deliberately peaky
@@ -89,6 +99,7 @@ def test_coattn_forward_backward(dev, golden, case, dtype):
     # fp64 on the peaky one; an fp32 bag keeps a 2^-17 residual of its own hi + lo split).
     print(f"[K1 map] {case} {str(dtype)[6:]}: rel err {rel_a:.2e}")
     assert rel_a < 1e-3, rel_a
+    worst["map"] = rel_a
     torch.testing.assert_close(a1.sum(1).cpu(), torch.ones(C.N_OMIC), rtol=1e-4, atol=1e-4)
 
     params = dict(mod.named_parameters())
@@ -102,6 +113,9 @@ def test_coattn_forward_backward(dev, golden, case, dtype):
             tol = bag_tol if n == "bag" else 1e-3
             e = relerr(gr, ref[n]) if ref[n].abs().max() > 0 else float(gr.abs().max())
             assert e < tol, (tag, n, e)
+            key = "d_bag" if n == "bag" else "grads"
+            worst[key] = max(worst.get(key, 0.0), e)
+            assert bool(torch.isfinite(gr.float()).all()), (tag, n)
 
     if dtype == torch.float32:
         # the reference's own numbers (golden vectors), fp32 bag only
@@ -114,22 +128,33 @@ def test_coattn_forward_backward(dev, golden, case, dtype):
             ref = g[f"{case}/grad1/{n}"]
             if ref.abs().max() > 0:
                 assert relerr(sub(gr), ref) < 2e-3, (n, relerr(sub(gr), ref))
+    return worst
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_coattn_ragged_window_equals_per_slide(dev, dtype):
     """A window of slides in ONE ragged launch gives each slide the result of its own call."""
-    lengths = [1, 31, 32, 33, 500, 4097, 129]
+    check_coattn_ragged_window(dev, dtype, [1, 31, 32, 33, 500, 4097, 129])
+
+
+def check_coattn_ragged_window(dev, dtype, lengths, window_plan=contextlib.nullcontext(), place=None):
+    """The body of test_coattn_ragged_window_equals_per_slide; the window's batch is built, run and differentiated inside
+    `window_plan` (tests/test_gpu_plan_cuts.py: a coarser work plan for the window, the slides keep their own); `place` puts
+    the window's concatenated rows where the caller wants them (default: a clone).  Returns the worst window-against-slide
+    differences."""
     mod, p = make_module(77, 2.0, dev)
     g = syn.rng(78)
     bags = [torch.clamp(syn.normal(g, (m, C.E)), min=0).to(dtype).to(dev) for m in lengths]
     query = syn.normal(g, (len(lengths), C.N_OMIC, C.E)).to(dev).requires_grad_(True)
-    batch = BagBatch.from_list(bags)
-    data = batch.data.clone().requires_grad_(True)
-    out_w, maps = mod.forward_window(query, batch.with_data(data), need_weights=True)
     probe = syn.normal(g, (len(lengths), C.N_OMIC, C.E)).to(dev)
-    gq, gb, gw = torch.autograd.grad((out_w * probe).sum(), [query, data, mod.in_proj_weight])
+    with window_plan:
+        batch = BagBatch.from_list(bags)
+        data = (place(batch.data) if place else batch.data.clone()).requires_grad_(True)
+        out_w, maps = mod.forward_window(query, batch.with_data(data), need_weights=True)
+        gq, gb, gw = torch.autograd.grad((out_w * probe).sum(), [query, data, mod.in_proj_weight])
+    assert all(bool(torch.isfinite(t.float()).all()) for t in (out_w, gq, gb, gw, *maps))
     off = 0
+    worst = {"out": 0.0, "map": 0.0, "d_query": 0.0, "d_bag": 0.0}
     gw_sum = torch.zeros_like(gw)
     for i, bag in enumerate(bags):
         qi = query[i].detach().clone().requires_grad_(True)
@@ -142,11 +167,16 @@ def test_coattn_ragged_window_equals_per_slide(dev, dtype):
         assert relerr(o_i, o_o) < 1e-4
         assert ((a_i.cpu() - a_o).abs() / a_o.clamp_min(1e-30)).max().item() < 1e-3
         gqi, gbi, gwi = torch.autograd.grad((o_i * probe[i]).sum(), [qi, bi, mod.in_proj_weight])
+        for k, v in (("out", relerr(out_w[i], o_i)), ("map", relerr(maps[i], a_i)), ("d_query", relerr(gq[i], gqi)),
+                     ("d_bag", relerr(gb[off:off + lengths[i]], gbi))):
+            worst[k] = max(worst[k], v)
         assert relerr(gq[i], gqi) < 1e-5
         assert relerr(gb[off:off + lengths[i]], gbi) < 1e-5
         gw_sum += gwi
         off += lengths[i]
+    worst["d_in_proj_weight"] = relerr(gw, gw_sum)
     assert relerr(gw, gw_sum) < 1e-4
+    return worst
 
 
 def test_coattn_rejects_bad_arguments(dev):
