@@ -2,8 +2,6 @@
 gated pooling head called with T = L = M, and the gene-expression model of models/ge_nacagat/ge_nacagat.py against the
 reference's golden vectors.  Kernel-level checks compare with a plain torch fp32 restatement of the same op; bars: 1e-3
 relative on maps (north star), 1e-3 of the largest entry on gradients."""
-import math
-
 import pytest
 import torch
 
@@ -14,56 +12,16 @@ from multimodal_path_omic_amd.models import GeneExprNarrowContextualAttentionGat
 from multimodal_path_omic_amd.transformer import make_set_transformer
 from multimodal_path_omic_amd.blocks import AttentionNetGated
 from oracle import mpo_oracle as O
+from selfattn_helpers import _b3_modes, _dropout_mask_check, attention_ref, bf16x3, part_scale, relmax
 
 pytestmark = pytest.mark.gpu
 sub = syn.subsample
-
-
-def relmax(a, b, scale=None):
-    a, b = a.detach().double().cpu().reshape(-1), b.detach().double().cpu().reshape(-1)
-    return float((a - b).abs().max() / (b.abs().max().clamp_min(1e-30) if scale is None else scale))
-
-
-def part_scale(ref):
-    """Scale for one of dq / dk / dv: its own largest entry, but no smaller than 1e-2 of the whole gradient's (at M = 1 the
-    true dq and dk are exactly zero)."""
-    return lambda sl: max(float(ref[..., sl].abs().max()), 1e-2 * float(ref.abs().max()))
-
-
-def attention_ref(qkv, heads, keep=None):
-    """(n, M, 3d) fp64 on the CPU -> out (n, M, d), probabilities (n, h, M, M); keep: (n, h, M, M) scaled keep mask."""
-    n, m, d3 = qkv.shape
-    d, hd = d3 // 3, d3 // 3 // heads
-    q, k, v = (qkv[..., i * d:(i + 1) * d].reshape(n, m, heads, hd).transpose(1, 2) for i in range(3))
-    p = torch.softmax(q @ k.transpose(-1, -2) / math.sqrt(hd), dim=-1)
-    pd = p if keep is None else p * keep
-    return (pd @ v).transpose(1, 2).reshape(n, m, d), p
 
 
 CASES = [  # n_bags, M, d, heads, q gain
     (1, 333, 256, 1, 1.0), (1, 1000, 256, 8, 1.0), (2, 64, 256, 8, 1.0), (1, 70, 128, 1, 1.0), (1, 130, 128, 8, 1.0),
     (1, 200, 512, 8, 1.0), (1, 257, 256, 1, 6.0), (1, 515, 256, 8, 6.0), (1, 1, 256, 8, 1.0), (1, 17, 256, 1, 1.0),
     (1, 150, 512, 1, 1.0), (2, 333, 512, 1, 6.0)]      # one head of 512 (model_size='big'): dK / dV in two column passes
-
-
-def _b3_modes(d, heads):
-    """Heads of width 32 (several) and 256 (one) run on three-term bf16 MFMAs by default (~16 mantissa bits per operand); the
-    verification hook keeps them on the fp32 kernels.  -> [(hook value, output bar, gradient bar)]"""
-    b3 = (heads > 1 and d == 32 * heads) or (heads == 1 and d == 256)
-    return [(1, 1e-4, 1e-3), (0, 1e-5, 1e-4)] if b3 else [(1, 1e-5, 1e-4)]
-
-
-class bf16x3:
-    def __init__(self, on):
-        self.on = on
-
-    def __enter__(self):
-        from multimodal_path_omic_amd import _lib as L
-        self.was = L.lib().mpo_set_bag_self_attention_bf16x3(self.on)
-
-    def __exit__(self, *exc):
-        from multimodal_path_omic_amd import _lib as L
-        L.lib().mpo_set_bag_self_attention_bf16x3(self.was)
 
 
 @pytest.mark.parametrize("n,m,d,heads,gain", CASES)
@@ -97,25 +55,6 @@ def test_attention_core_equals_torch(dev, n, m, d, heads, gain):
             assert amap is None
 
 
-def _recover_keep(dev, qkv, heads, p, offset):
-    """The kernel's own (scaled) keep mask, read back through V = identity blocks: out[q][h hd + c] = P_drop[h][q][b hd + c]."""
-    n, m, d3 = qkv.shape
-    d, hd = d3 // 3, d3 // 3 // heads
-    _, p_ref = attention_ref(qkv.double(), heads)
-    keep = torch.zeros(n, heads, m, m, dtype=torch.float64)
-    for b in range((m + hd - 1) // hd):
-        probe = qkv.clone()
-        v = torch.zeros(n, m, heads, hd)
-        rows = torch.arange(b * hd, min(m, (b + 1) * hd))
-        v[:, rows, :, rows - b * hd] = 1.0
-        probe[..., 2 * d:] = v.reshape(n, m, d)
-        ops._rng_calls = offset
-        out, _ = ops.BagSelfAttentionFn.apply(probe.to(dev), heads, p, False)
-        pd = out.cpu().double().reshape(n, m, heads, hd).permute(0, 2, 1, 3)          # (n, h, q, c)
-        keep[..., rows] = pd[..., : len(rows)] / p_ref[..., rows].clamp_min(1e-300)
-    return keep
-
-
 @pytest.mark.parametrize("m,d,heads", [(96, 256, 8), (200, 256, 1), (70, 512, 1)])
 def test_attention_dropout_mask_is_shared_by_forward_and_backward(dev, m, d, heads):
     """Dropout on the probabilities: the mask is never stored.  It is read back here through identity-block values, must be
@@ -124,35 +63,6 @@ def test_attention_dropout_mask_is_shared_by_forward_and_backward(dev, m, d, hea
     for hook, out_bar, grad_bar in _b3_modes(d, heads):
         with bf16x3(hook):
             _dropout_mask_check(dev, m, d, heads, out_bar, grad_bar)
-
-
-def _dropout_mask_check(dev, m, d, heads, out_bar, grad_bar):
-    g = syn.rng(7100 + m)
-    qkv = syn.normal(g, (1, m, 3 * d)) * 0.5
-    probe = syn.normal(g, (1, m, d))
-    p, offset = 0.25, 12345
-    keep = _recover_keep(dev, qkv, heads, p, offset)
-    vals = keep.round(decimals=4).unique()
-    assert all(min(abs(float(v)), abs(float(v) - 1 / (1 - p))) < 1e-3 for v in vals), vals
-    rate = float((keep < 0.5).double().mean())
-    assert abs(rate - p) < 4 * math.sqrt(p * (1 - p) / keep.numel()) + 1e-3, rate
-    if heads > 1:
-        assert not torch.equal(keep[0, 0] > 0.5, keep[0, 1] > 0.5)                    # heads draw their own masks
-    ops._rng_calls = offset
-    x = qkv.to(dev).requires_grad_(True)
-    out, _ = ops.BagSelfAttentionFn.apply(x, heads, p, False)
-    (out * probe.to(dev)).sum().backward()
-    xr = qkv.double().requires_grad_(True)
-    out_r, _ = attention_ref(xr, heads, keep=(keep > 0.5).double() / (1 - p))
-    (out_r * probe.double()).sum().backward()
-    assert relmax(out, out_r) < out_bar
-    for part in range(3):
-        sl = slice(part * d, (part + 1) * d)
-        assert relmax(x.grad[..., sl], xr.grad[..., sl], part_scale(xr.grad)(sl)) < grad_bar, part
-    # another offset = another mask
-    ops._rng_calls = offset + 1
-    out2, _ = ops.BagSelfAttentionFn.apply(qkv.to(dev), heads, p, False)
-    assert not torch.equal(out2, out.detach())
 
 
 def _leaf(sd):
