@@ -260,6 +260,7 @@ int mpo_launch_bag_sa_fwd(const float* qkv, int n_seq, int M, int d, int H, floa
 int mpo_launch_bag_sa_bwd(const float* qkv, const float* o, const float* saved, const float* d_o, int n_seq, int M, int d, int H,
                           float drop_p, unsigned long long seed, unsigned long long offset, const unsigned long long* epoch,
                           float* dqkv, float* scratch, hipStream_t s);
+int mpo_check_mha_small(int T, int d, int H);      // non-zero (error set) for a geometry the forward OR the backward would refuse
 int mpo_launch_mha_small_fwd(const float* qkv, float* o, float* p_save, int B, int T, int d, int H, float drop_p,
                              unsigned long long seed, unsigned long long offset, const unsigned long long* epoch,
                              hipStream_t s);

@@ -948,13 +948,29 @@ int mpo_launch_ln_bwd_params_only(const float* dy, const float* x, const float* 
                                   hipStream_t s) {
     return mpo_launch_ln_bwd_br(dy, x, stats, one_branch(nullptr, nullptr, dw, db, rows), nullptr, rows, d, 0, 2, s);
 }
+// dynamic LDS of the two mha_small kernels: four waves of per_wave floats (the kernels' own carve).  The backward's is the
+// larger for every T >= 1, hd >= 1 (by T (hd + 2 T - 2) floats per wave), so a geometry the forward takes must fit the
+// backward as well: a training step must not pass its forward and be refused in its backward.
+constexpr size_t kMhaSmallMaxLds = 160 * 1024;
+static size_t mha_small_lds(int T, int hd, bool backward) {
+    const size_t per_wave = backward ? (size_t)4 * T * hd + 4 * T * T : (size_t)3 * T * hd + 2 * T * T + 2 * T;
+    return 4 * per_wave * sizeof(float);
+}
+// what mpo_launch_mha_small_fwd asks of a geometry; mpo_encoder_forward asks it before its first launch
+int mpo_check_mha_small(int T, int d, int H) {
+    MPO_CHECK(T >= 1 && T <= kMaxT && H >= 1 && d % H == 0, "set-transformer attention: T=%d (max %d), d=%d, heads=%d", T, kMaxT, d, H);
+    const int hd = d / H;
+    MPO_CHECK(mha_small_lds(T, hd, true) <= kMhaSmallMaxLds,
+              "set-transformer attention: T=%d, head dim %d: the backward needs %zu bytes of LDS (forward %zu, at most %zu)", T, hd,
+              mha_small_lds(T, hd, true), mha_small_lds(T, hd, false), kMhaSmallMaxLds);
+    return 0;
+}
 int mpo_launch_mha_small_fwd(const float* qkv, float* o, float* p_save, int B, int T, int d, int H, float drop_p,
                              unsigned long long seed, unsigned long long offset, const unsigned long long* epoch,
                              hipStream_t s) {
-    MPO_CHECK(T >= 1 && T <= kMaxT && d % H == 0, "set-transformer attention: T=%d (max %d), d=%d, heads=%d", T, kMaxT, d, H);
+    RC(mpo_check_mha_small(T, d, H));
     const int hd = d / H;
-    const size_t lds = 4 * ((size_t)3 * T * hd + 2 * T * T + 2 * T) * sizeof(float);
-    MPO_CHECK(lds <= 160 * 1024, "set-transformer attention: T=%d, head dim %d needs %zu bytes of LDS", T, hd, lds);
+    const size_t lds = mha_small_lds(T, hd, false);
     if (T == 6 && hd == 32) mha_small_fwd_kernel<6, 32><<<(B * H + 3) / 4, 256, lds, s>>>(qkv, o, p_save, B, T, d, H, drop_p, seed, offset, epoch);
     else mha_small_fwd_kernel<0, 0><<<(B * H + 3) / 4, 256, lds, s>>>(qkv, o, p_save, B, T, d, H, drop_p, seed, offset, epoch);
     MPO_LAUNCH_CHECK();
@@ -964,8 +980,8 @@ int mpo_launch_mha_small_bwd(const float* qkv, const float* p_save, const float*
                              hipStream_t s) {
     MPO_CHECK(T >= 1 && T <= kMaxT && d % H == 0, "set-transformer attention: T=%d (max %d), d=%d, heads=%d", T, kMaxT, d, H);
     const int hd = d / H;
-    const size_t lds = 4 * ((size_t)4 * T * hd + 4 * T * T) * sizeof(float);
-    MPO_CHECK(lds <= 160 * 1024, "set-transformer attention backward: T=%d, head dim %d needs %zu bytes of LDS", T, hd, lds);
+    const size_t lds = mha_small_lds(T, hd, true);
+    MPO_CHECK(lds <= kMhaSmallMaxLds, "set-transformer attention backward: T=%d, head dim %d needs %zu bytes of LDS", T, hd, lds);
     if (T == 6 && hd == 32) mha_small_bwd_kernel<6, 32><<<(B * H + 3) / 4, 256, lds, s>>>(qkv, p_save, d_o, dqkv, B, T, d, H);
     else mha_small_bwd_kernel<0, 0><<<(B * H + 3) / 4, 256, lds, s>>>(qkv, p_save, d_o, dqkv, B, T, d, H);
     MPO_LAUNCH_CHECK();

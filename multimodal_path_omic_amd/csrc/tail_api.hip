@@ -189,6 +189,8 @@ int mpo_encoder_forward(const float* x, int n_branches, int n_slides, int T, int
     MPO_CHECK(drop_p <= 0.f || T > kSmallAttnMaxT || (uint64_t)heads * T <= (uint64_t)(ff > 3 * d ? ff : 3 * d),
               "encoder: heads * T = %d * %d exceeds max(ff, 3 d) = %d: the attention dropout stream would overlap the next one",
               heads, T, ff > 3 * d ? ff : 3 * d);
+    // (a geometry whose attention backward would be refused is refused here, before the first launch)
+    if (T <= kSmallAttnMaxT) RC(mpo_check_mha_small(T, d, heads));
     const int NB = n_branches, R = n_slides * T, RT = NB * R, BT = NB * n_slides;
     const uint64_t stride = enc_stream_stride(BT, T, d, ff);
     Carve<kPad64> c(saved);

@@ -1,0 +1,404 @@
+"""The token tail's non-GEMM kernels (csrc/tail.hip: LayerNorm, `mha_small_*`, the three pooling families, the survival head and
+loss kernels, the CAG middle) at the edges of their launch arithmetic, over the case tables of tests/test_tail_edges_cpu.py.
+
+The comparisons are composite, as everywhere in the suite for these entries: the GEMMs plus these kernels against the fp64
+oracle (oracle/mpo_oracle.py), in eval mode and -- with p = 0.25 and the masks replayed by tests/dropout_replay.py -- in
+training mode.  Bars are the project's own: forward 1e-4 of the reference's largest entry, dx and every parameter gradient 2e-3 of
+that tensor's largest entry (tests/test_gpu_train_dropout.py); head and losses the rtol / atol of tests/test_gpu_tail.py and
+tests/test_gpu_sct_loss.py; CAG 1e-4 / 1e-3 (tests/test_gpu_coattn_nacagat.py).
+
+Every encoder and pooling case runs through the C ABI on buffers the test owns (tail_helpers.encoder_guarded / pool_guarded:
+sized exactly by the entry's size query, between runs of NaN that must survive); the training-mode cases also through `ops`."""
+import pytest
+import torch
+import torch.nn as nn
+
+import dropout_replay as R
+import tail_helpers as H
+import test_tail_edges_cpu as E
+from multimodal_path_omic_amd import _lib as L
+from multimodal_path_omic_amd import ops
+from multimodal_path_omic_amd import synthetic as syn
+from multimodal_path_omic_amd.blocks import ContextualAttentionGate
+from multimodal_path_omic_amd.fusion import ConcatFusion
+from oracle import mpo_oracle as O
+
+pytestmark = pytest.mark.gpu
+MODES = [False, True]
+MODE_IDS = ["eval", "training"]
+
+
+@pytest.fixture(autouse=True)
+def _rng_calls_put_back():
+    was = ops._rng_calls
+    yield
+    ops._rng_calls = was
+
+
+def ids(case):
+    return "x".join(str(v) for v in case)
+
+
+# ---------------------------------------------------------------------------------------------------------------- encoder
+def _unaligned_module_parameter(dev, enc, name):
+    """Replaces parameter `name` ('enc.layers.0.norm1.weight') of `enc` by a view one float into a larger tensor."""
+    owner = enc
+    *path, leaf = name[len("enc."):].split(".")
+    for part in path:
+        owner = getattr(owner, part)
+    old = getattr(owner, leaf)
+    base = torch.zeros(old.numel() + 1, device=dev)
+    base[1:].copy_(old.detach())
+    setattr(owner, leaf, nn.Parameter(base[1:]))
+    assert getattr(owner, leaf).data_ptr() % 16 == 4
+
+
+def encoder_case(dev, case, training, unaligned=()):
+    nb, ns, T, d, heads, ff = case
+    tag = f"[tail edges] encoder {case} {'training' if training else 'eval'}{' unaligned' if unaligned else ''}"
+    sds, encs, x, probe = H._encoder_setup(dev, nb, ns, T, d, 3000 + 37 * T + d + 5 * heads + nb + ns, ff, heads, training)
+    keeps = R.encoder_keeps(H.SEED, H.OFF, nb, ns, T, d, ff, heads, H.LAYERS, H.P) if training else None
+    ref = H._encoder_oracle(sds, x, probe, keeps, heads)
+    got = H.encoder_guarded(dev, sds, x, probe, ff, heads, training, unaligned)
+    H.encoder_compare(tag + " C ABI", got, ref, sds)
+    if training:
+        for br, name in unaligned:
+            _unaligned_module_parameter(dev, encs[br], name)
+        H.encoder_compare(tag + " ops", H._encoder_gpu(dev, sds, encs, x, probe, True), ref, sds)
+
+
+@pytest.mark.parametrize("training", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("case", [c for c in E.ENCODER_CASES if c != E.LDS_CASE], ids=ids)
+def test_encoder_edges(dev, case, training):
+    """(2, 128, 16, 256, 8, 512) in eval mode is the one figure of this file near its bar: dx 1.4e-3 and linear1.weight 1.6e-3
+    of 2e-3, everything else of the case at 3e-7.  Of its 2 x 10^6 FFN pre-activations per layer one, branch 0 layer 0 row 1690
+    column 489, is +3.07e-7 in fp64 at a maximum of 5.0 -- inside the fp32 rounding of a 256-term product -- and the whole dx
+    error sits in that row (the next rows: 2e-4 and below, median 2e-7): the ReLU gate of one element differs, not a kernel.
+    In training mode the dropout masks move the pre-activations and the same case is at 5e-7."""
+    encoder_case(dev, case, training)
+
+
+def test_encoder_head_width_128_launches_with_more_than_64_kib_of_lds(dev):
+    """hd = 128 at T = 16: 107 008 bytes of dynamic LDS in the forward, 147 456 in the backward -- the largest head width both
+    launchers take at T = kMaxT is 144.  Eval, then training."""
+    m = E.mha(*E.LDS_CASE[:5])
+    assert m["lds_fwd"] > 64 * 1024 and m["lds_bwd"] <= E.MHA_MAX_LDS
+    encoder_case(dev, E.LDS_CASE, False)
+    encoder_case(dev, E.LDS_CASE, True)
+
+
+@pytest.mark.parametrize("training", MODES, ids=MODE_IDS)
+def test_encoder_unaligned_layer_norm_parameter(dev, training):
+    """norm1.weight of branch 1, layer 0, one float into its storage: ln_vec_ok is false and d = 256 runs the strided kernels."""
+    encoder_case(dev, E.UNALIGNED_CASE, training, unaligned=(E.UNALIGNED_PARAM,))
+
+
+def _encoder_refused(dev, case, training, match):
+    """mpo_encoder_forward on `case` must fail with `match` and launch nothing: y and `saved` (where the first launch, the
+    in-projection, writes qkv) are still NaN."""
+    nb, ns, T, d, heads, ff = case
+    sds, _, x, _ = H._encoder_setup(dev, nb, ns, T, d, 77, ff, heads, training)
+    G = H.Guarded(dev)
+    xb = G.buf(x.numel(), x)
+    params = [G.buf(v.numel(), v) for sd in sds for v in sd.values()]
+    y = G.buf(x.numel())
+    saved = G.buf(nb * ns * T * 3 * d)
+    p, seed, off = (H.P, H.SEED, H.OFF) if training else (0.0, 0, 0)
+    with pytest.raises(RuntimeError, match=match):
+        L.call("mpo_encoder_forward", L.ptr(xb), nb, ns, T, d, ff, heads, H.LAYERS, L.ptr_array(params), float(p), seed, off,
+               ops._epoch(), L.ptr(y), L.ptr(saved), L.stream_of(xb))
+    assert G.all_nan([y, saved])
+
+
+def test_encoder_refuses_five_branches(dev):
+    _encoder_refused(dev, E.FIVE_BRANCHES, False, "1\\.\\.4 branches")
+    encs = [H.make_set_transformer(256, H.P).to(dev) for _ in range(5)]
+    with pytest.raises(RuntimeError, match="1\\.\\.4 branches"):
+        ops.encoder_stacked(torch.zeros(5, 1, 6, 256, device=dev), [list(e.layers) for e in encs], training=False)
+
+
+@pytest.mark.parametrize("training", MODES, ids=MODE_IDS)
+def test_encoder_forward_refuses_what_its_backward_would_refuse(dev, training):
+    """d = 160 with one head at T = 16: the forward's LDS (131 584 bytes) fits, the backward's (180 224) does not.  The forward
+    used to run and the backward to fail; now the forward entry refuses before its first launch and names the backward's need."""
+    _encoder_refused(dev, E.LDS_REFUSED, training, "backward needs 180224 bytes")
+    nb, ns, T, d, heads, ff = E.LDS_REFUSED
+    enc = H.make_set_transformer(d, H.P, nhead=heads, dim_feedforward=ff, num_layers=1).to(dev)
+    with pytest.raises(RuntimeError, match="backward needs"):
+        ops.encoder_stacked(torch.zeros(nb, ns, T, d, device=dev), [list(enc.layers)], training=training)
+
+
+# ---------------------------------------------------------------------------------------------------------------- gated pool
+def pool_case(dev, case, training, interleave):
+    nb, ns, L_, d = case
+    tag = (f"[tail edges] pool {E.pool_route(nb, L_, d)} {case} {'training' if training else 'eval'} "
+           f"{'interleaved' if interleave else 'plain'}")
+    sds, heads, rhos, x, ph, pa = H._pool_setup(dev, nb, ns, L_, d, 4000 + 13 * L_ + d + nb + ns, training=training)
+    keeps = R.pool_keeps(H.SEED, H.OFF, nb, ns, L_, d, H.P, H.P, interleave) if training else None
+    ref = H._pool_oracle(sds, x, ph, pa, keeps)
+    H.pool_compare(tag + " C ABI", H.pool_guarded(dev, sds, x, ph, pa, interleave, training), ref, sds)
+    if training:
+        H.pool_compare(tag + " ops", H._pool_gpu(dev, sds, heads, rhos, x, ph, pa, interleave, True), ref, sds)
+
+
+@pytest.mark.parametrize("interleave", [False, True], ids=["plain", "interleaved"])
+@pytest.mark.parametrize("training", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("case", E.POOL_FUSED + E.POOL_SHORT + E.POOL_LONG, ids=ids)
+def test_gated_pool_edges(dev, case, training, interleave):
+    assert case[3] % 4 == 0
+    pool_case(dev, case, training, interleave)
+
+
+@pytest.mark.parametrize("case", E.POOL_FUSED_EVAL_PLAIN, ids=ids)
+def test_gated_pool_width_off_the_4_grid(dev, case):
+    """d = 102: no row of x, a, b is 16-byte aligned; eval mode, plain layout."""
+    pool_case(dev, case, False, False)
+
+
+@pytest.mark.parametrize("case", E.POOL_SHORT_FORWARD_ONLY, ids=ids)
+def test_gated_pool_three_and_four_branches_forward_only(dev, case):
+    """More than two branches leave the fused scorer for pool_fwd_kernel; the backward refuses them and launches nothing."""
+    nb, ns, L_, d = case
+    assert E.pool_route(nb, L_, d) == "short"
+    sds, _, _, x, ph, pa = H._pool_setup(dev, nb, ns, L_, d, 4500 + nb, training=False)
+    ref = H._pool_oracle(sds, x, ph, pa, None)
+    for interleave in (False, True):
+        sc, h, _, _, state = H.pool_guarded(dev, sds, x, ph, pa, interleave, False, backward=False)
+        H.pool_compare(f"[tail edges] pool short {case} eval interleave={interleave} C ABI, forward", (sc, h, None, None), ref, sds,
+                       forward_only=True)
+        with pytest.raises(RuntimeError, match="1\\.\\.2 branches"):
+            state["run_backward"]()
+        assert state["G"].all_nan(state["untouched"])
+        state["G"].check("gated pool, refused backward")
+
+
+def test_gated_pool_refuses_interleaved_output_off_the_4_grid(dev):
+    nb, ns, L_, d = E.POOL_REFUSED_INTERLEAVED
+    sds, heads, rhos, x, ph, pa = H._pool_setup(dev, nb, ns, L_, d, 4600, training=False)
+    with pytest.raises(RuntimeError, match="interleaved h needs d % 4 == 0"):
+        H.pool_guarded(dev, sds, x, ph, pa, True, False)
+    with pytest.raises(RuntimeError, match="interleaved h needs d % 4 == 0"):
+        ops.gated_pool_stacked(x.to(dev), heads, rhos, training=False, interleave=True)
+
+
+# ---------------------------------------------------------------------------------------------------------------- head, losses
+EPS = 1e-7
+HEAD_ABS = 1e-5                                   # hazards, survs, Y (test_fusion_head_matches_golden)
+CES_LOSS, CES_GRAD = dict(rtol=1e-5, atol=1e-6), dict(rtol=1e-5, atol=1e-7)            # test_ces_loss_kernel_matches_...
+SCT_LOSS, SCT_GRAD = dict(rtol=1e-5, atol=1e-6), dict(rtol=0, atol=1e-6)               # test_standalone_sct_matches_fp64
+FUSED_LOSS, FUSED_GRAD = dict(rtol=1e-4, atol=1e-4), dict(rtol=0, atol=1e-6)           # test_fused_sct_head_matches_fp64
+
+
+def head_inputs(b, c, seed):
+    """Labels walk 0 .. C - 1 and the censoring state flips every C slides: from B = 2 C on every label -- 0 and C - 1 among
+    them -- occurs in both states.  B = 1 has (label, state) = (seed % C, seed // C % 2): the four variants run in turn."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    logits = torch.randn(b, c, generator=g) * 2.0
+    if b == 1:
+        return logits, torch.tensor([seed % c]), torch.tensor([float(seed // c % 2)])
+    label = torch.arange(b) % c
+    cens = ((torch.arange(b) // c) % 2).float()
+    for lab in (0, c - 1):
+        assert {float(v) for v in cens[label == lab]} == {0.0, 1.0}
+    return logits, label, cens
+
+
+def head_variants(b, c):
+    """seeds: one for a batch, (label 0 | C - 1) x (both states) for one slide"""
+    return [9000 + 17 * b + c] if b > 1 else sorted({lab + c * st for lab in (0, c - 1) for st in (0, 1)})
+
+
+def head_fp64(logits):
+    hz = torch.sigmoid(logits)
+    return hz, torch.cumprod(1 - hz, dim=1), torch.softmax(logits, dim=1)
+
+
+def ces_fp64(hz, sv, label, cens):
+    return torch.stack([O.ces_loss(hz[i:i + 1], sv[i:i + 1], label[i:i + 1], cens[i:i + 1], eps=EPS) for i in range(hz.shape[0])])
+
+
+def sct_fp64(y, label, cens):
+    idx = torch.arange(y.shape[1])[None, :]
+    lab = label.view(-1, 1)
+    keep = torch.where(cens.view(-1, 1) != 0, idx >= lab, idx == lab)
+    return -torch.log((y * keep).sum(1) + EPS)
+
+
+def worst(a, r):
+    return float((a.detach().double().cpu() - r.detach().double()).abs().max())
+
+
+@pytest.mark.parametrize("b", E.HEAD_B)
+@pytest.mark.parametrize("c", E.HEAD_C)
+def test_survival_head_edges(dev, b, c):
+    """ops.survival_head forward and backward against fp64 torch."""
+    for seed in head_variants(b, c):
+        logits, _, _ = head_inputs(b, c, seed)
+        g = torch.Generator(device="cpu").manual_seed(seed + 1)
+        probes = [torch.randn(b, c, generator=g) for _ in range(3)]
+        lg = logits.to(dev).requires_grad_(True)
+        out = ops.survival_head(lg)
+        sum(((t * p.to(dev)).sum() for t, p in zip(out, probes))).backward()
+        lg64 = logits.double().requires_grad_(True)
+        ref = head_fp64(lg64)
+        sum(((t * p.double()).sum() for t, p in zip(ref, probes))).backward()
+        errs = [worst(t, r) for t, r in zip(out, ref)]
+        e_g = H.grad_errs([lg.grad], [lg64.grad])[0]
+        print(f"[tail edges] survival head B={b} C={c}: hazards {errs[0]:.1e} survs {errs[1]:.1e} Y {errs[2]:.1e} dlogits {e_g:.1e}")
+        assert max(errs) < HEAD_ABS, errs
+        assert e_g < H.GRAD_TOL, e_g
+
+
+@pytest.mark.parametrize("b", E.HEAD_B)
+@pytest.mark.parametrize("c", E.HEAD_C)
+def test_ces_loss_edges(dev, b, c):
+    """ops.ces_loss on given hazards / survs (the values the fp64 reference reads too), per-slide and broadcast upstream gradient."""
+    for seed in head_variants(b, c):
+        _, label, cens = head_inputs(b, c, seed)
+        g = torch.Generator(device="cpu").manual_seed(seed + 2)
+        hz = torch.rand(b, c, generator=g) * 0.6 + 0.01                 # survs stay above eps at C = 16: 0.39^16 = 2.9e-7
+        sv = torch.cumprod(1 - hz, dim=1)
+        w = torch.rand(b, generator=g)
+        for weights in (w, None):
+            hz_o, sv_o = hz.double().requires_grad_(True), sv.double().requires_grad_(True)
+            per_o = ces_fp64(hz_o, sv_o, label, cens)
+            ((per_o * weights.double()).sum() if weights is not None else per_o.sum() / 8).backward()
+            hz_d, sv_d = hz.to(dev).requires_grad_(True), sv.to(dev).requires_grad_(True)
+            per_d, risk = ops.ces_loss(hz_d, sv_d, label.to(dev), cens.to(dev))
+            ((per_d * weights.to(dev)).sum() if weights is not None else per_d.sum() / 8).backward()
+            print(f"[tail edges] ces B={b} C={c}: loss {worst(per_d, per_o):.1e} risk {worst(risk, -sv.double().sum(1)):.1e} "
+                  f"d_hazards {worst(hz_d.grad, hz_o.grad):.1e} d_survs {worst(sv_d.grad, sv_o.grad):.1e}")
+            torch.testing.assert_close(per_d.double().cpu(), per_o.detach(), **CES_LOSS)
+            torch.testing.assert_close(risk.double().cpu(), -sv.double().sum(1), rtol=1e-6, atol=1e-6)
+            torch.testing.assert_close(hz_d.grad.double().cpu(), hz_o.grad, **CES_GRAD)
+            torch.testing.assert_close(sv_d.grad.double().cpu(), sv_o.grad, **CES_GRAD)
+
+
+@pytest.mark.parametrize("b", E.HEAD_B)
+@pytest.mark.parametrize("c", E.HEAD_C)
+def test_sct_loss_edges(dev, b, c):
+    """ops.sct_loss through the survival head, per-slide and broadcast upstream gradient."""
+    for seed in head_variants(b, c):
+        logits, label, cens = head_inputs(b, c, seed)
+        w = torch.rand(b, generator=torch.Generator(device="cpu").manual_seed(seed + 3)) * 0.9 + 0.1
+        for weights in (w, None):
+            lg = logits.to(dev).requires_grad_(True)
+            loss = ops.sct_loss(ops.survival_head(lg)[2], label.to(dev), cens.to(dev))
+            (loss * weights.to(dev)).sum().backward() if weights is not None else loss.sum().backward()
+            lg64 = logits.double().requires_grad_(True)
+            ref = sct_fp64(torch.softmax(lg64, dim=1), label, cens)
+            (ref * weights.double()).sum().backward() if weights is not None else ref.sum().backward()
+            print(f"[tail edges] sct B={b} C={c}: loss {worst(loss, ref):.1e} dlogits {worst(lg.grad, lg64.grad):.1e}")
+            torch.testing.assert_close(loss.double().cpu(), ref.detach(), **SCT_LOSS)
+            torch.testing.assert_close(lg.grad.double().cpu(), lg64.grad, **SCT_GRAD)
+
+
+def fused(dev, logits, label, cens, w, kind):
+    """ops.fusion_head_loss_cat on a fusion MLP that passes `logits` through (tests/test_gpu_sct_loss.py: identity-like weights,
+    zero biases, the ReLU layers see logits + 30) -> (loss, risk, hazards, survs, Y, d loss / d logits)"""
+    b, c = logits.shape
+    d = max(8, c)
+    fus = ConcatFusion(dims=[d // 2, d // 2], hidden_size=d, output_size=d).to(dev)
+    cls = nn.Linear(d, c).to(dev)
+    with torch.no_grad():
+        for lin in (fus.fusion_layer[0], fus.fusion_layer[2]):
+            lin.weight.zero_()
+            lin.weight[:c, :c] = torch.eye(c)
+            lin.bias.zero_()
+        cls.weight.zero_()
+        cls.weight[:, :c] = torch.eye(c)
+        cls.bias.fill_(-30.0)
+    hcat = torch.zeros(b, d, device=dev)
+    hcat[:, :c] = logits.to(dev) + 30.0
+    hcat.requires_grad_(True)
+    loss, risk, hz, sv, y = ops.fusion_head_loss_cat(hcat, fus, cls, label.to(dev), cens.to(dev), w, loss=kind)
+    loss.backward(w)
+    return loss, risk, hz, sv, y, hcat.grad[:, :c]
+
+
+@pytest.mark.parametrize("kind", ["ces", "sct"])
+@pytest.mark.parametrize("b", E.HEAD_B)
+@pytest.mark.parametrize("c", E.HEAD_C)
+def test_fused_head_loss_edges(dev, b, c, kind):
+    """ops.fusion_head_loss_cat, `ces` (head_loss_kernel) and `sct` (head_sct_loss_kernel): head, loss and the gradient with
+    respect to the logits in one launch, against fp64 torch / the oracle from the same logits."""
+    for seed in head_variants(b, c):
+        logits, label, cens = head_inputs(b, c, seed)
+        w = torch.full((b,), 0.125, device=dev)
+        loss, risk, hz, sv, y, dlog = fused(dev, logits, label, cens, w, kind)
+        lg64 = logits.double().requires_grad_(True)
+        hz_o, sv_o, y_o = head_fp64(lg64)
+        ref = ces_fp64(hz_o, sv_o, label, cens) if kind == "ces" else sct_fp64(y_o, label, cens)
+        ref.backward(w.double().cpu())
+        errs = [worst(t, r) for t, r in ((hz, hz_o), (sv, sv_o), (y, y_o))]
+        print(f"[tail edges] fused {kind} B={b} C={c}: loss {worst(loss, ref):.1e} dlogits {worst(dlog, lg64.grad):.1e} "
+              f"hazards {errs[0]:.1e} survs {errs[1]:.1e} Y {errs[2]:.1e}")
+        assert bool(torch.isfinite(dlog).all())
+        torch.testing.assert_close(loss.double().cpu(), ref.detach(), **FUSED_LOSS)
+        torch.testing.assert_close(dlog.double().cpu(), lg64.grad, **FUSED_GRAD)
+        torch.testing.assert_close(risk, -sv.sum(1))
+        assert max(errs) < HEAD_ABS, errs
+
+
+def test_head_entries_refuse_seventeen_classes(dev):
+    """kMaxC = 16 is the size of the per-thread arrays: every entry with such an array, or with the limit in its check, refuses
+    C = 17.  (mpo_ces_loss_* keep no per-class array and have no limit.)"""
+    c = E.HEAD_C_REFUSED
+    assert c == E.K_MAX_C + 1
+    z = torch.zeros(2, c, device=dev)
+    lab, cens, w = torch.zeros(2, dtype=torch.int64, device=dev), torch.zeros(2, device=dev), torch.ones(2, device=dev)
+    with pytest.raises(RuntimeError, match="n_classes 17"):
+        ops.survival_head(z)
+    with pytest.raises(RuntimeError, match="n_classes 17"):
+        L.call("mpo_survival_head_backward", L.ptr(z), L.ptr(z), L.ptr(z), L.ptr(z), L.ptr(z), L.ptr(z), 2, c, L.ptr(z.clone()),
+               L.stream_of(z))
+    with pytest.raises(RuntimeError, match="n_classes 17"):
+        ops.sct_loss(z, lab, cens)
+    with pytest.raises(RuntimeError, match="n_classes 17"):
+        L.call("mpo_sct_loss_backward", L.ptr(z), L.ptr(lab), L.ptr(cens), 2, c, EPS, L.ptr(w), 0, L.ptr(z.clone()), L.stream_of(z))
+    fus = ConcatFusion(dims=[16, 16], hidden_size=32, output_size=32).to(dev)
+    cls = nn.Linear(32, c).to(dev)
+    hcat = torch.zeros(2, 32, device=dev)
+    with pytest.raises(RuntimeError, match="n_classes 17"):
+        ops.fusion_head_cat(hcat, fus, cls)
+    for kind in ("ces", "sct"):
+        with pytest.raises(RuntimeError, match="classes in 1\\.\\.16"):
+            ops.fusion_head_loss_cat(hcat, fus, cls, lab, cens, w, loss=kind)
+
+
+# ---------------------------------------------------------------------------------------------------------------- CAG
+CAG_FWD, CAG_GRAD = 1e-4, 1e-3                    # test_cag_matches_golden
+CAG_NAMES = ["fc1.0.weight", "fc1.0.bias", "fc2.0.weight", "fc2.0.bias", "fc3.0.weight", "fc3.0.bias", "G.1.weight", "G.1.bias",
+             "E.1.weight", "E.1.bias", "fc_c.0.weight", "fc_c.0.bias"]
+
+
+@pytest.mark.parametrize("residual", [False, True], ids=["plain", "residual"])
+@pytest.mark.parametrize("hidden,rows", E.CAG_CASES)
+def test_cag_edges(dev, hidden, rows, residual):
+    """ops.contextual_gate (dim = hidden) against O.contextual_attention_gate in fp64: forward and all gradients."""
+    prefix = "co_attention.CAG."
+    shapes = {prefix + n: ((hidden,) if n.startswith(("G.", "E.")) or n.endswith("bias") else (hidden, hidden)) for n in CAG_NAMES}
+    sd = syn.fill_state_dict(shapes, 5000 + hidden + rows)
+    mod = ContextualAttentionGate(dim=hidden, hidden_dim=hidden)
+    mod.load_state_dict({k[len(prefix):]: v for k, v in sd.items()}, strict=True)
+    mod.to(dev)
+    g = syn.rng(5100 + hidden + rows)
+    q, qh, probe, res = (syn.normal(g, (rows, hidden)) for _ in range(4))
+    leaves = [t.to(dev).requires_grad_(True) for t in ((q, qh, res) if residual else (q, qh))]
+    out = ops.contextual_gate(leaves[0], leaves[1], mod, residual=leaves[2] if residual else None)
+    params = dict(mod.named_parameters())
+    grads = torch.autograd.grad((out * probe.to(dev)).sum(), leaves + [params[n] for n in CAG_NAMES])
+    p = {k: v.double().requires_grad_(True) for k, v in sd.items()}
+    leaves_o = [t.double().requires_grad_(True) for t in ((q, qh, res) if residual else (q, qh))]
+    out_o = O.contextual_attention_gate(leaves_o[0], leaves_o[1], p)
+    if residual:
+        out_o = out_o + leaves_o[2]
+    grads_o = torch.autograd.grad((out_o * probe.double()).sum(), leaves_o + [p[prefix + n] for n in CAG_NAMES])
+    names = ["Q", "Q_hat"] + (["residual"] if residual else []) + CAG_NAMES
+    e_out = H.relerr(out, out_o)
+    e_g = [H.relerr(a, r) for a, r in zip(grads, grads_o)]
+    k = max(range(len(e_g)), key=e_g.__getitem__)
+    print(f"[tail edges] CAG hidden={hidden} rows={rows} residual={residual}: out {e_out:.1e} grads max {e_g[k]:.1e} ({names[k]})")
+    assert bool(torch.isfinite(out).all()) and e_out < CAG_FWD, e_out
+    for n, e in zip(names, e_g):
+        assert e < CAG_GRAD, (n, e)
