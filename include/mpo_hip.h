@@ -549,6 +549,10 @@ int mpo_coattn_bwd_bagpass(const void* bag, int bag_dtype, const int32_t* cu_row
                            const float* d_attn_map /* nullable */, void* d_bag, float* part_dqk,
                            int n_q, int max_rows, const mpo_bag_plan* plan /* nullable */, mpo_stream_t stream);
 
+/* ---- fixed-budget patch sampling (csrc/bag_sample.hip): its entries are part of this ABI and are declared in the companion
+ * header beside this file, which the Python host binds from as well (additive to ABI 14). */
+#include "mpo_bag_sample.h"
+
 #ifdef __cplusplus
 }
 #endif

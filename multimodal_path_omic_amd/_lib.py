@@ -17,6 +17,8 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmpo_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mpo_hip.h")
+# Companion headers mpo_hip.h includes (entries added to the ABI after its own list was closed): bound the same way.
+COMPANION_HEADER_PATHS = [os.path.join(os.path.dirname(_HERE), "include", "mpo_bag_sample.h")]
 
 # The closed map from the header's scalar parameter types; a new scalar type in the header needs a new line here.
 _SCALARS = {"int": c_int, "int32_t": c_int, "int64_t": c_int64, "uint64_t": c_uint64, "size_t": c_size_t, "float": c_float,
@@ -76,12 +78,30 @@ def _read_header():
     return signatures, constants, version
 
 
+def _read_companions():
+    """Entry signatures of the companion headers (no enums, no version of their own)."""
+    out = {}
+    for path in COMPANION_HEADER_PATHS:
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} is missing: include/mpo_hip.h includes it and the package binds its entries")
+        with open(path) as f:
+            signatures, constants, version = parse_header(f.read())
+        if not signatures or constants or version is not None:
+            raise RuntimeError(f"{path}: a companion header declares entries only (no enum, no MPO_ABI_VERSION)")
+        for name in signatures:
+            if name in _signatures or name in out:
+                raise RuntimeError(f"{path}: {name} is declared twice")
+        out.update(signatures)
+    return out
+
+
 # Everything below is what include/mpo_hip.h says: the signatures lib() binds, its enums and the ABI version it describes.
 _signatures, _constants, ABI_VERSION = _read_header()
 MPO_F32, MPO_BF16 = _constants["MPO_F32"], _constants["MPO_BF16"]
 ACT = {k[len("MPO_ACT_"):-1].lower(): v for k, v in _constants.items() if k.startswith("MPO_ACT_")}      # MPO_ACT_RELU_ -> relu
 OPTIM = {k[len("MPO_OPTIM_"):].lower(): v for k, v in _constants.items() if k.startswith("MPO_OPTIM_")}
 GEMM_ROUTE = {k[len("MPO_GEMM_ROUTE_"):].lower(): v for k, v in _constants.items() if k.startswith("MPO_GEMM_ROUTE_")}
+_companion_signatures = _read_companions()
 
 
 class BagPlanC(ctypes.Structure):
@@ -98,6 +118,11 @@ def exported_symbols():
     return list(_signatures)
 
 
+def companion_symbols():
+    """The entries declared in the companion headers: exported and bound like the header's own."""
+    return list(_companion_signatures)
+
+
 def check_abi_version(found: int, expected: int):
     if found != expected:
         raise RuntimeError(f"{LIB_PATH} reports ABI version {found}, include/mpo_hip.h describes {expected}: the library is "
@@ -111,7 +136,7 @@ def lib():
             raise RuntimeError(
                 f"{LIB_PATH} is missing: the HIP extension has not been built ({_REBUILD}). There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _signatures.items():
+        for name, (res, args) in {**_signatures, **_companion_signatures}.items():
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

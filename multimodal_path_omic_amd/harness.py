@@ -79,11 +79,27 @@ def make_ge_window(slides: Sequence[dict], device, bag_dtype=torch.float32):
     return bags, labels
 
 
-def train_ge_window(model, bags: BagBatch, labels, grad_acc_step: int, l1: float = 0.0):
+def sample_window_rows(model, bags: BagBatch, sample_rows) -> BagBatch:
+    """The window a training step runs on under `sample_rows` (None / 0: off): in training mode min(sample_rows, M_b) rows
+    of every slide, drawn anew on every call without replacement (ops.RowSampler, eager form); in eval mode the whole
+    window, so validation sees every patch."""
+    if not sample_rows or not model.training:
+        return bags
+    from . import ops
+    x = bags.data
+    return ops.RowSampler(bags.n_slides, int(sample_rows), x.shape[1], x.dtype, x.device, static=False).bind(bags)()
+
+
+def train_ge_window(model, bags: BagBatch, labels, grad_acc_step: int, l1: float = 0.0, sample_rows: "int | None" = None):
     """Forward + backward of one window of the gene-expression model (models/ge_nacagat/main.py:24-52): the `ce` loss on Y
     in the head's launch, gradients ACCUMULATE into .grad with the reference's 1 / grad_acc_step per bag (main.py:51), no
     M x M map is allocated.  Returns the per-bag loss (B,) on the device -- no host sync.  l1: as in train_window (the
-    REPORTED loss gains l1 * sum|W|, main.py:41-43; the penalty's gradient is folded by dp.FlatOptimizer)."""
+    REPORTED loss gains l1 * sum|W|, main.py:41-43; the penalty's gradient is folded by dp.FlatOptimizer).
+    sample_rows: as in train_window; at least the model's row floor (17)."""
+    if sample_rows and sample_rows < model.MIN_WINDOW_ROWS:
+        raise ValueError(f"sample_rows {sample_rows}: the gene-expression model's window step needs at least "
+                         f"{model.MIN_WINDOW_ROWS} rows per bag")
+    bags = sample_window_rows(model, bags, sample_rows)
     w = _slide_weights(bags.n_slides, grad_acc_step, labels.device)
     _, att = model.forward_window(bags, need_maps=False, ce_targets=(labels, w))
     per_bag = att["loss"]
@@ -92,15 +108,18 @@ def train_ge_window(model, bags: BagBatch, labels, grad_acc_step: int, l1: float
 
 
 def train_window(model, bags: BagBatch, omics, labels, cens, grad_acc_step: int, loss: str = "ces", lambda_reg: float = 0.01,
-                 alpha: float = 0.75, l1: float = 0.0):
+                 alpha: float = 0.75, l1: float = 0.0, sample_rows: "int | None" = None):
     """Forward + backward of one window; gradients ACCUMULATE into .grad with the reference's
     1/grad_acc_step scaling per slide (models/mcat/main.py:69-70).  Returns (per-slide loss, risk) tensors
     on the device -- no host sync.  loss: 'ces' (models/loss.py:5-28, weight `alpha`), 'sct' (:62-85 on Y) or 'cesar'
     (:88-101: ces + lambda_reg * ||A_b||_2 of the slide's co-attention map, models/nacagat/main.py:49-50).
     l1 > 0 (training.lambda): every slide's REPORTED loss gains l1 * sum|W| over the weights the window runs with
     (models/mcat/main.py:51-54,61); the penalty's gradient is not taken here -- the flat optimiser folds it into its
-    pass (dp.FlatOptimizer(l1_lambda=l1), step(l1_slides=...))."""
+    pass (dp.FlatOptimizer(l1_lambda=l1), step(l1_slides=...)).
+    sample_rows = k (default off; beyond the reference): in training mode the step runs on k rows of every slide drawn
+    anew per call without replacement (a slide shorter than k whole); in eval mode on the whole window."""
     from . import ops
+    bags = sample_window_rows(model, bags, sample_rows)
     if loss == "cesar":
         hazards, survs, _, att = model.forward_window(bags, omics, inference=True)    # the map is an output here
         per_slide, risk = ops.ces_loss(hazards, survs, labels, cens, alpha)
@@ -231,11 +250,18 @@ class GraphedWindowStep:
     The gene-expression model takes the window (bags, labels) of make_ge_window: the body is train_ge_window (its one
     loss, `ce`), the call returns the per-bag loss alone, and split_patch_grad is refused (no data-parallel exchange is
     built for that model).
+
+    sample_rows = k lifts the one-window restriction: the captured body starts (right behind the counter bump, so that a
+    replay's sample and masks share its epoch) with the gather of ops.RowSampler -- k rows of every slide into a buffer of
+    static shape -- and everything behind it sees the same lengths, plan and grids whatever window the sampler reads.
+    bind(window) then re-points the captured step at another window of the same slide count, width and dtype with at least
+    k rows per slide; every replay draws a fresh sample (the device epoch).  bf16 windows, model in training mode.
     """
 
     def __init__(self, model, bucket, window, grad_acc_step: int, opt=None, warmup: int = 2, pool=None,
                  split_patch_grad: bool = False, prime: bool = True, loss: str = "ces", alpha: float = 0.75,
-                 lambda_reg: float = 0.01, l1: "float | None" = None, rng_base: "int | None" = None):
+                 lambda_reg: float = 0.01, l1: "float | None" = None, rng_base: "int | None" = None,
+                 sample_rows: "int | None" = None):
         """split_patch_grad (data-parallel steps, opt=None): the patch layer's weight gradient -- a 0.3 ms GEMM nobody
         downstream waits for -- is captured into a SECOND graph, `replay_tail()`.  The caller replays the main graph,
         starts the all-reduce of every other gradient (bucket.all_reduce_mean_async(lo=head)), replays the tail while
@@ -263,7 +289,16 @@ class GraphedWindowStep:
         if self.split and opt is not None:
             raise ValueError("split_patch_grad is for steps whose optimiser runs after an all-reduce (opt=None)")
         self.tail_graph = None
-        window[0].plan()                      # the work plan's H2D copy must not happen inside the capture
+        self.sampler = None
+        if sample_rows:
+            # built (output batch, its cu and work plan: H2D copies) and bound before the warm-up
+            reason = self._sampling_refusal(window[0], int(sample_rows))
+            if reason:
+                raise ValueError(f"GraphedWindowStep(sample_rows={sample_rows}): {reason}")
+            x = window[0].data
+            self.sampler = ops.RowSampler(window[0].n_slides, int(sample_rows), x.shape[1], x.dtype, x.device).bind(window[0])
+        else:
+            window[0].plan()                  # the work plan's H2D copy must not happen inside the capture
         dev = bucket.flat.device
         if ops._rng_epoch_tensor is None:
             ops.set_rng_epoch(torch.zeros(1, dtype=torch.int64, device=dev))
@@ -317,8 +352,8 @@ class GraphedWindowStep:
     def _body(self, flush: bool = True):
         from . import ops
         ops.bump_step_counters(self.epoch, self.opt.t_dev if self.opt is not None else None)   # one launch for both
+        bags = self.window[0] if self.sampler is None else self.sampler()
         self.bucket.begin()
-        bags = self.window[0]
         if self.ge:
             out = train_ge_window(self.model, bags, self.window[1], self.acc, l1=self.l1)
         else:
@@ -337,6 +372,48 @@ class GraphedWindowStep:
             else:
                 self.opt.step(bump=False)
         return out
+
+    def _sampling_refusal(self, bags, k: int) -> "str | None":
+        """Why a sampled step cannot run on `bags` (None: it can)."""
+        if bags.data.dtype == torch.float32:
+            return ("an fp32 window's feature scale is baked into the graph as a kernel argument; the sampled step is built "
+                    "for bf16 windows")
+        if not self.model.training:
+            return ("the model is in eval mode, where the whole window is passed through (validation sees every patch): "
+                    "nothing a re-pointable graph could capture")
+        if self.ge and k < self.model.MIN_WINDOW_ROWS:
+            return f"the gene-expression model's window step needs at least {self.model.MIN_WINDOW_ROWS} rows per bag"
+        return None
+
+    def bind(self, window):
+        """Re-point the captured step at `window` (same layout as the constructor's): before the next replay, ordered on
+        the current stream (the one that replays), the sampler's descriptor is rewritten (one tiny launch) and omics,
+        labels and censorship are copied into the tensors the graph reads.  No host synchronisation.  The window's rows
+        must stay valid until the replays that read them have finished.  Raises ValueError with the reason when the
+        window does not fit the capture: another slide count, a slide shorter than k, another width or dtype, fp32."""
+        if self.sampler is None:
+            raise ValueError("GraphedWindowStep.bind: the step was captured without sample_rows -- its graph reads one "
+                             "resident window's rows directly")
+        if len(window) != len(self.window):
+            raise ValueError(f"GraphedWindowStep.bind: a window of {len(window)} parts for a step captured on {len(self.window)}")
+        bags = window[0]
+        reason = self._sampling_refusal(bags, self.sampler.k)
+        if reason:
+            raise ValueError(f"GraphedWindowStep.bind: {reason}")
+        try:
+            self.sampler.check(bags)
+        except ValueError as e:
+            raise ValueError(f"GraphedWindowStep.bind: {e}") from None
+        static = self.window[1:]
+        flat_new = list(window[1]) + list(window[2:]) if not self.ge else list(window[1:])
+        flat_old = list(static[0]) + list(static[1:]) if not self.ge else list(static)
+        if len(flat_new) != len(flat_old) or any(a.shape != b.shape or a.dtype != b.dtype for a, b in zip(flat_new, flat_old)):
+            raise ValueError("GraphedWindowStep.bind: omics / labels / censorship differ in shape or dtype from the captured window's")
+        self.sampler.bind(bags)
+        for dst, src in zip(flat_old, flat_new):
+            if dst is not src:
+                dst.copy_(src, non_blocking=True)
+        self.window = (bags, *static)
 
     def head_numel(self) -> int:
         """Number of leading bucket elements that only replay_tail() writes (the patch layer's weight)."""

@@ -1326,6 +1326,87 @@ def set_rng_state(state: dict, device=None):
         set_rng_epoch(torch.full((1,), int(epoch), dtype=torch.int64, device=device))
 
 
+# ------------------------------------------------------------------------------------ fixed-budget patch sampling
+class RowSampler:
+    """k randomly chosen rows of every slide of a window, without replacement, gathered on the device into one buffer
+    (csrc/bag_sample.hip; beyond the reference, off unless asked for).  Owns the output buffer (n_slides * k, width), the
+    output BagBatch and the device-resident descriptor (base pointer + row offsets of the bound window) the gather reads at
+    run time.
+
+    static=True (what a captured step needs): every bound window must have at least k rows per slide; the output batch
+    -- lengths [k] * n_slides, its cu and its work plan -- is built HERE (both do an H2D copy, which must not happen
+    inside a capture) and is the same object for every window, so everything behind the sampler sees static shapes.
+    static=False (eager): a slide shorter than k is passed whole (k_b = min(k, M_b), in permuted order) and the output
+    batch is built per bind().
+
+    bind(bags) writes the descriptor with one tiny launch on the current stream (no host sync, no staging memory) and
+    keeps `bags` alive; the rows must stay valid until the last gather that reads the binding has finished (for a ring
+    slot of ingest.WindowFeeder: bind and run the step before requesting `depth` further windows).
+    __call__() launches the gather on the current stream and returns the output batch.  The draw is keyed by
+    (torch.initial_seed(), one offset taken with _reserve(RNG_SPAN), the device epoch): every eager call draws anew; in a
+    capture the offset is baked and the epoch (bumped inside the graph) advances the draw.  The sampler takes exactly ONE
+    value of the generator's host counter per call -- the offset is a key, not a range of counters -- so
+    GraphedWindowStep.rng_base and checkpoint.save / load see it like any other stream.  `last_stream` = (seed, offset) of
+    the most recent call, for tests/row_sampling_replay.py."""
+
+    RNG_SPAN = 0            # _reserve(0): one counter value
+
+    def __init__(self, n_slides: int, k: int, width: int, dtype, device, static: bool = True):
+        n_slides, k, width = int(n_slides), int(k), int(width)
+        if n_slides < 1 or k < 1:
+            raise ValueError(f"RowSampler: n_slides {n_slides} and k {k} must be at least 1")
+        if dtype not in (torch.bfloat16, torch.float32):
+            raise ValueError(f"RowSampler: bag dtype must be float32 or bfloat16, got {dtype}")
+        self.elem_bytes = 2 if dtype == torch.bfloat16 else 4
+        if (width * self.elem_bytes) % 16:
+            raise ValueError(f"RowSampler: a row of {width} x {self.elem_bytes} bytes is not a multiple of 16 bytes")
+        self.n_slides, self.k, self.width, self.dtype, self.static = n_slides, k, width, dtype, bool(static)
+        self.device = torch.device(device)
+        self.out = torch.empty(n_slides * k, width, dtype=dtype, device=self.device)
+        self.desc = torch.zeros(L.lib().mpo_bag_sample_desc_bytes(n_slides) // 8, dtype=torch.int64, device=self.device)
+        self.bound = None
+        self.last_stream = None
+        self.batch = None
+        if self.static:
+            self.batch = BagBatch(self.out, make_cu([k] * n_slides, self.device), [k] * n_slides)
+            self.batch.plan()
+
+    def check(self, bags: BagBatch):
+        """Raise ValueError with the reason when `bags` cannot be bound."""
+        x = bags.data
+        if bags.n_slides != self.n_slides:
+            raise ValueError(f"RowSampler: the window has {bags.n_slides} slides, the sampler was built for {self.n_slides}")
+        if x.dim() != 2 or int(x.shape[1]) != self.width:
+            raise ValueError(f"RowSampler: the window's rows are {tuple(x.shape)[1:]} wide, the sampler was built for width {self.width}")
+        if x.dtype != self.dtype:
+            raise ValueError(f"RowSampler: the window is stored as {x.dtype}, the sampler was built for {self.dtype}")
+        if self.static:
+            for b, m in enumerate(bags.lengths):
+                if m < self.k:
+                    raise ValueError(f"RowSampler: slide {b} has {m} rows, fewer than k = {self.k} (static mode neither pads "
+                                     "nor samples with replacement)")
+
+    def bind(self, bags: BagBatch):
+        self.check(bags)
+        L.call("mpo_bag_sample_bind", L.ptr(self.desc), L.ptr(bags.data), L.ptr(bags.cu), self.n_slides, self.k,
+               L.stream_of(self.desc))
+        self.bound = bags
+        if not self.static:
+            lengths = [min(self.k, int(m)) for m in bags.lengths]
+            self.batch = BagBatch(self.out[:sum(lengths)], make_cu(lengths, self.device), lengths)
+        return self
+
+    def __call__(self) -> BagBatch:
+        if self.bound is None:
+            raise RuntimeError("RowSampler: bind(bags) a window first")
+        seed, off = _reserve(self.RNG_SPAN)
+        self.last_stream = (seed, off)
+        self.batch.data.__dict__.pop("_mpo_feature_scale", None)        # (fp32: the rows are about to change under the cache)
+        L.call("mpo_bag_sample_rows", L.ptr(self.desc), self.n_slides, self.k, self.width, self.elem_bytes, seed, off,
+               _epoch(), L.ptr(self.out), L.stream_of(self.out))
+        return self.batch
+
+
 # False: the patch-side gradient of K2 as library GEMM + mpo_nacagat_patch_grad (the r02 path; kept for the small model and as
 # the cross-check of csrc/k2_patchgrad.hip in tools/gpu_diag_nacagat.py)
 k2_fused_patch_grad = True
