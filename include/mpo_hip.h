@@ -553,6 +553,9 @@ int mpo_coattn_bwd_bagpass(const void* bag, int bag_dtype, const int32_t* cu_row
  * header beside this file, which the Python host binds from as well (additive to ABI 14). */
 #include "mpo_bag_sample.h"
 
+/* ---- gated-concat fusion + head in one call each way (csrc/fusion_next.hip): likewise additive to ABI 14. */
+#include "mpo_fusion_next.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmpo_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mpo_hip.h")
 # Companion headers mpo_hip.h includes (entries added to the ABI after its own list was closed): bound the same way.
-COMPANION_HEADER_PATHS = [os.path.join(os.path.dirname(_HERE), "include", "mpo_bag_sample.h")]
+COMPANION_HEADER_PATHS = [os.path.join(os.path.dirname(_HERE), "include", name)
+                          for name in ("mpo_bag_sample.h", "mpo_fusion_next.h")]
 
 # The closed map from the header's scalar parameter types; a new scalar type in the header needs a new line here.
 _SCALARS = {"int": c_int, "int32_t": c_int, "int64_t": c_int64, "uint64_t": c_uint64, "size_t": c_size_t, "float": c_float,
@@ -79,8 +80,8 @@ def _read_header():
 
 
 def _read_companions():
-    """Entry signatures of the companion headers (no enums, no version of their own)."""
-    out = {}
+    """Entry signatures of the companion headers (no enums, no version of their own) -> (all of them, {header: its names})."""
+    out, by_header = {}, {}
     for path in COMPANION_HEADER_PATHS:
         if not os.path.exists(path):
             raise RuntimeError(f"{path} is missing: include/mpo_hip.h includes it and the package binds its entries")
@@ -92,7 +93,8 @@ def _read_companions():
             if name in _signatures or name in out:
                 raise RuntimeError(f"{path}: {name} is declared twice")
         out.update(signatures)
-    return out
+        by_header[os.path.basename(path)] = list(signatures)
+    return out, by_header
 
 
 # Everything below is what include/mpo_hip.h says: the signatures lib() binds, its enums and the ABI version it describes.
@@ -101,7 +103,7 @@ MPO_F32, MPO_BF16 = _constants["MPO_F32"], _constants["MPO_BF16"]
 ACT = {k[len("MPO_ACT_"):-1].lower(): v for k, v in _constants.items() if k.startswith("MPO_ACT_")}      # MPO_ACT_RELU_ -> relu
 OPTIM = {k[len("MPO_OPTIM_"):].lower(): v for k, v in _constants.items() if k.startswith("MPO_OPTIM_")}
 GEMM_ROUTE = {k[len("MPO_GEMM_ROUTE_"):].lower(): v for k, v in _constants.items() if k.startswith("MPO_GEMM_ROUTE_")}
-_companion_signatures = _read_companions()
+_companion_signatures, _companion_names = _read_companions()
 
 
 class BagPlanC(ctypes.Structure):
@@ -118,8 +120,14 @@ def exported_symbols():
     return list(_signatures)
 
 
-def companion_symbols():
-    """The entries declared in the companion headers: exported and bound like the header's own."""
+def companion_symbols(header: str = os.path.basename(COMPANION_HEADER_PATHS[0])):
+    """The entries declared in the companion header `header` (file name; default: the first, the patch sampler's), in
+    the order it declares them: exported and bound like mpo_hip.h's own."""
+    return list(_companion_names[header])
+
+
+def all_companion_symbols():
+    """The entries of every companion header (what lib() binds beside exported_symbols())."""
     return list(_companion_signatures)
 
 

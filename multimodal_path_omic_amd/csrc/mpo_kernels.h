@@ -282,6 +282,7 @@ int mpo_launch_pool_score_bwd(const float* dh, const float* x, const float* w, c
 int mpo_launch_pool_fwd(const float* scores, const float* x, float* w, float* h, int B, int L, int d, hipStream_t s);
 int mpo_launch_pool_bwd(const float* dh, const float* x, const float* w, const float* d_ext, float* d_scores, float* dx,
                         int B, int L, int d, hipStream_t s);
+int mpo_head_max_classes();                        // the head kernels take n_classes 1..this
 int mpo_launch_head_fwd(const float* logits, float* hazards, float* survs, float* y, int B, int C, hipStream_t s);
 int mpo_launch_head_loss(const float* logits, const long long* label, const float* cens, const float* w, float* hazards,
                          float* survs, float* y, float* loss, float* risk, float* dlogits, int B, int C, float alpha,
@@ -297,6 +298,31 @@ int mpo_launch_head_sct_loss(const float* logits, const long long* label, const 
 int mpo_launch_counters_bump(unsigned long long* epoch, int* step, hipStream_t s);
 int mpo_launch_head_bwd(const float* hazards, const float* survs, const float* y, const float* dhz, const float* dsv,
                         const float* dy, float* dlogits, int B, int C, hipStream_t s);
+// the gates of GatedConcatFusion (fusion_next.hip): hcat [B][2 d] = [x0 g0 | x1 g1], g [2 B]; x0 / x1 rows have stride ldx.
+// params / grads: gates.0.0.weight, .bias, gates.1.0.weight, .bias; t [2 B] is scratch of the backward.
+int mpo_check_gate_concat(const float* x0, const float* x1, int ldx, int n_slides, int d);      // non-zero (error set): refused
+int mpo_launch_gate_concat_fwd(const float* x0, const float* x1, int ldx, const float* const* params, float* hcat, float* g,
+                               int n_slides, int d, hipStream_t s);
+int mpo_launch_gate_concat_bwd(const float* x0, const float* x1, int ldx, const float* const* params, const float* d_hcat,
+                               const float* g, float* t, float* dx0, float* dx1, float* const* grads, int n_slides, int d,
+                               hipStream_t s);
+// BilinearFusion's kernels (fusion_next.hip); hidden 32, mm_hidden 64.  o / h / sz / gated / dz / dh: [2][B][32]; cat, dcat:
+// [B][130]; zp: [2][32][4][B]; da_part: [2][32][B][d]; dx_part: [2][128][B][d]; dropout site s starts at off + s * stride(B)
+unsigned long long mpo_bilinear_stream_stride(int n_slides);
+int mpo_check_bilinear(const float* x0, const float* x1, int ldx, int n_slides, int d, int hidden, int mm_hidden);
+int mpo_launch_bilinear_z_fwd(const float* x0, const float* x1, int ld, const float* wz0, const float* wz1, float* zp, int B, int d,
+                              hipStream_t s);
+int mpo_launch_bilinear_gate_fwd(const float* zp, const float* bz0, const float* bz1, const float* h, float* sz, float* gated, int B,
+                                 hipStream_t s);
+int mpo_launch_bilinear_gate_bwd(const float* dgated, const float* h, const float* sz, float* dz, float* dh, int B, hipStream_t s);
+int mpo_launch_bilinear_kron_fc1_fwd(const float* o, const float* W1, const float* b1, float* cat, int B, float p,
+                                     unsigned long long seed, unsigned long long off, const unsigned long long* epoch, hipStream_t s);
+int mpo_launch_bilinear_kron_fc1_bwd(const float* o, const float* W1, const float* cat, const float* dcat, float* dupre, float* d_o,
+                                     float* dW1, float* db1, int B, float p, unsigned long long seed, unsigned long long off,
+                                     const unsigned long long* epoch, hipStream_t s);
+int mpo_launch_bilinear_z_bwd(const float* x0, const float* x1, int ld, const float* wz0, const float* wz1, const float* dz,
+                              float* dwz0, float* dwz1, float* dbz0, float* dbz1, float* da_part, float* dx_part, float* dx0,
+                              float* dx1, int B, int d, hipStream_t s);
 int mpo_launch_ew_add(float* acc, const float* b, size_t n, hipStream_t s);      // acc += b
 int mpo_launch_ew_mul(const float* a, const float* b, float* out, int n, hipStream_t s);
 int mpo_launch_ew_mul2(const float* x, const float* p, const float* q, float* xp, float* xq, int n, hipStream_t s);

@@ -1026,6 +1026,7 @@ int mpo_launch_pool_bwd(const float* dh, const float* x, const float* w, const f
     MPO_LAUNCH_CHECK();
     return 0;
 }
+int mpo_head_max_classes() { return kMaxC; }
 int mpo_launch_head_fwd(const float* logits, float* hazards, float* survs, float* y, int B, int C, hipStream_t s) {
     MPO_CHECK(C >= 1 && C <= kMaxC, "survival head: n_classes %d not in 1..%d", C, kMaxC);
     head_fwd_kernel<<<(B + 63) / 64, 64, 0, s>>>(logits, hazards, survs, y, B, C);

@@ -94,6 +94,30 @@ template <class A> HeadWs head_ws(A& c, size_t B, size_t hidden, size_t dout, si
     return {c.floats(B * n_classes), c.floats(B * dout), c.floats(B * hidden)};
 }
 
+// ---- gated-concat fusion + head: the gates' state in front of K6's blocks
+// saved: hcat [B,2d] | g [2B] | K6's saved;  workspace: d_hcat [B,2d] | t [2B] | K6's workspace
+template <typename T> struct GatedHeadSaved { T *hcat, *g; HeadSaved<T> head; };
+template <class A> GatedHeadSaved<typename A::elem> gated_head_saved(A& c, size_t B, size_t d, size_t n_classes, bool with_loss) {
+    return {c.floats(B * 2 * d), c.floats(2 * B), head_saved(c, B, d, d, n_classes, with_loss)};
+}
+struct GatedHeadWs { float *d_hcat, *t; HeadWs head; };
+template <class A> GatedHeadWs gated_head_ws(A& c, size_t B, size_t d, size_t n_classes) {
+    return {c.floats(B * 2 * d), c.floats(2 * B), head_ws(c, B, d, d, n_classes)};
+}
+
+// ---- bilinear fusion + head (hidden 32, mm_hidden 64, fc2 row of 130)
+// saved: h | sz | gated | o [2,B,32 each] | zp [2,32,4,B] (the forward's own partials) | cat [B,130] | fused [B,d] | logits (| d_logits)
+template <typename T> struct BilinearSaved { T *h, *sz, *gated, *o, *zp, *cat, *fused, *logits, *dlogits; };
+template <class A> BilinearSaved<typename A::elem> bilinear_saved(A& c, size_t B, size_t d, size_t n_classes, bool with_loss) {
+    return {c.floats(2 * B * 32), c.floats(2 * B * 32), c.floats(2 * B * 32), c.floats(2 * B * 32), c.floats(2 * 32 * 4 * B),
+            c.floats(B * 130), c.floats(B * d), c.floats(B * n_classes), with_loss ? c.floats(B * n_classes) : nullptr};
+}
+struct BilinearWs { float *dlogits, *dfused, *dcat, *dupre, *d_o, *dgated, *dz, *dh, *da_part, *dx_part; };
+template <class A> BilinearWs bilinear_ws(A& c, size_t B, size_t d, size_t n_classes) {
+    return {c.floats(B * n_classes), c.floats(B * d), c.floats(B * 130), c.floats(B * 64), c.floats(2 * B * 32), c.floats(2 * B * 32),
+            c.floats(2 * B * 32), c.floats(2 * B * 32), c.floats(2 * 32 * B * d), c.floats(2 * 128 * B * d)};
+}
+
 // ---- K3 CAG
 // saved: u1 u2 u3 t1 t3 G E m  [R,h each] | stats_g [R,2] | stats_e [R,2]
 template <typename T> struct CagSaved { T *u1, *u2, *u3, *t1, *t3, *g, *e, *m, *sg, *se; };
@@ -549,6 +573,266 @@ int mpo_fusion_head_loss_backward(const float* hcat, int n_slides, int din, int 
     const HeadWs W = head_ws(ws, n_slides, hidden, dout, n_classes);
     MPO_CHECK(ws.ok(), "fusion head + loss backward: workspace too small (%zu bytes)", workspace_bytes);
     return head_mlp_backward(hcat, n_slides, din, hidden, dout, n_classes, P, S, S.dlogits, W, d_hcat, G, stream);
+}
+
+// ------------------------------------------------------------------------------------------- gated-concat fusion + head
+// (include/mpo_fusion_next.h)  params: gates.0.0.weight, .bias, gates.1.0.weight, .bias, then K6's six
+enum { kGatedHeadGateParams = 4 };
+size_t mpo_gated_concat_head_saved_floats(int n_slides, int d, int n_classes) {
+    SavedCount c;
+    gated_head_saved(c, n_slides, d, n_classes, false);
+    return c.n_floats();
+}
+size_t mpo_gated_concat_head_loss_saved_floats(int n_slides, int d, int n_classes) {
+    SavedCount c;
+    gated_head_saved(c, n_slides, d, n_classes, true);
+    return c.n_floats();
+}
+size_t mpo_gated_concat_head_workspace_bytes(int n_slides, int d, int n_classes) {
+    WsCount c;
+    gated_head_ws(c, n_slides, d, n_classes);
+    return c.workspace_bytes();
+}
+uint64_t mpo_gated_concat_head_rng_span(int, int) { return 0; }      // no dropout in this layer
+
+// what every entry refuses before its first launch
+static int gated_head_check(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int n_classes,
+                            const float* d_h_path = nullptr, const float* d_h_omic = nullptr) {
+    RC(mpo_check_gate_concat(h_path, h_omic, row_stride, n_slides, d));
+    RC(mpo_check_gate_concat(d_h_path, d_h_omic, row_stride, n_slides, d));
+    MPO_CHECK(n_classes >= 1 && n_classes <= mpo_head_max_classes(), "gated concat head: n_classes %d not in 1..%d", n_classes,
+              mpo_head_max_classes());
+    return 0;
+}
+static int gated_head_forward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int n_classes,
+                              const float* const* P, const GatedHeadSaved<float>& S, hipStream_t stream) {
+    RC(mpo_launch_gate_concat_fwd(h_path, h_omic, row_stride, P, S.hcat, S.g, n_slides, d, stream));
+    return head_mlp_forward(S.hcat, n_slides, 2 * d, d, d, n_classes, P + kGatedHeadGateParams, S.head, stream);
+}
+// from d_logits on: K6's chain down to d_hcat, then the gates
+static int gated_head_backward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int n_classes,
+                               const float* const* P, const GatedHeadSaved<const float>& S, const float* dlogits,
+                               const GatedHeadWs& W, float* d_h_path, float* d_h_omic, float* const* G, hipStream_t stream) {
+    RC(head_mlp_backward(S.hcat, n_slides, 2 * d, d, d, n_classes, P + kGatedHeadGateParams, S.head, dlogits, W.head, W.d_hcat,
+                         G + kGatedHeadGateParams, stream));
+    return mpo_launch_gate_concat_bwd(h_path, h_omic, row_stride, P, W.d_hcat, S.g, W.t, d_h_path, d_h_omic, G, n_slides, d, stream);
+}
+
+int mpo_gated_concat_head_forward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int n_classes,
+                                  const float* const* P, float* hazards, float* survs, float* y, float* saved,
+                                  mpo_stream_t stream) {
+    MPO_CHECK(h_path && h_omic && P && hazards && survs && y && saved, "gated concat head forward: null argument");
+    RC(gated_head_check(h_path, h_omic, row_stride, n_slides, d, n_classes));
+    Carve<kPad64> c(saved);
+    const GatedHeadSaved<float> S = gated_head_saved(c, n_slides, d, n_classes, false);
+    RC(gated_head_forward(h_path, h_omic, row_stride, n_slides, d, n_classes, P, S, static_cast<hipStream_t>(stream)));
+    return mpo_launch_head_fwd(S.head.logits, hazards, survs, y, n_slides, n_classes, static_cast<hipStream_t>(stream));
+}
+int mpo_gated_concat_head_backward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int n_classes,
+                                   const float* const* P, const float* saved, const float* hazards, const float* survs,
+                                   const float* y, const float* d_hazards, const float* d_survs, const float* d_y,
+                                   float* d_h_path, float* d_h_omic, float* const* G, void* workspace, size_t workspace_bytes,
+                                   mpo_stream_t stream) {
+    MPO_CHECK(h_path && h_omic && P && saved && hazards && survs && y && d_h_path && d_h_omic && G && workspace,
+              "gated concat head backward: null argument");
+    RC(gated_head_check(h_path, h_omic, row_stride, n_slides, d, n_classes, d_h_path, d_h_omic));
+    Carve<kPad64, const float> c(saved);
+    const GatedHeadSaved<const float> S = gated_head_saved(c, n_slides, d, n_classes, false);
+    WsCarve ws(workspace, workspace_bytes);
+    const GatedHeadWs W = gated_head_ws(ws, n_slides, d, n_classes);
+    MPO_CHECK(ws.ok(), "gated concat head backward: workspace too small (%zu bytes)", workspace_bytes);
+    RC(mpo_launch_head_bwd(hazards, survs, y, d_hazards, d_survs, d_y, W.head.dlogits, n_slides, n_classes,
+                           static_cast<hipStream_t>(stream)));
+    return gated_head_backward(h_path, h_omic, row_stride, n_slides, d, n_classes, P, S, W.head.dlogits, W, d_h_path, d_h_omic, G,
+                               static_cast<hipStream_t>(stream));
+}
+// Training-step form: differs from the pair above in the head launch and in where d_logits lives, nothing else.
+int mpo_gated_concat_head_loss_forward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d,
+                                       int n_classes, const float* const* P, const int64_t* label, const float* censorship,
+                                       const float* slide_weight, float alpha, float eps, int loss_kind, float* hazards,
+                                       float* survs, float* y, float* loss, float* risk, float* saved, mpo_stream_t stream) {
+    MPO_CHECK(h_path && h_omic && P && label && censorship && slide_weight && hazards && survs && y && loss && saved,
+              "gated concat head + loss forward: null argument");
+    MPO_CHECK(loss_kind == 0 || loss_kind == 1, "gated concat head + loss forward: loss_kind %d is neither 0 (ces) nor 1 (sct)", loss_kind);
+    RC(gated_head_check(h_path, h_omic, row_stride, n_slides, d, n_classes));
+    Carve<kPad64> c(saved);
+    const GatedHeadSaved<float> S = gated_head_saved(c, n_slides, d, n_classes, true);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    RC(gated_head_forward(h_path, h_omic, row_stride, n_slides, d, n_classes, P, S, s));
+    const long long* lab = reinterpret_cast<const long long*>(label);
+    if (loss_kind == 0)
+        return mpo_launch_head_loss(S.head.logits, lab, censorship, slide_weight, hazards, survs, y, loss, risk, S.head.dlogits,
+                                    n_slides, n_classes, alpha, eps, s);
+    return mpo_launch_head_sct_loss(S.head.logits, lab, censorship, slide_weight, hazards, survs, y, loss, risk, S.head.dlogits,
+                                    n_slides, n_classes, eps, s);
+}
+int mpo_gated_concat_head_loss_backward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d,
+                                        int n_classes, const float* const* P, const float* saved, float* d_h_path,
+                                        float* d_h_omic, float* const* G, void* workspace, size_t workspace_bytes,
+                                        mpo_stream_t stream) {
+    MPO_CHECK(h_path && h_omic && P && saved && d_h_path && d_h_omic && G && workspace,
+              "gated concat head + loss backward: null argument");
+    RC(gated_head_check(h_path, h_omic, row_stride, n_slides, d, n_classes, d_h_path, d_h_omic));
+    Carve<kPad64, const float> c(saved);
+    const GatedHeadSaved<const float> S = gated_head_saved(c, n_slides, d, n_classes, true);
+    WsCarve ws(workspace, workspace_bytes);
+    const GatedHeadWs W = gated_head_ws(ws, n_slides, d, n_classes);
+    MPO_CHECK(ws.ok(), "gated concat head + loss backward: workspace too small (%zu bytes)", workspace_bytes);
+    return gated_head_backward(h_path, h_omic, row_stride, n_slides, d, n_classes, P, S, S.head.dlogits, W, d_h_path, d_h_omic, G,
+                               static_cast<hipStream_t>(stream));
+}
+
+// ------------------------------------------------------------------------------------------- bilinear fusion + head
+// (include/mpo_fusion_next.h)  params: per branch linear_h.0.weight, .bias, linear_z.weight, .bias, linear_o.0.weight, .bias;
+// then fc1.0.weight, .bias, fc2.0.weight, .bias, classifier.weight, .bias
+enum { BIL_HW, BIL_HB, BIL_ZW, BIL_ZB, BIL_OW, BIL_OB, BIL_PER_BRANCH, BIL_FC1W = 12, BIL_FC1B, BIL_FC2W, BIL_FC2B, BIL_CW, BIL_CB };
+size_t mpo_bilinear_head_saved_floats(int n_slides, int d, int n_classes) {
+    SavedCount c;
+    bilinear_saved(c, n_slides, d, n_classes, false);
+    return c.n_floats();
+}
+size_t mpo_bilinear_head_loss_saved_floats(int n_slides, int d, int n_classes) {
+    SavedCount c;
+    bilinear_saved(c, n_slides, d, n_classes, true);
+    return c.n_floats();
+}
+size_t mpo_bilinear_head_workspace_bytes(int n_slides, int d, int n_classes) {
+    WsCount c;
+    bilinear_ws(c, n_slides, d, n_classes);
+    return c.workspace_bytes();
+}
+uint64_t mpo_bilinear_head_rng_span(int n_slides, int) { return 5 * mpo_bilinear_stream_stride(n_slides); }
+
+static int bilinear_check(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int hidden, int mm_hidden,
+                          int n_classes, float drop_p, const float* d_h_path = nullptr, const float* d_h_omic = nullptr) {
+    RC(mpo_check_bilinear(h_path, h_omic, row_stride, n_slides, d, hidden, mm_hidden));
+    RC(mpo_check_bilinear(d_h_path, d_h_omic, row_stride, n_slides, d, hidden, mm_hidden));
+    MPO_CHECK(n_classes >= 1 && n_classes <= mpo_head_max_classes(), "bilinear head: n_classes %d not in 1..%d", n_classes,
+              mpo_head_max_classes());
+    MPO_CHECK(drop_p >= 0.f && drop_p < 1.f, "bilinear head: dropout probability %g not in [0, 1)", (double)drop_p);
+    return 0;
+}
+struct BilinearRng { float p; uint64_t seed, off; const uint64_t* epoch; };
+static DropSpec bilinear_site(const BilinearRng& r, int n_slides, int site) {
+    return stream_of(r.p, r.seed, r.off, mpo_bilinear_stream_stride(n_slides), site, r.epoch);
+}
+static int bilinear_forward(const float* h_path, const float* h_omic, int ld, int B, int d, int C, const float* const* P,
+                            const BilinearRng& r, const BilinearSaved<float>& S, hipStream_t stream) {
+    const float* x[2] = {h_path, h_omic};
+    const size_t H = (size_t)B * 32;
+    GroupBuilder gh, go;
+    for (int br = 0; br < 2; ++br) {
+        GemmArgs m = mpo_args_fwd(x[br], P[br * BIL_PER_BRANCH + BIL_HW], P[br * BIL_PER_BRANCH + BIL_HB], S.h + br * H, B, d, 32, 1.0f, MPO_ACT_RELU);
+        m.lda = ld;
+        RC(gh.add(m));
+        RC(go.add(mpo_args_fwd(S.gated + br * H, P[br * BIL_PER_BRANCH + BIL_OW], P[br * BIL_PER_BRANCH + BIL_OB], S.o + br * H, B, 32, 32, 1.0f,
+                               MPO_ACT_RELU, nullptr, bilinear_site(r, B, br))));
+    }
+    RC(gh.launch(stream));
+    RC(mpo_launch_bilinear_z_fwd(h_path, h_omic, ld, P[BIL_ZW], P[BIL_PER_BRANCH + BIL_ZW], S.zp, B, d, stream));
+    RC(mpo_launch_bilinear_gate_fwd(S.zp, P[BIL_ZB], P[BIL_PER_BRANCH + BIL_ZB], S.h, S.sz, S.gated, B, stream));
+    RC(go.launch(stream));
+    RC(mpo_launch_bilinear_kron_fc1_fwd(S.o, P[BIL_FC1W], P[BIL_FC1B], S.cat, B, r.p, r.seed, r.off,
+                                        reinterpret_cast<const unsigned long long*>(r.epoch), stream));
+    RC(mpo_linear_fwd(S.cat, P[BIL_FC2W], P[BIL_FC2B], S.fused, B, 130, d, 1.0f, MPO_ACT_RELU, stream, nullptr, bilinear_site(r, B, 4)));
+    return mpo_linear_fwd(S.fused, P[BIL_CW], P[BIL_CB], S.logits, B, d, C, 1.0f, MPO_ACT_NONE, stream);
+}
+// from d_logits on
+static int bilinear_backward(const float* h_path, const float* h_omic, int ld, int B, int d, int C, const float* const* P,
+                             const BilinearRng& r, const BilinearSaved<const float>& S, const float* dlogits, const BilinearWs& W,
+                             float* d_h_path, float* d_h_omic, float* const* G, hipStream_t stream) {
+    const float* x[2] = {h_path, h_omic};
+    float* dx[2] = {d_h_path, d_h_omic};
+    const size_t H = (size_t)B * 32;
+    const GateSpec gf = gate(S.fused, MPO_GATE_RELU, r.p);
+    PAIR(mpo_args_bwd_input(dlogits, P[BIL_CW], W.dfused, B, d, C, 1.0f, 0),
+         mpo_args_bwd_weight(dlogits, S.fused, G[BIL_CW], G[BIL_CB], B, d, C, 1.0f));
+    PAIR(mpo_args_bwd_input(W.dfused, P[BIL_FC2W], W.dcat, B, 130, d, 1.0f, 0, gf),
+         mpo_args_bwd_weight(W.dfused, S.cat, G[BIL_FC2W], G[BIL_FC2B], B, 130, d, 1.0f, gf));
+    RC(mpo_launch_bilinear_kron_fc1_bwd(S.o, P[BIL_FC1W], S.cat, W.dcat, W.dupre, W.d_o, G[BIL_FC1W], G[BIL_FC1B], B, r.p, r.seed, r.off,
+                                        reinterpret_cast<const unsigned long long*>(r.epoch), stream));
+    GroupBuilder go, gh;
+    for (int br = 0; br < 2; ++br) {
+        const int q = br * BIL_PER_BRANCH;
+        const GateSpec g_o = gate(S.o + br * H, MPO_GATE_RELU, r.p), g_h = gate(S.h + br * H, MPO_GATE_RELU);
+        RC(go.add(mpo_args_bwd_input(W.d_o + br * H, P[q + BIL_OW], W.dgated + br * H, B, 32, 32, 1.0f, 0, g_o)));
+        RC(go.add(mpo_args_bwd_weight(W.d_o + br * H, S.gated + br * H, G[q + BIL_OW], G[q + BIL_OB], B, 32, 32, 1.0f, g_o)));
+        GemmArgs mx = mpo_args_bwd_input(W.dh + br * H, P[q + BIL_HW], dx[br], B, d, 32, 1.0f, 0, g_h);
+        mx.ldc = ld;
+        GemmArgs mw = mpo_args_bwd_weight(W.dh + br * H, x[br], G[q + BIL_HW], G[q + BIL_HB], B, d, 32, 1.0f, g_h);
+        mw.ldb = ld;
+        RC(gh.add(mx));
+        RC(gh.add(mw));
+    }
+    RC(go.launch(stream));
+    RC(mpo_launch_bilinear_gate_bwd(W.dgated, S.h, S.sz, W.dz, W.dh, B, stream));
+    RC(gh.launch(stream));
+    return mpo_launch_bilinear_z_bwd(h_path, h_omic, ld, P[BIL_ZW], P[BIL_PER_BRANCH + BIL_ZW], W.dz, G[BIL_ZW], G[BIL_PER_BRANCH + BIL_ZW],
+                                     G[BIL_ZB], G[BIL_PER_BRANCH + BIL_ZB], W.da_part, W.dx_part, d_h_path, d_h_omic, B, d, stream);
+}
+
+int mpo_bilinear_head_forward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int hidden, int mm_hidden,
+                              int n_classes, const float* const* P, float drop_p, uint64_t seed, uint64_t offset,
+                              const uint64_t* rng_epoch, float* hazards, float* survs, float* y, float* saved, mpo_stream_t stream) {
+    MPO_CHECK(h_path && h_omic && P && hazards && survs && y && saved, "bilinear head forward: null argument");
+    RC(bilinear_check(h_path, h_omic, row_stride, n_slides, d, hidden, mm_hidden, n_classes, drop_p));
+    Carve<kPad64> c(saved);
+    const BilinearSaved<float> S = bilinear_saved(c, n_slides, d, n_classes, false);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    RC(bilinear_forward(h_path, h_omic, row_stride, n_slides, d, n_classes, P, {drop_p, seed, offset, rng_epoch}, S, s));
+    return mpo_launch_head_fwd(S.logits, hazards, survs, y, n_slides, n_classes, s);
+}
+int mpo_bilinear_head_backward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int hidden, int mm_hidden,
+                               int n_classes, const float* const* P, float drop_p, uint64_t seed, uint64_t offset,
+                               const uint64_t* rng_epoch, const float* saved, const float* hazards, const float* survs, const float* y,
+                               const float* d_hazards, const float* d_survs, const float* d_y, float* d_h_path, float* d_h_omic,
+                               float* const* G, void* workspace, size_t workspace_bytes, mpo_stream_t stream) {
+    MPO_CHECK(h_path && h_omic && P && saved && hazards && survs && y && d_h_path && d_h_omic && G && workspace,
+              "bilinear head backward: null argument");
+    RC(bilinear_check(h_path, h_omic, row_stride, n_slides, d, hidden, mm_hidden, n_classes, drop_p, d_h_path, d_h_omic));
+    Carve<kPad64, const float> c(saved);
+    const BilinearSaved<const float> S = bilinear_saved(c, n_slides, d, n_classes, false);
+    WsCarve ws(workspace, workspace_bytes);
+    const BilinearWs W = bilinear_ws(ws, n_slides, d, n_classes);
+    MPO_CHECK(ws.ok(), "bilinear head backward: workspace too small (%zu bytes)", workspace_bytes);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    RC(mpo_launch_head_bwd(hazards, survs, y, d_hazards, d_survs, d_y, W.dlogits, n_slides, n_classes, s));
+    return bilinear_backward(h_path, h_omic, row_stride, n_slides, d, n_classes, P, {drop_p, seed, offset, rng_epoch}, S, W.dlogits, W,
+                             d_h_path, d_h_omic, G, s);
+}
+int mpo_bilinear_head_loss_forward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int hidden,
+                                   int mm_hidden, int n_classes, const float* const* P, float drop_p, uint64_t seed, uint64_t offset,
+                                   const uint64_t* rng_epoch, const int64_t* label, const float* censorship, const float* slide_weight,
+                                   float alpha, float eps, int loss_kind, float* hazards, float* survs, float* y, float* loss,
+                                   float* risk, float* saved, mpo_stream_t stream) {
+    MPO_CHECK(h_path && h_omic && P && label && censorship && slide_weight && hazards && survs && y && loss && saved,
+              "bilinear head + loss forward: null argument");
+    MPO_CHECK(loss_kind == 0 || loss_kind == 1, "bilinear head + loss forward: loss_kind %d is neither 0 (ces) nor 1 (sct)", loss_kind);
+    RC(bilinear_check(h_path, h_omic, row_stride, n_slides, d, hidden, mm_hidden, n_classes, drop_p));
+    Carve<kPad64> c(saved);
+    const BilinearSaved<float> S = bilinear_saved(c, n_slides, d, n_classes, true);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    RC(bilinear_forward(h_path, h_omic, row_stride, n_slides, d, n_classes, P, {drop_p, seed, offset, rng_epoch}, S, s));
+    const long long* lab = reinterpret_cast<const long long*>(label);
+    if (loss_kind == 0)
+        return mpo_launch_head_loss(S.logits, lab, censorship, slide_weight, hazards, survs, y, loss, risk, S.dlogits, n_slides,
+                                    n_classes, alpha, eps, s);
+    return mpo_launch_head_sct_loss(S.logits, lab, censorship, slide_weight, hazards, survs, y, loss, risk, S.dlogits, n_slides,
+                                    n_classes, eps, s);
+}
+int mpo_bilinear_head_loss_backward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int hidden,
+                                    int mm_hidden, int n_classes, const float* const* P, float drop_p, uint64_t seed, uint64_t offset,
+                                    const uint64_t* rng_epoch, const float* saved, float* d_h_path, float* d_h_omic, float* const* G,
+                                    void* workspace, size_t workspace_bytes, mpo_stream_t stream) {
+    MPO_CHECK(h_path && h_omic && P && saved && d_h_path && d_h_omic && G && workspace, "bilinear head + loss backward: null argument");
+    RC(bilinear_check(h_path, h_omic, row_stride, n_slides, d, hidden, mm_hidden, n_classes, drop_p, d_h_path, d_h_omic));
+    Carve<kPad64, const float> c(saved);
+    const BilinearSaved<const float> S = bilinear_saved(c, n_slides, d, n_classes, true);
+    WsCarve ws(workspace, workspace_bytes);
+    const BilinearWs W = bilinear_ws(ws, n_slides, d, n_classes);
+    MPO_CHECK(ws.ok(), "bilinear head + loss backward: workspace too small (%zu bytes)", workspace_bytes);
+    return bilinear_backward(h_path, h_omic, row_stride, n_slides, d, n_classes, P, {drop_p, seed, offset, rng_epoch}, S, S.dlogits, W,
+                             d_h_path, d_h_omic, G, static_cast<hipStream_t>(stream));
 }
 
 // ------------------------------------------------------------------------------------------- survival head alone

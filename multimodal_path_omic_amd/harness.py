@@ -125,18 +125,12 @@ def train_window(model, bags: BagBatch, omics, labels, cens, grad_acc_step: int,
         per_slide, risk = ops.ces_loss(hazards, survs, labels, cens, alpha)
         per_slide = per_slide + lambda_reg * ops.map_block_norm(att["coattn"])
     elif loss in ("ces", "sct"):
-        if getattr(model, "fusion", None) == "concat":
-            # head, loss and the backward of both in one launch: the loss gradient is known before the forward
-            w = _slide_weights(bags.n_slides, grad_acc_step, labels.device)
-            _, _, _, att = model.forward_window(bags, omics, ces_targets=(labels, cens, w), fused_loss=loss, alpha=alpha)
-            per_slide, risk = att["loss"], att["risk"]
-            per_slide.backward(w)
-            return _with_penalty(model, per_slide.detach(), l1), risk
-        hazards, survs, y, _ = model.forward_window(bags, omics)
-        if loss == "ces":
-            per_slide, risk = ops.ces_loss(hazards, survs, labels, cens, alpha)    # one HIP launch each way
-        else:
-            per_slide, risk = ops.sct_loss(y, labels, cens), risk_score(survs.detach())
+        # head, loss and the backward of both in one launch: the loss gradient is known before the forward
+        w = _slide_weights(bags.n_slides, grad_acc_step, labels.device)
+        _, _, _, att = model.forward_window(bags, omics, ces_targets=(labels, cens, w), fused_loss=loss, alpha=alpha)
+        per_slide, risk = att["loss"], att["risk"]
+        per_slide.backward(w)
+        return _with_penalty(model, per_slide.detach(), l1), risk
     elif loss == "ce":
         raise ValueError(CE_REFUSAL)
     else:

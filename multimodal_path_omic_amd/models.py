@@ -110,9 +110,10 @@ class _FusionModelBase(nn.Module):
                        fused_loss: str = "ces", alpha: float = 0.75):
         """bags: raw patch features (total_rows, 1024) of the window; omics: per group (B, d_i).
         Returns hazards, survs, Y (B, C) and {'coattn': [ (N, M_b) ] | None, 'path': (B,1,N), 'omic': (B,1,N)}.
-        ces_targets = (labels, censorship, slide_weight) (training step, fusion 'concat'): the `ces` loss and its backward
-        ride in the head's launch (ops.fusion_head_loss_cat); the dict gains 'loss' and 'risk' (per slide), and
-        backward must be driven as loss.backward(slide_weight).  fused_loss names that loss: 'ces' (weight `alpha`) or 'sct'.
+        ces_targets = (labels, censorship, slide_weight) (training step): the `ces` loss and its backward ride in the
+        head's launch (ops.fusion_head_loss_cat / gated_concat_head_loss / bilinear_head_loss); the dict gains
+        'loss' and 'risk' (per slide), and backward must be driven as loss.backward(slide_weight).  fused_loss names that
+        loss: 'ces' (weight `alpha`) or 'sct'.
 
         The path and the omic set-Transformer / pooling head have identical geometry and run as ONE launch sequence
         with grouped GEMMs (ops.encoder_stacked, ops.gated_pool_stacked): the token tail is a latency-bound chain of
@@ -124,29 +125,28 @@ class _FusionModelBase(nn.Module):
         stacked = pair.stack(h_coattn, g_tok).view(2, *h_coattn.shape) if pair is not None else torch.stack([h_coattn, g_tok])
         tokens = ops.encoder_stacked(stacked, [list(self.path_transformer.layers), list(self.omic_transformer.layers)],
                                      self.training)
-        concat = self.fusion == "concat"
+        # every fusion's head reads h as (B, [h_path | h_omic]) rows: the pooling launch writes it interleaved
         a, h = ops.gated_pool_stacked(tokens, [self.path_attention_head, self.omic_attention_head],
-                                      [self.path_rho, self.omic_rho], self.training, interleave=concat)
+                                      [self.path_rho, self.omic_rho], self.training, interleave=True)
         att = {"coattn": a_coattn, "path": a[0], "omic": a[1]}
+        fl, cl = self.fusion_layer, self.classifier
         if ces_targets is not None:
-            if not concat:
-                raise ValueError("forward_window(ces_targets=...) is built for fusion 'concat'")
-            att["loss"], att["risk"], hazards, survs, y = ops.fusion_head_loss_cat(h, self.fusion_layer, self.classifier,
-                                                                                   *ces_targets, alpha=alpha, loss=fused_loss)
+            kw = dict(alpha=alpha, loss=fused_loss)
+            if self.fusion == "concat":
+                out = ops.fusion_head_loss_cat(h, fl, cl, *ces_targets, **kw)
+            elif self.fusion == "gated_concat":
+                out = ops.gated_concat_head_loss(h, fl, cl, *ces_targets, **kw)
+            else:
+                out = ops.bilinear_head_loss(h, fl, cl, *ces_targets, self.training, **kw)
+            att["loss"], att["risk"], hazards, survs, y = out
             return hazards, survs, y, att
-        if concat:                              # h IS (B, [h_path | h_omic]): the pooling launch wrote it interleaved
-            hazards, survs, y = ops.fusion_head_cat(h, self.fusion_layer, self.classifier)
-        else:
-            hazards, survs, y = self._fuse_and_head(h[0], h[1])
-        return hazards, survs, y, att
-
-    def _fuse_and_head(self, h_path, h_omic):
-        """Fusion + classifier + survival head (models/mcat/mcat.py:119-138).  `concat` is one K6 call; the other fusion
-        layers (row f4) run their own forward, then the classifier GEMM and the HIP head."""
         if self.fusion == "concat":
-            return ops.fusion_head(h_path, h_omic, self.fusion_layer, self.classifier)
-        fused = self.fusion_layer(h_path, h_omic)
-        return ops.survival_head(ops.linear(fused, self.classifier.weight, self.classifier.bias))
+            hazards, survs, y = ops.fusion_head_cat(h, fl, cl)
+        elif self.fusion == "gated_concat":
+            hazards, survs, y = ops.gated_concat_head(h, fl, cl)
+        else:
+            hazards, survs, y = ops.bilinear_head(h, fl, cl, self.training)
+        return hazards, survs, y, att
 
     def _forward_one(self, wsi, omics, inference):
         """The reference's call: wsi (1,M,1024) or (M,1024); omics list of (1,d_i) or (d_i,)."""

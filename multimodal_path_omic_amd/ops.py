@@ -272,7 +272,7 @@ def coattn_mcat(query, batch: BagBatch, in_w, in_b, out_w, out_b, need_weights: 
 # by patch_coattn_mcat / coattn_nacagat / contextual_gate) met the gradient of that query -- accumulated in place on a
 # buffer the caller's wiring owns, or on a copy (see _query_grad_buffer)
 stats = {"colsum_handoffs": 0, "qpass_in_place": 0, "qpass_copied": 0, "head_loss_ces": 0, "head_loss_sct": 0,
-         "head_loss_ce": 0}
+         "head_loss_ce": 0, "gated_concat_head": 0, "bilinear_head": 0}
 
 
 def _query_grad_buffer(d_qpass, owned: bool, query):
@@ -1241,6 +1241,262 @@ def fusion_head_loss_cat(hcat, fusion_layer, classifier, label, censorship, slid
     seq = fusion_layer.fusion_layer
     return FusionHeadLossFn.apply(hcat, label, censorship, slide_weight, alpha, eps, loss, seq[0].weight, seq[0].bias,
                                   seq[2].weight, seq[2].bias, classifier.weight, classifier.bias)
+
+
+def _head_rows(h, interleaved: bool):
+    """h: the pooled rows of the two branches as the pooling launch wrote them, (B, 2 d) rows [h_path | h_omic] when
+    `interleaved`, else (2, B, d) -> (h_omic's offset in elements, row stride, B, d).  No copy either way: a tensor of
+    another shape or a strided one is refused."""
+    if not h.is_contiguous():
+        raise ValueError("fusion head: h must be contiguous (the entries read it in place)")
+    if interleaved and h.dim() == 2 and h.shape[1] % 2 == 0:
+        b, d = h.shape[0], h.shape[1] // 2
+        return d, 2 * d, b, d
+    if not interleaved and h.dim() == 3 and h.shape[0] == 2:
+        b, d = h.shape[1], h.shape[2]
+        return b * d, d, b, d
+    raise ValueError(f"fusion head: h {tuple(h.shape)} is not {'(B, 2 d)' if interleaved else '(2, B, d)'}")
+
+
+def _gated_concat_params(fusion_layer, classifier):
+    gates, seq = fusion_layer.gates, fusion_layer.fusion_layer
+    return (gates[0][0].weight, gates[0][0].bias, gates[1][0].weight, gates[1][0].bias, seq[0].weight, seq[0].bias,
+            seq[2].weight, seq[2].bias, classifier.weight, classifier.bias)
+
+
+class GatedConcatHeadFn(torch.autograd.Function):
+    """GatedConcatFusion's gates + K6 (MLP, classifier, survival head), one C-ABI call each way (mpo_gated_concat_head_*)."""
+
+    @staticmethod
+    def forward(ctx, h, interleaved, *params):
+        lib = L.lib()
+        ctx.set_materialize_grads(False)
+        omic, ld, b, d = _head_rows(h, interleaved)
+        ctx.interleaved = interleaved
+        c = params[8].shape[0]
+        hz = torch.empty(b, c, device=h.device, dtype=torch.float32)
+        sv, y = torch.empty_like(hz), torch.empty_like(hz)
+        saved = torch.empty(lib.mpo_gated_concat_head_saved_floats(b, d, c), device=h.device, dtype=torch.float32)
+        L.call("mpo_gated_concat_head_forward", L.ptr(h), L.ptr(h) + 4 * omic, ld, b, d, c, L.ptr_array(params), L.ptr(hz),
+               L.ptr(sv), L.ptr(y), L.ptr(saved), L.stream_of(h))
+        stats["gated_concat_head"] += 1
+        ctx.save_for_backward(h, saved, hz, sv, y, *params)
+        ctx.param_refs = params
+        return hz, sv, y
+
+    @staticmethod
+    def backward(ctx, dhz, dsv, dy):
+        lib = L.lib()
+        h, saved, hz, sv, y, *params = ctx.saved_tensors
+        omic, ld, b, d = _head_rows(h, ctx.interleaved)
+        c = params[8].shape[0]
+        d_h = torch.empty_like(h)
+        grads = [grad_out(p) for p in ctx.param_refs]
+        ws = _workspace(lib.mpo_gated_concat_head_workspace_bytes(b, d, c), h.device)
+        dhz, dsv, dy = (t.contiguous() if t is not None else None for t in (dhz, dsv, dy))
+        L.call("mpo_gated_concat_head_backward",
+            L.ptr(h), L.ptr(h) + 4 * omic, ld, b, d, c, L.ptr_array(params), L.ptr(saved), L.ptr(hz), L.ptr(sv), L.ptr(y),
+            L.ptr(dhz), L.ptr(dsv), L.ptr(dy), L.ptr(d_h), L.ptr(d_h) + 4 * omic, L.ptr_array(grads), L.ptr(ws), ws.numel(),
+            L.stream_of(h))
+        return (d_h, None, *grads)
+
+
+def gated_concat_head(h, fusion_layer, classifier, interleaved: bool = True):
+    """h (B, 2 d) = [h_path | h_omic] (`interleaved`) or (2, B, d) -> hazards, survs, Y (B, C)   (models/fusion.py:22-41 +
+    models/mcat/mcat.py:126-138); fusion_layer: a fusion.GatedConcatFusion."""
+    return GatedConcatHeadFn.apply(h, bool(interleaved), *_gated_concat_params(fusion_layer, classifier))
+
+
+class GatedConcatHeadLossFn(torch.autograd.Function):
+    """GatedConcatHeadFn for a training step, as FusionHeadLossFn is to FusionHeadFn: head, `ces` / `sct` loss and the
+    backward of both in ONE launch; backward() must be driven with the `slide_weight` tensor given to forward.
+    Returns (loss (B,), risk (B,), hazards, survs, Y); only `loss` carries gradient."""
+
+    @staticmethod
+    def forward(ctx, h, interleaved, label, censorship, slide_weight, alpha, eps, kind, *params):
+        lib = L.lib()
+        ctx.set_materialize_grads(False)
+        omic, ld, b, d = _head_rows(h, interleaved)
+        ctx.interleaved = interleaved
+        c = params[8].shape[0]
+        label = label.view(-1).to(torch.int64).contiguous()
+        censorship = censorship.view(-1).to(torch.float32).contiguous()
+        if slide_weight.shape != (b,) or slide_weight.dtype != torch.float32 or not slide_weight.is_contiguous():
+            raise ValueError("gated_concat_head_loss: slide_weight must be a contiguous fp32 tensor of one value per slide")
+        dev = h.device
+        hz = torch.empty(b, c, device=dev, dtype=torch.float32)
+        sv, y = torch.empty_like(hz), torch.empty_like(hz)
+        loss = torch.empty(b, device=dev, dtype=torch.float32)
+        risk = torch.empty(b, device=dev, dtype=torch.float32)
+        saved = torch.empty(lib.mpo_gated_concat_head_loss_saved_floats(b, d, c), device=dev, dtype=torch.float32)
+        L.call("mpo_gated_concat_head_loss_forward",
+            L.ptr(h), L.ptr(h) + 4 * omic, ld, b, d, c, L.ptr_array(params), L.ptr(label), L.ptr(censorship),
+            L.ptr(slide_weight), float(alpha), float(eps), FUSED_LOSSES.index(kind), L.ptr(hz), L.ptr(sv), L.ptr(y),
+            L.ptr(loss), L.ptr(risk), L.ptr(saved), L.stream_of(h))
+        stats["head_loss_" + kind] += 1
+        stats["gated_concat_head"] += 1
+        ctx.save_for_backward(h, saved, slide_weight, *params)
+        ctx.param_refs = params
+        ctx.mark_non_differentiable(risk, hz, sv, y)
+        return loss, risk, hz, sv, y
+
+    @staticmethod
+    def backward(ctx, d_loss, *_unused):
+        lib = L.lib()
+        h, saved, slide_weight, *params = ctx.saved_tensors
+        if d_loss is None:
+            return (None,) * (8 + len(params))
+        if d_loss.data_ptr() != slide_weight.data_ptr() or d_loss.shape != slide_weight.shape:
+            raise RuntimeError("gated_concat_head_loss: backward() must be driven with the slide_weight tensor given to "
+                               "forward (the loss gradient is folded into the forward launch)")
+        omic, ld, b, d = _head_rows(h, ctx.interleaved)
+        c = params[8].shape[0]
+        d_h = torch.empty_like(h)
+        grads = [grad_out(p) for p in ctx.param_refs]
+        ws = _workspace(lib.mpo_gated_concat_head_workspace_bytes(b, d, c), h.device)
+        L.call("mpo_gated_concat_head_loss_backward",
+            L.ptr(h), L.ptr(h) + 4 * omic, ld, b, d, c, L.ptr_array(params), L.ptr(saved), L.ptr(d_h), L.ptr(d_h) + 4 * omic,
+            L.ptr_array(grads), L.ptr(ws), ws.numel(), L.stream_of(h))
+        return (d_h, None, None, None, None, None, None, None, *grads)
+
+
+def gated_concat_head_loss(h, fusion_layer, classifier, label, censorship, slide_weight, alpha: float = 0.75, eps: float = 1e-7,
+                           loss: str = "ces", interleaved: bool = True):
+    """Training-step form of gated_concat_head: -> (per-slide loss, risk, hazards, survs, Y); drive backward with
+    `slide_weight` itself.  loss: 'ces' (weight `alpha`) or 'sct' (`alpha` unused), as fusion_head_loss_cat."""
+    if loss not in FUSED_LOSSES:
+        raise ValueError(f"gated_concat_head_loss: loss '{loss}' has no fused head launch ({' | '.join(FUSED_LOSSES)})")
+    return GatedConcatHeadLossFn.apply(h, bool(interleaved), label, censorship, slide_weight, alpha, eps, loss,
+                                       *_gated_concat_params(fusion_layer, classifier))
+
+
+def _bilinear_params(fusion_layer, classifier):
+    f = fusion_layer
+    if not (f.use_bilinear and f.use_gates and f.use_skip_connection):
+        raise NotImplementedError("bilinear_head: built for BilinearFusion with gates, bilinear products and the skip connection on")
+    out = []
+    for h, z, o in ((f.linear_h1, f.linear_z1, f.linear_o1), (f.linear_h2, f.linear_z2, f.linear_o2)):
+        out += [h[0].weight, h[0].bias, z.weight, z.bias, o[0].weight, o[0].bias]
+    return (*out, f.fc1[0].weight, f.fc1[0].bias, f.fc2[0].weight, f.fc2[0].bias, classifier.weight, classifier.bias)
+
+
+def _bilinear_drop_p(fusion_layer, training: bool) -> float:
+    f = fusion_layer
+    ps = {f.linear_o1[2].p, f.linear_o2[2].p, f.post_fusion_dropout.p, f.fc1[2].p, f.fc2[2].p}
+    if len(ps) != 1:
+        raise NotImplementedError("bilinear_head: one dropout rate for the layer's five sites")
+    return float(ps.pop()) if training else 0.0
+
+
+def _bilinear_geom(h, interleaved, params):
+    omic, ld, b, d = _head_rows(h, interleaved)
+    return omic, ld, b, d, params[4].shape[0], params[12].shape[0], params[16].shape[0]     # hidden, mm_hidden, n_classes
+
+
+class BilinearHeadFn(torch.autograd.Function):
+    """BilinearFusion + classifier + survival head, one C-ABI call each way (mpo_bilinear_head_*).  Training-mode masks are
+    a function of (seed, offset + epoch * 2^40): the backward regenerates them, nothing is stored."""
+
+    @staticmethod
+    def forward(ctx, h, interleaved, drop_p, *params):
+        lib = L.lib()
+        ctx.set_materialize_grads(False)
+        omic, ld, b, d, hid, mm, c = _bilinear_geom(h, interleaved, params)
+        seed, off = _reserve(lib.mpo_bilinear_head_rng_span(b, d)) if drop_p > 0 else (0, 0)
+        hz = torch.empty(b, c, device=h.device, dtype=torch.float32)
+        sv, y = torch.empty_like(hz), torch.empty_like(hz)
+        saved = torch.empty(lib.mpo_bilinear_head_saved_floats(b, d, c), device=h.device, dtype=torch.float32)
+        L.call("mpo_bilinear_head_forward", L.ptr(h), L.ptr(h) + 4 * omic, ld, b, d, hid, mm, c, L.ptr_array(params), float(drop_p),
+               seed, off, _epoch(), L.ptr(hz), L.ptr(sv), L.ptr(y), L.ptr(saved), L.stream_of(h))
+        stats["bilinear_head"] += 1
+        ctx.save_for_backward(h, saved, hz, sv, y, *params)
+        ctx.param_refs = params
+        ctx.interleaved, ctx.rng = interleaved, (float(drop_p), seed, off)
+        return hz, sv, y
+
+    @staticmethod
+    def backward(ctx, dhz, dsv, dy):
+        lib = L.lib()
+        h, saved, hz, sv, y, *params = ctx.saved_tensors
+        omic, ld, b, d, hid, mm, c = _bilinear_geom(h, ctx.interleaved, params)
+        d_h = torch.empty_like(h)
+        grads = [grad_out(p) for p in ctx.param_refs]
+        ws = _workspace(lib.mpo_bilinear_head_workspace_bytes(b, d, c), h.device)
+        dhz, dsv, dy = (t.contiguous() if t is not None else None for t in (dhz, dsv, dy))
+        L.call("mpo_bilinear_head_backward",
+            L.ptr(h), L.ptr(h) + 4 * omic, ld, b, d, hid, mm, c, L.ptr_array(params), *ctx.rng, _epoch(), L.ptr(saved), L.ptr(hz),
+            L.ptr(sv), L.ptr(y), L.ptr(dhz), L.ptr(dsv), L.ptr(dy), L.ptr(d_h), L.ptr(d_h) + 4 * omic, L.ptr_array(grads), L.ptr(ws),
+            ws.numel(), L.stream_of(h))
+        return (d_h, None, None, *grads)
+
+
+def bilinear_head(h, fusion_layer, classifier, training: bool, interleaved: bool = True):
+    """h (B, 2 d) = [h_path | h_omic] (`interleaved`) or (2, B, d) -> hazards, survs, Y (B, C)   (models/fusion.py:44-113 +
+    models/mcat/mcat.py:126-138); fusion_layer: a fusion.BilinearFusion as the models build it."""
+    return BilinearHeadFn.apply(h, bool(interleaved), _bilinear_drop_p(fusion_layer, training),
+                                *_bilinear_params(fusion_layer, classifier))
+
+
+class BilinearHeadLossFn(torch.autograd.Function):
+    """BilinearHeadFn for a training step, as FusionHeadLossFn is to FusionHeadFn: head, `ces` / `sct` loss and the backward
+    of both in ONE launch; backward() must be driven with the `slide_weight` tensor given to forward.
+    Returns (loss (B,), risk (B,), hazards, survs, Y); only `loss` carries gradient."""
+
+    @staticmethod
+    def forward(ctx, h, interleaved, drop_p, label, censorship, slide_weight, alpha, eps, kind, *params):
+        lib = L.lib()
+        ctx.set_materialize_grads(False)
+        omic, ld, b, d, hid, mm, c = _bilinear_geom(h, interleaved, params)
+        label = label.view(-1).to(torch.int64).contiguous()
+        censorship = censorship.view(-1).to(torch.float32).contiguous()
+        if slide_weight.shape != (b,) or slide_weight.dtype != torch.float32 or not slide_weight.is_contiguous():
+            raise ValueError("bilinear_head_loss: slide_weight must be a contiguous fp32 tensor of one value per slide")
+        seed, off = _reserve(lib.mpo_bilinear_head_rng_span(b, d)) if drop_p > 0 else (0, 0)
+        dev = h.device
+        hz = torch.empty(b, c, device=dev, dtype=torch.float32)
+        sv, y = torch.empty_like(hz), torch.empty_like(hz)
+        loss = torch.empty(b, device=dev, dtype=torch.float32)
+        risk = torch.empty(b, device=dev, dtype=torch.float32)
+        saved = torch.empty(lib.mpo_bilinear_head_loss_saved_floats(b, d, c), device=dev, dtype=torch.float32)
+        L.call("mpo_bilinear_head_loss_forward",
+            L.ptr(h), L.ptr(h) + 4 * omic, ld, b, d, hid, mm, c, L.ptr_array(params), float(drop_p), seed, off, _epoch(),
+            L.ptr(label), L.ptr(censorship), L.ptr(slide_weight), float(alpha), float(eps), FUSED_LOSSES.index(kind), L.ptr(hz),
+            L.ptr(sv), L.ptr(y), L.ptr(loss), L.ptr(risk), L.ptr(saved), L.stream_of(h))
+        stats["head_loss_" + kind] += 1
+        stats["bilinear_head"] += 1
+        ctx.save_for_backward(h, saved, slide_weight, *params)
+        ctx.param_refs = params
+        ctx.interleaved, ctx.rng = interleaved, (float(drop_p), seed, off)
+        ctx.mark_non_differentiable(risk, hz, sv, y)
+        return loss, risk, hz, sv, y
+
+    @staticmethod
+    def backward(ctx, d_loss, *_unused):
+        lib = L.lib()
+        h, saved, slide_weight, *params = ctx.saved_tensors
+        if d_loss is None:
+            return (None,) * (9 + len(params))
+        if d_loss.data_ptr() != slide_weight.data_ptr() or d_loss.shape != slide_weight.shape:
+            raise RuntimeError("bilinear_head_loss: backward() must be driven with the slide_weight tensor given to forward "
+                               "(the loss gradient is folded into the forward launch)")
+        omic, ld, b, d, hid, mm, c = _bilinear_geom(h, ctx.interleaved, params)
+        d_h = torch.empty_like(h)
+        grads = [grad_out(p) for p in ctx.param_refs]
+        ws = _workspace(lib.mpo_bilinear_head_workspace_bytes(b, d, c), h.device)
+        L.call("mpo_bilinear_head_loss_backward",
+            L.ptr(h), L.ptr(h) + 4 * omic, ld, b, d, hid, mm, c, L.ptr_array(params), *ctx.rng, _epoch(), L.ptr(saved), L.ptr(d_h),
+            L.ptr(d_h) + 4 * omic, L.ptr_array(grads), L.ptr(ws), ws.numel(), L.stream_of(h))
+        return (d_h, None, None, None, None, None, None, None, None, *grads)
+
+
+def bilinear_head_loss(h, fusion_layer, classifier, label, censorship, slide_weight, training: bool, alpha: float = 0.75,
+                       eps: float = 1e-7, loss: str = "ces", interleaved: bool = True):
+    """Training-step form of bilinear_head: -> (per-slide loss, risk, hazards, survs, Y); drive backward with `slide_weight`
+    itself.  loss: 'ces' (weight `alpha`) or 'sct' (`alpha` unused), as fusion_head_loss_cat."""
+    if loss not in FUSED_LOSSES:
+        raise ValueError(f"bilinear_head_loss: loss '{loss}' has no fused head launch ({' | '.join(FUSED_LOSSES)})")
+    return BilinearHeadLossFn.apply(h, bool(interleaved), _bilinear_drop_p(fusion_layer, training), label, censorship, slide_weight,
+                                    alpha, eps, loss, *_bilinear_params(fusion_layer, classifier))
 
 
 class GeHeadLossFn(torch.autograd.Function):
