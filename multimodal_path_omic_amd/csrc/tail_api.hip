@@ -476,34 +476,28 @@ int mpo_gated_pool_backward(const float* x, int n_branches, int n_slides, int L,
     return 0;
 }
 
-// ------------------------------------------------------------------------------------------- K6 fusion + head
-// params: fusion_layer.0.weight, .bias, fusion_layer.2.weight, .bias, classifier.weight, .bias
-size_t mpo_fusion_head_saved_floats(int n_slides, int hidden, int dout, int n_classes) {
-    SavedCount c;
-    head_saved(c, n_slides, hidden, dout, n_classes, false);
-    return c.n_floats();
-}
-size_t mpo_fusion_head_loss_saved_floats(int n_slides, int hidden, int dout, int n_classes) {
-    SavedCount c;
-    head_saved(c, n_slides, hidden, dout, n_classes, true);
-    return c.n_floats();
-}
-size_t mpo_fusion_head_workspace_bytes(int n_slides, int hidden, int dout, int n_classes) {
-    WsCount c;
-    head_ws(c, n_slides, hidden, dout, n_classes);
-    return c.workspace_bytes();
-}
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------- the three fusion heads
+// K6 (concat), gated-concat and bilinear fusion, each with the classifier and the survival head behind it.  Every head has the
+// same four entries: forward, backward, and the training-step pair whose forward launch also computes the `ces` / `sct` loss and
+// d_logits (kept in `saved`), so that its backward starts at the classifier products.  The steps of the four are written once,
+// in the head_* templates below, over a description of what a fusion has of its own: geometry and row pointers, the layouts of
+// `saved` and the workspace, where the head's blocks (logits, d_logits) lie in them, what it refuses before the first launch,
+// the chain inputs -> logits and the chain d_logits -> input and parameter gradients.
+namespace {
 
 // ConcatFusion (models/fusion.py:7-19) on the concatenated [h_path | h_omic] and the classifier (models/mcat/mcat.py:126-129)
-static int head_mlp_forward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes, const float* const* P,
-                            const HeadSaved<float>& S, hipStream_t stream) {
+// params: fusion_layer.0.weight, .bias, fusion_layer.2.weight, .bias, classifier.weight, .bias
+int head_mlp_forward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes, const float* const* P,
+                     const HeadSaved<float>& S, hipStream_t stream) {
     RC(mpo_linear_fwd(hcat, P[0], P[1], S.z1, n_slides, din, hidden, 1.0f, MPO_ACT_RELU, stream));
     RC(mpo_linear_fwd(S.z1, P[2], P[3], S.z2, n_slides, hidden, dout, 1.0f, MPO_ACT_RELU, stream));
     return mpo_linear_fwd(S.z2, P[4], P[5], S.logits, n_slides, dout, n_classes, 1.0f, MPO_ACT_NONE, stream);
 }
-static int head_mlp_backward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes, const float* const* P,
-                             const HeadSaved<const float>& S, const float* dlogits, const HeadWs& W, float* d_hcat,
-                             float* const* G, hipStream_t stream) {
+int head_mlp_backward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes, const float* const* P,
+                      const HeadSaved<const float>& S, const float* dlogits, const HeadWs& W, float* d_hcat, float* const* G,
+                      hipStream_t stream) {
     PAIR(mpo_args_bwd_input(dlogits, P[4], W.dz2, n_slides, dout, n_classes, 1.0f, 0),
          mpo_args_bwd_weight(dlogits, S.z2, G[4], G[5], n_slides, dout, n_classes, 1.0f));
     PAIR(mpo_args_bwd_input(W.dz2, P[2], W.dz1, n_slides, hidden, dout, 1.0f, 0, gate(S.z2, MPO_GATE_RELU)),
@@ -512,121 +506,251 @@ static int head_mlp_backward(const float* hcat, int n_slides, int din, int hidde
          mpo_args_bwd_weight(W.dz1, hcat, G[0], G[1], n_slides, din, hidden, 1.0f, gate(S.z1, MPO_GATE_RELU)));
     return 0;
 }
+struct ConcatHead {
+    static constexpr const char* name = "fusion head";
+    int B, din, hidden, dout, C;
+    const float* hcat = nullptr;
+    float* d_hcat = nullptr;                                   // (backward entries)
+    template <class A> HeadSaved<typename A::elem> saved(A& c, bool with_loss) const { return head_saved(c, B, hidden, dout, C, with_loss); }
+    template <class A> HeadWs ws(A& c) const { return head_ws(c, B, hidden, dout, C); }
+    template <class X> static const X& head_of(const X& x) { return x; }
+    int check() const { return 0; }                            // (the GEMMs and the head launch refuse what they cannot run)
+    int to_logits(const float* const* P, const HeadSaved<float>& S, hipStream_t stream) const {
+        return head_mlp_forward(hcat, B, din, hidden, dout, C, P, S, stream);
+    }
+    int from_dlogits(const float* const* P, const HeadSaved<const float>& S, const float* dlogits, const HeadWs& W, float* const* G,
+                     hipStream_t stream) const {
+        return head_mlp_backward(hcat, B, din, hidden, dout, C, P, S, dlogits, W, d_hcat, G, stream);
+    }
+};
 
-// ... and the survival head of models/mcat/mcat.py:130-138
+// GatedConcatFusion (include/mpo_fusion_next.h)  params: gates.0.0.weight, .bias, gates.1.0.weight, .bias, then K6's six
+struct GatedConcatHead {
+    static constexpr const char* name = "gated concat head";
+    enum { kGateParams = 4 };
+    int B, d, C;
+    const float *h_path = nullptr, *h_omic = nullptr;
+    int ld = 0;
+    float *d_h_path = nullptr, *d_h_omic = nullptr;            // (backward entries)
+    template <class A> GatedHeadSaved<typename A::elem> saved(A& c, bool with_loss) const { return gated_head_saved(c, B, d, C, with_loss); }
+    template <class A> GatedHeadWs ws(A& c) const { return gated_head_ws(c, B, d, C); }
+    template <class X> static auto head_of(const X& x) -> decltype((x.head)) { return x.head; }
+    int check() const {
+        RC(mpo_check_gate_concat(h_path, h_omic, ld, B, d));
+        RC(mpo_check_gate_concat(d_h_path, d_h_omic, ld, B, d));
+        MPO_CHECK(C >= 1 && C <= mpo_head_max_classes(), "gated concat head: n_classes %d not in 1..%d", C, mpo_head_max_classes());
+        return 0;
+    }
+    int to_logits(const float* const* P, const GatedHeadSaved<float>& S, hipStream_t stream) const {
+        RC(mpo_launch_gate_concat_fwd(h_path, h_omic, ld, P, S.hcat, S.g, B, d, stream));
+        return head_mlp_forward(S.hcat, B, 2 * d, d, d, C, P + kGateParams, S.head, stream);
+    }
+    // K6's chain down to d_hcat, then the gates
+    int from_dlogits(const float* const* P, const GatedHeadSaved<const float>& S, const float* dlogits, const GatedHeadWs& W,
+                     float* const* G, hipStream_t stream) const {
+        RC(head_mlp_backward(S.hcat, B, 2 * d, d, d, C, P + kGateParams, S.head, dlogits, W.head, W.d_hcat, G + kGateParams, stream));
+        return mpo_launch_gate_concat_bwd(h_path, h_omic, ld, P, W.d_hcat, S.g, W.t, d_h_path, d_h_omic, G, B, d, stream);
+    }
+};
+
+// BilinearFusion (include/mpo_fusion_next.h)  params: per branch linear_h.0.weight, .bias, linear_z.weight, .bias,
+// linear_o.0.weight, .bias; then fc1.0.weight, .bias, fc2.0.weight, .bias, classifier.weight, .bias
+enum { BIL_HW, BIL_HB, BIL_ZW, BIL_ZB, BIL_OW, BIL_OB, BIL_PER_BRANCH, BIL_FC1W = 12, BIL_FC1B, BIL_FC2W, BIL_FC2B, BIL_CW, BIL_CB };
+struct BilinearHead {
+    static constexpr const char* name = "bilinear head";
+    int B, d, C;
+    int hidden = 32, mm_hidden = 64;
+    const float *h_path = nullptr, *h_omic = nullptr;
+    int ld = 0;
+    float p = 0.f;                                             // the five dropout sites: one rate, streams `stride` counters apart
+    uint64_t seed = 0, off = 0;
+    const uint64_t* epoch = nullptr;
+    float *d_h_path = nullptr, *d_h_omic = nullptr;            // (backward entries)
+    template <class A> BilinearSaved<typename A::elem> saved(A& c, bool with_loss) const { return bilinear_saved(c, B, d, C, with_loss); }
+    template <class A> BilinearWs ws(A& c) const { return bilinear_ws(c, B, d, C); }
+    template <class X> static const X& head_of(const X& x) { return x; }
+    int check() const {
+        RC(mpo_check_bilinear(h_path, h_omic, ld, B, d, hidden, mm_hidden));
+        RC(mpo_check_bilinear(d_h_path, d_h_omic, ld, B, d, hidden, mm_hidden));
+        MPO_CHECK(C >= 1 && C <= mpo_head_max_classes(), "bilinear head: n_classes %d not in 1..%d", C, mpo_head_max_classes());
+        MPO_CHECK(p >= 0.f && p < 1.f, "bilinear head: dropout probability %g not in [0, 1)", (double)p);
+        return 0;
+    }
+    DropSpec site(int k) const { return stream_of(p, seed, off, mpo_bilinear_stream_stride(B), k, epoch); }
+    int to_logits(const float* const* P, const BilinearSaved<float>& S, hipStream_t stream) const {
+        const float* x[2] = {h_path, h_omic};
+        const size_t H = (size_t)B * 32;
+        GroupBuilder gh, go;
+        for (int br = 0; br < 2; ++br) {
+            GemmArgs m = mpo_args_fwd(x[br], P[br * BIL_PER_BRANCH + BIL_HW], P[br * BIL_PER_BRANCH + BIL_HB], S.h + br * H, B, d, 32, 1.0f, MPO_ACT_RELU);
+            m.lda = ld;
+            RC(gh.add(m));
+            RC(go.add(mpo_args_fwd(S.gated + br * H, P[br * BIL_PER_BRANCH + BIL_OW], P[br * BIL_PER_BRANCH + BIL_OB], S.o + br * H, B, 32, 32, 1.0f,
+                                   MPO_ACT_RELU, nullptr, site(br))));
+        }
+        RC(gh.launch(stream));
+        RC(mpo_launch_bilinear_z_fwd(h_path, h_omic, ld, P[BIL_ZW], P[BIL_PER_BRANCH + BIL_ZW], S.zp, B, d, stream));
+        RC(mpo_launch_bilinear_gate_fwd(S.zp, P[BIL_ZB], P[BIL_PER_BRANCH + BIL_ZB], S.h, S.sz, S.gated, B, stream));
+        RC(go.launch(stream));
+        RC(mpo_launch_bilinear_kron_fc1_fwd(S.o, P[BIL_FC1W], P[BIL_FC1B], S.cat, B, p, seed, off,
+                                            reinterpret_cast<const unsigned long long*>(epoch), stream));
+        RC(mpo_linear_fwd(S.cat, P[BIL_FC2W], P[BIL_FC2B], S.fused, B, 130, d, 1.0f, MPO_ACT_RELU, stream, nullptr, site(4)));
+        return mpo_linear_fwd(S.fused, P[BIL_CW], P[BIL_CB], S.logits, B, d, C, 1.0f, MPO_ACT_NONE, stream);
+    }
+    int from_dlogits(const float* const* P, const BilinearSaved<const float>& S, const float* dlogits, const BilinearWs& W,
+                     float* const* G, hipStream_t stream) const {
+        const float* x[2] = {h_path, h_omic};
+        float* dx[2] = {d_h_path, d_h_omic};
+        const size_t H = (size_t)B * 32;
+        const GateSpec gf = gate(S.fused, MPO_GATE_RELU, p);
+        PAIR(mpo_args_bwd_input(dlogits, P[BIL_CW], W.dfused, B, d, C, 1.0f, 0),
+             mpo_args_bwd_weight(dlogits, S.fused, G[BIL_CW], G[BIL_CB], B, d, C, 1.0f));
+        PAIR(mpo_args_bwd_input(W.dfused, P[BIL_FC2W], W.dcat, B, 130, d, 1.0f, 0, gf),
+             mpo_args_bwd_weight(W.dfused, S.cat, G[BIL_FC2W], G[BIL_FC2B], B, 130, d, 1.0f, gf));
+        RC(mpo_launch_bilinear_kron_fc1_bwd(S.o, P[BIL_FC1W], S.cat, W.dcat, W.dupre, W.d_o, G[BIL_FC1W], G[BIL_FC1B], B, p, seed, off,
+                                            reinterpret_cast<const unsigned long long*>(epoch), stream));
+        GroupBuilder go, gh;
+        for (int br = 0; br < 2; ++br) {
+            const int q = br * BIL_PER_BRANCH;
+            const GateSpec g_o = gate(S.o + br * H, MPO_GATE_RELU, p), g_h = gate(S.h + br * H, MPO_GATE_RELU);
+            RC(go.add(mpo_args_bwd_input(W.d_o + br * H, P[q + BIL_OW], W.dgated + br * H, B, 32, 32, 1.0f, 0, g_o)));
+            RC(go.add(mpo_args_bwd_weight(W.d_o + br * H, S.gated + br * H, G[q + BIL_OW], G[q + BIL_OB], B, 32, 32, 1.0f, g_o)));
+            GemmArgs mx = mpo_args_bwd_input(W.dh + br * H, P[q + BIL_HW], dx[br], B, d, 32, 1.0f, 0, g_h);
+            mx.ldc = ld;
+            GemmArgs mw = mpo_args_bwd_weight(W.dh + br * H, x[br], G[q + BIL_HW], G[q + BIL_HB], B, d, 32, 1.0f, g_h);
+            mw.ldb = ld;
+            RC(gh.add(mx));
+            RC(gh.add(mw));
+        }
+        RC(go.launch(stream));
+        RC(mpo_launch_bilinear_gate_bwd(W.dgated, S.h, S.sz, W.dz, W.dh, B, stream));
+        RC(gh.launch(stream));
+        return mpo_launch_bilinear_z_bwd(h_path, h_omic, ld, P[BIL_ZW], P[BIL_PER_BRANCH + BIL_ZW], W.dz, G[BIL_ZW], G[BIL_PER_BRANCH + BIL_ZW],
+                                         G[BIL_ZB], G[BIL_PER_BRANCH + BIL_ZB], W.da_part, W.dx_part, d_h_path, d_h_omic, B, d, stream);
+    }
+};
+
+// ---- the four entries of a head F
+// inputs -> logits, then the survival head of models/mcat/mcat.py:130-138
+template <class F> int head_forward(const F& f, const float* const* P, float* hazards, float* survs, float* y, float* saved,
+                                    hipStream_t stream) {
+    RC(f.check());
+    Carve<kPad64> c(saved);
+    const auto S = f.saved(c, false);
+    RC(f.to_logits(P, S, stream));
+    return mpo_launch_head_fwd(F::head_of(S).logits, hazards, survs, y, f.B, f.C, stream);
+}
+template <class F> int head_backward(const F& f, const float* const* P, const float* saved, const float* hazards, const float* survs,
+                                     const float* y, const float* d_hazards, const float* d_survs, const float* d_y, float* const* G,
+                                     void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    RC(f.check());
+    Carve<kPad64, const float> c(saved);
+    const auto S = f.saved(c, false);
+    WsCarve ws(workspace, workspace_bytes);
+    const auto W = f.ws(ws);
+    MPO_CHECK(ws.ok(), "%s backward: workspace too small (%zu bytes)", F::name, workspace_bytes);
+    float* dlogits = F::head_of(W).dlogits;
+    RC(mpo_launch_head_bwd(hazards, survs, y, d_hazards, d_survs, d_y, dlogits, f.B, f.C, stream));
+    return f.from_dlogits(P, S, dlogits, W, G, stream);
+}
+// Training-step form: differs from the pair above in the head launch -- head, loss (loss_kind 0: `ces`, head_loss_kernel; 1: `sct`,
+// head_sct_loss_kernel) and the backward of both in ONE launch -- and in where d_logits lives (`saved`; the workspace's block
+// stays unused), nothing else.
+template <class F> int head_loss_forward(const F& f, const float* const* P, const int64_t* label, const float* censorship,
+                                         const float* slide_weight, float alpha, float eps, int loss_kind, float* hazards, float* survs,
+                                         float* y, float* loss, float* risk, float* saved, hipStream_t stream) {
+    MPO_CHECK(loss_kind == 0 || loss_kind == 1, "%s + loss forward: loss_kind %d is neither 0 (ces) nor 1 (sct)", F::name, loss_kind);
+    RC(f.check());
+    Carve<kPad64> c(saved);
+    const auto S = f.saved(c, true);
+    RC(f.to_logits(P, S, stream));
+    const auto& H = F::head_of(S);
+    const long long* lab = reinterpret_cast<const long long*>(label);
+    if (loss_kind == 0)
+        return mpo_launch_head_loss(H.logits, lab, censorship, slide_weight, hazards, survs, y, loss, risk, H.dlogits, f.B, f.C, alpha,
+                                    eps, stream);
+    return mpo_launch_head_sct_loss(H.logits, lab, censorship, slide_weight, hazards, survs, y, loss, risk, H.dlogits, f.B, f.C, eps,
+                                    stream);
+}
+template <class F> int head_loss_backward(const F& f, const float* const* P, const float* saved, float* const* G, void* workspace,
+                                          size_t workspace_bytes, hipStream_t stream) {
+    RC(f.check());
+    Carve<kPad64, const float> c(saved);
+    const auto S = f.saved(c, true);
+    WsCarve ws(workspace, workspace_bytes);
+    const auto W = f.ws(ws);
+    MPO_CHECK(ws.ok(), "%s + loss backward: workspace too small (%zu bytes)", F::name, workspace_bytes);
+    return f.from_dlogits(P, S, F::head_of(S).dlogits, W, G, stream);
+}
+// the size queries: `saved` of the plain pair, `saved` of the training-step pair, the workspace of either backward
+enum HeadBuffer { kHeadSaved, kHeadLossSaved, kHeadWorkspace };
+template <class F> size_t head_size(const F& f, HeadBuffer which) {
+    if (which == kHeadWorkspace) { WsCount c; f.ws(c); return c.workspace_bytes(); }
+    SavedCount c;
+    f.saved(c, which == kHeadLossSaved);
+    return c.n_floats();
+}
+}  // namespace
+
+extern "C" {
+
+// ---- K6: concat fusion + head
+size_t mpo_fusion_head_saved_floats(int n_slides, int hidden, int dout, int n_classes) { return head_size(ConcatHead{n_slides, 0, hidden, dout, n_classes}, kHeadSaved); }
+size_t mpo_fusion_head_loss_saved_floats(int n_slides, int hidden, int dout, int n_classes) { return head_size(ConcatHead{n_slides, 0, hidden, dout, n_classes}, kHeadLossSaved); }
+size_t mpo_fusion_head_workspace_bytes(int n_slides, int hidden, int dout, int n_classes) { return head_size(ConcatHead{n_slides, 0, hidden, dout, n_classes}, kHeadWorkspace); }
+
 int mpo_fusion_head_forward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes,
                             const float* const* P, float* hazards, float* survs, float* y, float* saved,
                             mpo_stream_t stream) {
-    Carve<kPad64> c(saved);
-    const HeadSaved<float> S = head_saved(c, n_slides, hidden, dout, n_classes, false);
-    RC(head_mlp_forward(hcat, n_slides, din, hidden, dout, n_classes, P, S, stream));
-    return mpo_launch_head_fwd(S.logits, hazards, survs, y, n_slides, n_classes, stream);
+    MPO_CHECK(hcat && P && hazards && survs && y && saved, "fusion head forward: null argument");
+    return head_forward(ConcatHead{n_slides, din, hidden, dout, n_classes, hcat}, P, hazards, survs, y, saved, stream);
 }
-
+// (the two backward entries keep answering an empty call with "workspace too small": no null check in front of that one)
 int mpo_fusion_head_backward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes,
                              const float* const* P, const float* saved, const float* hazards, const float* survs,
                              const float* y, const float* d_hazards, const float* d_survs, const float* d_y,
                              float* d_hcat, float* const* G, void* workspace, size_t workspace_bytes,
                              mpo_stream_t stream) {
-    Carve<kPad64, const float> c(saved);
-    const HeadSaved<const float> S = head_saved(c, n_slides, hidden, dout, n_classes, false);
-    WsCarve ws(workspace, workspace_bytes);
-    const HeadWs W = head_ws(ws, n_slides, hidden, dout, n_classes);
-    MPO_CHECK(ws.ok(), "fusion head backward: workspace too small (%zu bytes)", workspace_bytes);
-    RC(mpo_launch_head_bwd(hazards, survs, y, d_hazards, d_survs, d_y, W.dlogits, n_slides, n_classes, stream));
-    return head_mlp_backward(hcat, n_slides, din, hidden, dout, n_classes, P, S, W.dlogits, W, d_hcat, G, stream);
+    return head_backward(ConcatHead{n_slides, din, hidden, dout, n_classes, hcat, d_hcat}, P, saved, hazards, survs, y, d_hazards,
+                         d_survs, d_y, G, workspace, workspace_bytes, stream);
 }
-
-// Training-step form: the same MLP, then head + 'ces' loss + their backward in ONE launch (head_loss_kernel); the
-// gradient w.r.t. the logits is kept in `saved` and the backward starts at the classifier products.
 int mpo_fusion_head_loss_forward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes,
                                  const float* const* P, const int64_t* label, const float* censorship,
                                  const float* slide_weight, float alpha, float eps, float* hazards, float* survs, float* y,
                                  float* loss, float* risk, float* saved, mpo_stream_t stream) {
     MPO_CHECK(hcat && P && label && censorship && slide_weight && hazards && survs && y && loss && saved,
               "fusion head + loss forward: null argument");
-    Carve<kPad64> c(saved);
-    const HeadSaved<float> S = head_saved(c, n_slides, hidden, dout, n_classes, true);
-    RC(head_mlp_forward(hcat, n_slides, din, hidden, dout, n_classes, P, S, stream));
-    return mpo_launch_head_loss(S.logits, reinterpret_cast<const long long*>(label), censorship, slide_weight, hazards, survs, y,
-                                loss, risk, S.dlogits, n_slides, n_classes, alpha, eps, static_cast<hipStream_t>(stream));
+    return head_loss_forward(ConcatHead{n_slides, din, hidden, dout, n_classes, hcat}, P, label, censorship, slide_weight, alpha, eps,
+                             0, hazards, survs, y, loss, risk, saved, stream);
 }
-// The same with the `sct` loss (head_sct_loss_kernel); the backward is mpo_fusion_head_loss_backward unchanged.
+// The same with the `sct` loss; the backward is mpo_fusion_head_loss_backward unchanged.
 int mpo_fusion_head_sct_loss_forward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes,
                                      const float* const* P, const int64_t* label, const float* censorship,
                                      const float* slide_weight, float eps, float* hazards, float* survs, float* y,
                                      float* loss, float* risk, float* saved, mpo_stream_t stream) {
     MPO_CHECK(hcat && P && label && censorship && slide_weight && hazards && survs && y && loss && saved,
               "fusion head + sct loss forward: null argument");
-    Carve<kPad64> c(saved);
-    const HeadSaved<float> S = head_saved(c, n_slides, hidden, dout, n_classes, true);
-    RC(head_mlp_forward(hcat, n_slides, din, hidden, dout, n_classes, P, S, stream));
-    return mpo_launch_head_sct_loss(S.logits, reinterpret_cast<const long long*>(label), censorship, slide_weight, hazards, survs,
-                                    y, loss, risk, S.dlogits, n_slides, n_classes, eps, static_cast<hipStream_t>(stream));
+    return head_loss_forward(ConcatHead{n_slides, din, hidden, dout, n_classes, hcat}, P, label, censorship, slide_weight, 0.f, eps,
+                             1, hazards, survs, y, loss, risk, saved, stream);
 }
 int mpo_fusion_head_loss_backward(const float* hcat, int n_slides, int din, int hidden, int dout, int n_classes,
                                   const float* const* P, const float* saved, float* d_hcat, float* const* G,
                                   void* workspace, size_t workspace_bytes, mpo_stream_t stream) {
-    Carve<kPad64, const float> c(saved);
-    const HeadSaved<const float> S = head_saved(c, n_slides, hidden, dout, n_classes, true);
-    WsCarve ws(workspace, workspace_bytes);
-    const HeadWs W = head_ws(ws, n_slides, hidden, dout, n_classes);
-    MPO_CHECK(ws.ok(), "fusion head + loss backward: workspace too small (%zu bytes)", workspace_bytes);
-    return head_mlp_backward(hcat, n_slides, din, hidden, dout, n_classes, P, S, S.dlogits, W, d_hcat, G, stream);
+    return head_loss_backward(ConcatHead{n_slides, din, hidden, dout, n_classes, hcat, d_hcat}, P, saved, G, workspace,
+                              workspace_bytes, stream);
 }
 
-// ------------------------------------------------------------------------------------------- gated-concat fusion + head
-// (include/mpo_fusion_next.h)  params: gates.0.0.weight, .bias, gates.1.0.weight, .bias, then K6's six
-enum { kGatedHeadGateParams = 4 };
-size_t mpo_gated_concat_head_saved_floats(int n_slides, int d, int n_classes) {
-    SavedCount c;
-    gated_head_saved(c, n_slides, d, n_classes, false);
-    return c.n_floats();
-}
-size_t mpo_gated_concat_head_loss_saved_floats(int n_slides, int d, int n_classes) {
-    SavedCount c;
-    gated_head_saved(c, n_slides, d, n_classes, true);
-    return c.n_floats();
-}
-size_t mpo_gated_concat_head_workspace_bytes(int n_slides, int d, int n_classes) {
-    WsCount c;
-    gated_head_ws(c, n_slides, d, n_classes);
-    return c.workspace_bytes();
-}
+// ---- gated-concat fusion + head
+size_t mpo_gated_concat_head_saved_floats(int n_slides, int d, int n_classes) { return head_size(GatedConcatHead{n_slides, d, n_classes}, kHeadSaved); }
+size_t mpo_gated_concat_head_loss_saved_floats(int n_slides, int d, int n_classes) { return head_size(GatedConcatHead{n_slides, d, n_classes}, kHeadLossSaved); }
+size_t mpo_gated_concat_head_workspace_bytes(int n_slides, int d, int n_classes) { return head_size(GatedConcatHead{n_slides, d, n_classes}, kHeadWorkspace); }
 uint64_t mpo_gated_concat_head_rng_span(int, int) { return 0; }      // no dropout in this layer
-
-// what every entry refuses before its first launch
-static int gated_head_check(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int n_classes,
-                            const float* d_h_path = nullptr, const float* d_h_omic = nullptr) {
-    RC(mpo_check_gate_concat(h_path, h_omic, row_stride, n_slides, d));
-    RC(mpo_check_gate_concat(d_h_path, d_h_omic, row_stride, n_slides, d));
-    MPO_CHECK(n_classes >= 1 && n_classes <= mpo_head_max_classes(), "gated concat head: n_classes %d not in 1..%d", n_classes,
-              mpo_head_max_classes());
-    return 0;
-}
-static int gated_head_forward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int n_classes,
-                              const float* const* P, const GatedHeadSaved<float>& S, hipStream_t stream) {
-    RC(mpo_launch_gate_concat_fwd(h_path, h_omic, row_stride, P, S.hcat, S.g, n_slides, d, stream));
-    return head_mlp_forward(S.hcat, n_slides, 2 * d, d, d, n_classes, P + kGatedHeadGateParams, S.head, stream);
-}
-// from d_logits on: K6's chain down to d_hcat, then the gates
-static int gated_head_backward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int n_classes,
-                               const float* const* P, const GatedHeadSaved<const float>& S, const float* dlogits,
-                               const GatedHeadWs& W, float* d_h_path, float* d_h_omic, float* const* G, hipStream_t stream) {
-    RC(head_mlp_backward(S.hcat, n_slides, 2 * d, d, d, n_classes, P + kGatedHeadGateParams, S.head, dlogits, W.head, W.d_hcat,
-                         G + kGatedHeadGateParams, stream));
-    return mpo_launch_gate_concat_bwd(h_path, h_omic, row_stride, P, W.d_hcat, S.g, W.t, d_h_path, d_h_omic, G, n_slides, d, stream);
-}
 
 int mpo_gated_concat_head_forward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int n_classes,
                                   const float* const* P, float* hazards, float* survs, float* y, float* saved,
                                   mpo_stream_t stream) {
     MPO_CHECK(h_path && h_omic && P && hazards && survs && y && saved, "gated concat head forward: null argument");
-    RC(gated_head_check(h_path, h_omic, row_stride, n_slides, d, n_classes));
-    Carve<kPad64> c(saved);
-    const GatedHeadSaved<float> S = gated_head_saved(c, n_slides, d, n_classes, false);
-    RC(gated_head_forward(h_path, h_omic, row_stride, n_slides, d, n_classes, P, S, static_cast<hipStream_t>(stream)));
-    return mpo_launch_head_fwd(S.head.logits, hazards, survs, y, n_slides, n_classes, static_cast<hipStream_t>(stream));
+    return head_forward(GatedConcatHead{n_slides, d, n_classes, h_path, h_omic, row_stride}, P, hazards, survs, y, saved, stream);
 }
 int mpo_gated_concat_head_backward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int n_classes,
                                    const float* const* P, const float* saved, const float* hazards, const float* survs,
@@ -635,36 +759,17 @@ int mpo_gated_concat_head_backward(const float* h_path, const float* h_omic, int
                                    mpo_stream_t stream) {
     MPO_CHECK(h_path && h_omic && P && saved && hazards && survs && y && d_h_path && d_h_omic && G && workspace,
               "gated concat head backward: null argument");
-    RC(gated_head_check(h_path, h_omic, row_stride, n_slides, d, n_classes, d_h_path, d_h_omic));
-    Carve<kPad64, const float> c(saved);
-    const GatedHeadSaved<const float> S = gated_head_saved(c, n_slides, d, n_classes, false);
-    WsCarve ws(workspace, workspace_bytes);
-    const GatedHeadWs W = gated_head_ws(ws, n_slides, d, n_classes);
-    MPO_CHECK(ws.ok(), "gated concat head backward: workspace too small (%zu bytes)", workspace_bytes);
-    RC(mpo_launch_head_bwd(hazards, survs, y, d_hazards, d_survs, d_y, W.head.dlogits, n_slides, n_classes,
-                           static_cast<hipStream_t>(stream)));
-    return gated_head_backward(h_path, h_omic, row_stride, n_slides, d, n_classes, P, S, W.head.dlogits, W, d_h_path, d_h_omic, G,
-                               static_cast<hipStream_t>(stream));
+    return head_backward(GatedConcatHead{n_slides, d, n_classes, h_path, h_omic, row_stride, d_h_path, d_h_omic}, P, saved, hazards,
+                         survs, y, d_hazards, d_survs, d_y, G, workspace, workspace_bytes, stream);
 }
-// Training-step form: differs from the pair above in the head launch and in where d_logits lives, nothing else.
 int mpo_gated_concat_head_loss_forward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d,
                                        int n_classes, const float* const* P, const int64_t* label, const float* censorship,
                                        const float* slide_weight, float alpha, float eps, int loss_kind, float* hazards,
                                        float* survs, float* y, float* loss, float* risk, float* saved, mpo_stream_t stream) {
     MPO_CHECK(h_path && h_omic && P && label && censorship && slide_weight && hazards && survs && y && loss && saved,
               "gated concat head + loss forward: null argument");
-    MPO_CHECK(loss_kind == 0 || loss_kind == 1, "gated concat head + loss forward: loss_kind %d is neither 0 (ces) nor 1 (sct)", loss_kind);
-    RC(gated_head_check(h_path, h_omic, row_stride, n_slides, d, n_classes));
-    Carve<kPad64> c(saved);
-    const GatedHeadSaved<float> S = gated_head_saved(c, n_slides, d, n_classes, true);
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    RC(gated_head_forward(h_path, h_omic, row_stride, n_slides, d, n_classes, P, S, s));
-    const long long* lab = reinterpret_cast<const long long*>(label);
-    if (loss_kind == 0)
-        return mpo_launch_head_loss(S.head.logits, lab, censorship, slide_weight, hazards, survs, y, loss, risk, S.head.dlogits,
-                                    n_slides, n_classes, alpha, eps, s);
-    return mpo_launch_head_sct_loss(S.head.logits, lab, censorship, slide_weight, hazards, survs, y, loss, risk, S.head.dlogits,
-                                    n_slides, n_classes, eps, s);
+    return head_loss_forward(GatedConcatHead{n_slides, d, n_classes, h_path, h_omic, row_stride}, P, label, censorship, slide_weight,
+                             alpha, eps, loss_kind, hazards, survs, y, loss, risk, saved, stream);
 }
 int mpo_gated_concat_head_loss_backward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d,
                                         int n_classes, const float* const* P, const float* saved, float* d_h_path,
@@ -672,115 +777,22 @@ int mpo_gated_concat_head_loss_backward(const float* h_path, const float* h_omic
                                         mpo_stream_t stream) {
     MPO_CHECK(h_path && h_omic && P && saved && d_h_path && d_h_omic && G && workspace,
               "gated concat head + loss backward: null argument");
-    RC(gated_head_check(h_path, h_omic, row_stride, n_slides, d, n_classes, d_h_path, d_h_omic));
-    Carve<kPad64, const float> c(saved);
-    const GatedHeadSaved<const float> S = gated_head_saved(c, n_slides, d, n_classes, true);
-    WsCarve ws(workspace, workspace_bytes);
-    const GatedHeadWs W = gated_head_ws(ws, n_slides, d, n_classes);
-    MPO_CHECK(ws.ok(), "gated concat head + loss backward: workspace too small (%zu bytes)", workspace_bytes);
-    return gated_head_backward(h_path, h_omic, row_stride, n_slides, d, n_classes, P, S, S.head.dlogits, W, d_h_path, d_h_omic, G,
-                               static_cast<hipStream_t>(stream));
+    return head_loss_backward(GatedConcatHead{n_slides, d, n_classes, h_path, h_omic, row_stride, d_h_path, d_h_omic}, P, saved, G,
+                              workspace, workspace_bytes, stream);
 }
 
-// ------------------------------------------------------------------------------------------- bilinear fusion + head
-// (include/mpo_fusion_next.h)  params: per branch linear_h.0.weight, .bias, linear_z.weight, .bias, linear_o.0.weight, .bias;
-// then fc1.0.weight, .bias, fc2.0.weight, .bias, classifier.weight, .bias
-enum { BIL_HW, BIL_HB, BIL_ZW, BIL_ZB, BIL_OW, BIL_OB, BIL_PER_BRANCH, BIL_FC1W = 12, BIL_FC1B, BIL_FC2W, BIL_FC2B, BIL_CW, BIL_CB };
-size_t mpo_bilinear_head_saved_floats(int n_slides, int d, int n_classes) {
-    SavedCount c;
-    bilinear_saved(c, n_slides, d, n_classes, false);
-    return c.n_floats();
-}
-size_t mpo_bilinear_head_loss_saved_floats(int n_slides, int d, int n_classes) {
-    SavedCount c;
-    bilinear_saved(c, n_slides, d, n_classes, true);
-    return c.n_floats();
-}
-size_t mpo_bilinear_head_workspace_bytes(int n_slides, int d, int n_classes) {
-    WsCount c;
-    bilinear_ws(c, n_slides, d, n_classes);
-    return c.workspace_bytes();
-}
+// ---- bilinear fusion + head
+size_t mpo_bilinear_head_saved_floats(int n_slides, int d, int n_classes) { return head_size(BilinearHead{n_slides, d, n_classes}, kHeadSaved); }
+size_t mpo_bilinear_head_loss_saved_floats(int n_slides, int d, int n_classes) { return head_size(BilinearHead{n_slides, d, n_classes}, kHeadLossSaved); }
+size_t mpo_bilinear_head_workspace_bytes(int n_slides, int d, int n_classes) { return head_size(BilinearHead{n_slides, d, n_classes}, kHeadWorkspace); }
 uint64_t mpo_bilinear_head_rng_span(int n_slides, int) { return 5 * mpo_bilinear_stream_stride(n_slides); }
-
-static int bilinear_check(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int hidden, int mm_hidden,
-                          int n_classes, float drop_p, const float* d_h_path = nullptr, const float* d_h_omic = nullptr) {
-    RC(mpo_check_bilinear(h_path, h_omic, row_stride, n_slides, d, hidden, mm_hidden));
-    RC(mpo_check_bilinear(d_h_path, d_h_omic, row_stride, n_slides, d, hidden, mm_hidden));
-    MPO_CHECK(n_classes >= 1 && n_classes <= mpo_head_max_classes(), "bilinear head: n_classes %d not in 1..%d", n_classes,
-              mpo_head_max_classes());
-    MPO_CHECK(drop_p >= 0.f && drop_p < 1.f, "bilinear head: dropout probability %g not in [0, 1)", (double)drop_p);
-    return 0;
-}
-struct BilinearRng { float p; uint64_t seed, off; const uint64_t* epoch; };
-static DropSpec bilinear_site(const BilinearRng& r, int n_slides, int site) {
-    return stream_of(r.p, r.seed, r.off, mpo_bilinear_stream_stride(n_slides), site, r.epoch);
-}
-static int bilinear_forward(const float* h_path, const float* h_omic, int ld, int B, int d, int C, const float* const* P,
-                            const BilinearRng& r, const BilinearSaved<float>& S, hipStream_t stream) {
-    const float* x[2] = {h_path, h_omic};
-    const size_t H = (size_t)B * 32;
-    GroupBuilder gh, go;
-    for (int br = 0; br < 2; ++br) {
-        GemmArgs m = mpo_args_fwd(x[br], P[br * BIL_PER_BRANCH + BIL_HW], P[br * BIL_PER_BRANCH + BIL_HB], S.h + br * H, B, d, 32, 1.0f, MPO_ACT_RELU);
-        m.lda = ld;
-        RC(gh.add(m));
-        RC(go.add(mpo_args_fwd(S.gated + br * H, P[br * BIL_PER_BRANCH + BIL_OW], P[br * BIL_PER_BRANCH + BIL_OB], S.o + br * H, B, 32, 32, 1.0f,
-                               MPO_ACT_RELU, nullptr, bilinear_site(r, B, br))));
-    }
-    RC(gh.launch(stream));
-    RC(mpo_launch_bilinear_z_fwd(h_path, h_omic, ld, P[BIL_ZW], P[BIL_PER_BRANCH + BIL_ZW], S.zp, B, d, stream));
-    RC(mpo_launch_bilinear_gate_fwd(S.zp, P[BIL_ZB], P[BIL_PER_BRANCH + BIL_ZB], S.h, S.sz, S.gated, B, stream));
-    RC(go.launch(stream));
-    RC(mpo_launch_bilinear_kron_fc1_fwd(S.o, P[BIL_FC1W], P[BIL_FC1B], S.cat, B, r.p, r.seed, r.off,
-                                        reinterpret_cast<const unsigned long long*>(r.epoch), stream));
-    RC(mpo_linear_fwd(S.cat, P[BIL_FC2W], P[BIL_FC2B], S.fused, B, 130, d, 1.0f, MPO_ACT_RELU, stream, nullptr, bilinear_site(r, B, 4)));
-    return mpo_linear_fwd(S.fused, P[BIL_CW], P[BIL_CB], S.logits, B, d, C, 1.0f, MPO_ACT_NONE, stream);
-}
-// from d_logits on
-static int bilinear_backward(const float* h_path, const float* h_omic, int ld, int B, int d, int C, const float* const* P,
-                             const BilinearRng& r, const BilinearSaved<const float>& S, const float* dlogits, const BilinearWs& W,
-                             float* d_h_path, float* d_h_omic, float* const* G, hipStream_t stream) {
-    const float* x[2] = {h_path, h_omic};
-    float* dx[2] = {d_h_path, d_h_omic};
-    const size_t H = (size_t)B * 32;
-    const GateSpec gf = gate(S.fused, MPO_GATE_RELU, r.p);
-    PAIR(mpo_args_bwd_input(dlogits, P[BIL_CW], W.dfused, B, d, C, 1.0f, 0),
-         mpo_args_bwd_weight(dlogits, S.fused, G[BIL_CW], G[BIL_CB], B, d, C, 1.0f));
-    PAIR(mpo_args_bwd_input(W.dfused, P[BIL_FC2W], W.dcat, B, 130, d, 1.0f, 0, gf),
-         mpo_args_bwd_weight(W.dfused, S.cat, G[BIL_FC2W], G[BIL_FC2B], B, 130, d, 1.0f, gf));
-    RC(mpo_launch_bilinear_kron_fc1_bwd(S.o, P[BIL_FC1W], S.cat, W.dcat, W.dupre, W.d_o, G[BIL_FC1W], G[BIL_FC1B], B, r.p, r.seed, r.off,
-                                        reinterpret_cast<const unsigned long long*>(r.epoch), stream));
-    GroupBuilder go, gh;
-    for (int br = 0; br < 2; ++br) {
-        const int q = br * BIL_PER_BRANCH;
-        const GateSpec g_o = gate(S.o + br * H, MPO_GATE_RELU, r.p), g_h = gate(S.h + br * H, MPO_GATE_RELU);
-        RC(go.add(mpo_args_bwd_input(W.d_o + br * H, P[q + BIL_OW], W.dgated + br * H, B, 32, 32, 1.0f, 0, g_o)));
-        RC(go.add(mpo_args_bwd_weight(W.d_o + br * H, S.gated + br * H, G[q + BIL_OW], G[q + BIL_OB], B, 32, 32, 1.0f, g_o)));
-        GemmArgs mx = mpo_args_bwd_input(W.dh + br * H, P[q + BIL_HW], dx[br], B, d, 32, 1.0f, 0, g_h);
-        mx.ldc = ld;
-        GemmArgs mw = mpo_args_bwd_weight(W.dh + br * H, x[br], G[q + BIL_HW], G[q + BIL_HB], B, d, 32, 1.0f, g_h);
-        mw.ldb = ld;
-        RC(gh.add(mx));
-        RC(gh.add(mw));
-    }
-    RC(go.launch(stream));
-    RC(mpo_launch_bilinear_gate_bwd(W.dgated, S.h, S.sz, W.dz, W.dh, B, stream));
-    RC(gh.launch(stream));
-    return mpo_launch_bilinear_z_bwd(h_path, h_omic, ld, P[BIL_ZW], P[BIL_PER_BRANCH + BIL_ZW], W.dz, G[BIL_ZW], G[BIL_PER_BRANCH + BIL_ZW],
-                                     G[BIL_ZB], G[BIL_PER_BRANCH + BIL_ZB], W.da_part, W.dx_part, d_h_path, d_h_omic, B, d, stream);
-}
 
 int mpo_bilinear_head_forward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int hidden, int mm_hidden,
                               int n_classes, const float* const* P, float drop_p, uint64_t seed, uint64_t offset,
                               const uint64_t* rng_epoch, float* hazards, float* survs, float* y, float* saved, mpo_stream_t stream) {
     MPO_CHECK(h_path && h_omic && P && hazards && survs && y && saved, "bilinear head forward: null argument");
-    RC(bilinear_check(h_path, h_omic, row_stride, n_slides, d, hidden, mm_hidden, n_classes, drop_p));
-    Carve<kPad64> c(saved);
-    const BilinearSaved<float> S = bilinear_saved(c, n_slides, d, n_classes, false);
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    RC(bilinear_forward(h_path, h_omic, row_stride, n_slides, d, n_classes, P, {drop_p, seed, offset, rng_epoch}, S, s));
-    return mpo_launch_head_fwd(S.logits, hazards, survs, y, n_slides, n_classes, s);
+    return head_forward(BilinearHead{n_slides, d, n_classes, hidden, mm_hidden, h_path, h_omic, row_stride, drop_p, seed, offset, rng_epoch},
+                        P, hazards, survs, y, saved, stream);
 }
 int mpo_bilinear_head_backward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int hidden, int mm_hidden,
                                int n_classes, const float* const* P, float drop_p, uint64_t seed, uint64_t offset,
@@ -789,16 +801,9 @@ int mpo_bilinear_head_backward(const float* h_path, const float* h_omic, int row
                                float* const* G, void* workspace, size_t workspace_bytes, mpo_stream_t stream) {
     MPO_CHECK(h_path && h_omic && P && saved && hazards && survs && y && d_h_path && d_h_omic && G && workspace,
               "bilinear head backward: null argument");
-    RC(bilinear_check(h_path, h_omic, row_stride, n_slides, d, hidden, mm_hidden, n_classes, drop_p, d_h_path, d_h_omic));
-    Carve<kPad64, const float> c(saved);
-    const BilinearSaved<const float> S = bilinear_saved(c, n_slides, d, n_classes, false);
-    WsCarve ws(workspace, workspace_bytes);
-    const BilinearWs W = bilinear_ws(ws, n_slides, d, n_classes);
-    MPO_CHECK(ws.ok(), "bilinear head backward: workspace too small (%zu bytes)", workspace_bytes);
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    RC(mpo_launch_head_bwd(hazards, survs, y, d_hazards, d_survs, d_y, W.dlogits, n_slides, n_classes, s));
-    return bilinear_backward(h_path, h_omic, row_stride, n_slides, d, n_classes, P, {drop_p, seed, offset, rng_epoch}, S, W.dlogits, W,
-                             d_h_path, d_h_omic, G, s);
+    return head_backward(BilinearHead{n_slides, d, n_classes, hidden, mm_hidden, h_path, h_omic, row_stride, drop_p, seed, offset, rng_epoch,
+                                      d_h_path, d_h_omic},
+                         P, saved, hazards, survs, y, d_hazards, d_survs, d_y, G, workspace, workspace_bytes, stream);
 }
 int mpo_bilinear_head_loss_forward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int hidden,
                                    int mm_hidden, int n_classes, const float* const* P, float drop_p, uint64_t seed, uint64_t offset,
@@ -807,32 +812,17 @@ int mpo_bilinear_head_loss_forward(const float* h_path, const float* h_omic, int
                                    float* risk, float* saved, mpo_stream_t stream) {
     MPO_CHECK(h_path && h_omic && P && label && censorship && slide_weight && hazards && survs && y && loss && saved,
               "bilinear head + loss forward: null argument");
-    MPO_CHECK(loss_kind == 0 || loss_kind == 1, "bilinear head + loss forward: loss_kind %d is neither 0 (ces) nor 1 (sct)", loss_kind);
-    RC(bilinear_check(h_path, h_omic, row_stride, n_slides, d, hidden, mm_hidden, n_classes, drop_p));
-    Carve<kPad64> c(saved);
-    const BilinearSaved<float> S = bilinear_saved(c, n_slides, d, n_classes, true);
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    RC(bilinear_forward(h_path, h_omic, row_stride, n_slides, d, n_classes, P, {drop_p, seed, offset, rng_epoch}, S, s));
-    const long long* lab = reinterpret_cast<const long long*>(label);
-    if (loss_kind == 0)
-        return mpo_launch_head_loss(S.logits, lab, censorship, slide_weight, hazards, survs, y, loss, risk, S.dlogits, n_slides,
-                                    n_classes, alpha, eps, s);
-    return mpo_launch_head_sct_loss(S.logits, lab, censorship, slide_weight, hazards, survs, y, loss, risk, S.dlogits, n_slides,
-                                    n_classes, eps, s);
+    return head_loss_forward(BilinearHead{n_slides, d, n_classes, hidden, mm_hidden, h_path, h_omic, row_stride, drop_p, seed, offset, rng_epoch},
+                             P, label, censorship, slide_weight, alpha, eps, loss_kind, hazards, survs, y, loss, risk, saved, stream);
 }
 int mpo_bilinear_head_loss_backward(const float* h_path, const float* h_omic, int row_stride, int n_slides, int d, int hidden,
                                     int mm_hidden, int n_classes, const float* const* P, float drop_p, uint64_t seed, uint64_t offset,
                                     const uint64_t* rng_epoch, const float* saved, float* d_h_path, float* d_h_omic, float* const* G,
                                     void* workspace, size_t workspace_bytes, mpo_stream_t stream) {
     MPO_CHECK(h_path && h_omic && P && saved && d_h_path && d_h_omic && G && workspace, "bilinear head + loss backward: null argument");
-    RC(bilinear_check(h_path, h_omic, row_stride, n_slides, d, hidden, mm_hidden, n_classes, drop_p, d_h_path, d_h_omic));
-    Carve<kPad64, const float> c(saved);
-    const BilinearSaved<const float> S = bilinear_saved(c, n_slides, d, n_classes, true);
-    WsCarve ws(workspace, workspace_bytes);
-    const BilinearWs W = bilinear_ws(ws, n_slides, d, n_classes);
-    MPO_CHECK(ws.ok(), "bilinear head + loss backward: workspace too small (%zu bytes)", workspace_bytes);
-    return bilinear_backward(h_path, h_omic, row_stride, n_slides, d, n_classes, P, {drop_p, seed, offset, rng_epoch}, S, S.dlogits, W,
-                             d_h_path, d_h_omic, G, static_cast<hipStream_t>(stream));
+    return head_loss_backward(BilinearHead{n_slides, d, n_classes, hidden, mm_hidden, h_path, h_omic, row_stride, drop_p, seed, offset, rng_epoch,
+                                           d_h_path, d_h_omic},
+                              P, saved, G, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------- survival head alone

@@ -111,7 +111,7 @@ class _FusionModelBase(nn.Module):
         """bags: raw patch features (total_rows, 1024) of the window; omics: per group (B, d_i).
         Returns hazards, survs, Y (B, C) and {'coattn': [ (N, M_b) ] | None, 'path': (B,1,N), 'omic': (B,1,N)}.
         ces_targets = (labels, censorship, slide_weight) (training step): the `ces` loss and its backward ride in the
-        head's launch (ops.fusion_head_loss_cat / gated_concat_head_loss / bilinear_head_loss); the dict gains
+        head's launch (ops.head, whatever the fusion); the dict gains
         'loss' and 'risk' (per slide), and backward must be driven as loss.backward(slide_weight).  fused_loss names that
         loss: 'ces' (weight `alpha`) or 'sct'.
 
@@ -129,23 +129,10 @@ class _FusionModelBase(nn.Module):
         a, h = ops.gated_pool_stacked(tokens, [self.path_attention_head, self.omic_attention_head],
                                       [self.path_rho, self.omic_rho], self.training, interleave=True)
         att = {"coattn": a_coattn, "path": a[0], "omic": a[1]}
-        fl, cl = self.fusion_layer, self.classifier
+        out = ops.head(h, self.fusion_layer, self.classifier, self.training, ces_targets, alpha=alpha, loss=fused_loss)
         if ces_targets is not None:
-            kw = dict(alpha=alpha, loss=fused_loss)
-            if self.fusion == "concat":
-                out = ops.fusion_head_loss_cat(h, fl, cl, *ces_targets, **kw)
-            elif self.fusion == "gated_concat":
-                out = ops.gated_concat_head_loss(h, fl, cl, *ces_targets, **kw)
-            else:
-                out = ops.bilinear_head_loss(h, fl, cl, *ces_targets, self.training, **kw)
-            att["loss"], att["risk"], hazards, survs, y = out
-            return hazards, survs, y, att
-        if self.fusion == "concat":
-            hazards, survs, y = ops.fusion_head_cat(h, fl, cl)
-        elif self.fusion == "gated_concat":
-            hazards, survs, y = ops.gated_concat_head(h, fl, cl)
-        else:
-            hazards, survs, y = ops.bilinear_head(h, fl, cl, self.training)
+            att["loss"], att["risk"], *out = out
+        hazards, survs, y = out
         return hazards, survs, y, att
 
     def _forward_one(self, wsi, omics, inference):

@@ -1121,126 +1121,10 @@ def optim_step_flat(algorithm: str, params, grads, state1, state2, lr: float, lr
            float(weight_decay), float(l1), int(step), L.ptr(step_dev), L.stream_of(params))
 
 
-class FusionHeadFn(torch.autograd.Function):
-    """K6: concat-fusion MLP + classifier + survival head."""
-
-    @staticmethod
-    def forward(ctx, hcat, *params):
-        lib = L.lib()
-        ctx.set_materialize_grads(False)
-        hcat = hcat.contiguous()
-        b, din = hcat.shape
-        hidden, dout, c = params[0].shape[0], params[2].shape[0], params[4].shape[0]
-        hz = torch.empty(b, c, device=hcat.device, dtype=torch.float32)
-        sv, y = torch.empty_like(hz), torch.empty_like(hz)
-        saved = torch.empty(lib.mpo_fusion_head_saved_floats(b, hidden, dout, c), device=hcat.device, dtype=torch.float32)
-        pa = L.ptr_array(params)
-        L.call("mpo_fusion_head_forward", L.ptr(hcat), b, din, hidden, dout, c, pa, L.ptr(hz), L.ptr(sv), L.ptr(y),
-               L.ptr(saved), L.stream_of(hcat))
-        ctx.save_for_backward(hcat, saved, hz, sv, y, *params)
-        ctx.param_refs = params
-        return hz, sv, y
-
-    @staticmethod
-    def backward(ctx, dhz, dsv, dy):
-        lib = L.lib()
-        hcat, saved, hz, sv, y, *params = ctx.saved_tensors
-        b, din = hcat.shape
-        hidden, dout, c = params[0].shape[0], params[2].shape[0], params[4].shape[0]
-        d_hcat = torch.empty_like(hcat)
-        grads = [grad_out(p) for p in ctx.param_refs]
-        ws = _workspace(lib.mpo_fusion_head_workspace_bytes(b, hidden, dout, c), hcat.device)
-        pa, ga = L.ptr_array(params), L.ptr_array(grads)
-        dhz, dsv, dy = (t.contiguous() if t is not None else None for t in (dhz, dsv, dy))
-        L.call("mpo_fusion_head_backward",
-            L.ptr(hcat), b, din, hidden, dout, c, pa, L.ptr(saved), L.ptr(hz), L.ptr(sv), L.ptr(y), L.ptr(dhz), L.ptr(dsv),
-            L.ptr(dy), L.ptr(d_hcat), ga, L.ptr(ws), ws.numel(), L.stream_of(hcat))
-        return (d_hcat, *grads)
-
-
-def fusion_head(h_path, h_omic, fusion_layer, classifier):
-    """(B,d),(B,d) -> hazards, survs, Y (B, C)   (models/fusion.py:17-19 + models/mcat/mcat.py:126-138)."""
-    return fusion_head_cat(torch.cat([h_path, h_omic], dim=-1), fusion_layer, classifier)
-
-
-def fusion_head_cat(hcat, fusion_layer, classifier):
-    """hcat (B, 2d) = [h_path | h_omic] already concatenated."""
-    seq = fusion_layer.fusion_layer
-    return FusionHeadFn.apply(hcat, seq[0].weight, seq[0].bias, seq[2].weight, seq[2].bias, classifier.weight,
-                              classifier.bias)
-
-
-class FusionHeadLossFn(torch.autograd.Function):
-    """K6 + `ces` loss for a training step: ConcatFusion MLP + classifier GEMMs, then head, loss and the backward of both
-    in ONE launch.  The gradient the caller sends into the per-slide loss must be known up front: `slide_weight`
-    (B device floats; 1 / grad_acc_step in the reference's loop, models/mcat/main.py:69-70) -- backward() refuses any other
-    gradient tensor.  Returns (loss (B,), risk (B,), hazards, survs, Y); only `loss` carries gradient."""
-
-    @staticmethod
-    def forward(ctx, hcat, label, censorship, slide_weight, alpha, eps, kind, *params):
-        lib = L.lib()
-        ctx.set_materialize_grads(False)
-        hcat = hcat.contiguous()
-        b, din = hcat.shape
-        hidden, dout, c = params[0].shape[0], params[2].shape[0], params[4].shape[0]
-        label = label.view(-1).to(torch.int64).contiguous()
-        censorship = censorship.view(-1).to(torch.float32).contiguous()
-        if slide_weight.shape != (b,) or slide_weight.dtype != torch.float32 or not slide_weight.is_contiguous():
-            raise ValueError("fusion_head_loss: slide_weight must be a contiguous fp32 tensor of one value per slide")
-        dev = hcat.device
-        hz = torch.empty(b, c, device=dev, dtype=torch.float32)
-        sv, y = torch.empty_like(hz), torch.empty_like(hz)
-        loss = torch.empty(b, device=dev, dtype=torch.float32)
-        risk = torch.empty(b, device=dev, dtype=torch.float32)
-        saved = torch.empty(lib.mpo_fusion_head_loss_saved_floats(b, hidden, dout, c), device=dev, dtype=torch.float32)
-        if kind == "ces":
-            L.call("mpo_fusion_head_loss_forward",
-                L.ptr(hcat), b, din, hidden, dout, c, L.ptr_array(params), L.ptr(label), L.ptr(censorship), L.ptr(slide_weight),
-                float(alpha), float(eps), L.ptr(hz), L.ptr(sv), L.ptr(y), L.ptr(loss), L.ptr(risk), L.ptr(saved),
-                L.stream_of(hcat))
-        else:                                   # 'sct' (fusion_head_loss_cat checked the name)
-            L.call("mpo_fusion_head_sct_loss_forward",
-                L.ptr(hcat), b, din, hidden, dout, c, L.ptr_array(params), L.ptr(label), L.ptr(censorship), L.ptr(slide_weight),
-                float(eps), L.ptr(hz), L.ptr(sv), L.ptr(y), L.ptr(loss), L.ptr(risk), L.ptr(saved),
-                L.stream_of(hcat))
-        stats["head_loss_" + kind] += 1
-        ctx.save_for_backward(hcat, saved, slide_weight, *params)
-        ctx.param_refs = params
-        ctx.mark_non_differentiable(risk, hz, sv, y)
-        return loss, risk, hz, sv, y
-
-    @staticmethod
-    def backward(ctx, d_loss, *_unused):
-        lib = L.lib()
-        hcat, saved, slide_weight, *params = ctx.saved_tensors
-        if d_loss is None:
-            return (None,) * (7 + len(params))
-        if d_loss.data_ptr() != slide_weight.data_ptr() or d_loss.shape != slide_weight.shape:
-            raise RuntimeError("fusion_head_loss: backward() must be driven with the slide_weight tensor given to forward "
-                               "(the loss gradient is folded into the forward launch)")
-        b, din = hcat.shape
-        hidden, dout, c = params[0].shape[0], params[2].shape[0], params[4].shape[0]
-        d_hcat = torch.empty_like(hcat)
-        grads = [grad_out(p) for p in ctx.param_refs]
-        ws = _workspace(lib.mpo_fusion_head_workspace_bytes(b, hidden, dout, c), hcat.device)
-        L.call("mpo_fusion_head_loss_backward",
-            L.ptr(hcat), b, din, hidden, dout, c, L.ptr_array(params), L.ptr(saved), L.ptr(d_hcat), L.ptr_array(grads),
-            L.ptr(ws), ws.numel(), L.stream_of(hcat))
-        return (d_hcat, None, None, None, None, None, None, *grads)
-
-
+# ------------------------------------------------------------------------------------ fusion + classifier + survival head
+# The three fusions (K6 concat, gated-concat, bilinear) share one head protocol -- four C entries mpo_<name>_{forward, backward,
+# loss_forward, loss_backward}, csrc/tail_api.hip -- and one Python body for it: HeadFn / HeadLossFn over a _Head description.
 FUSED_LOSSES = ("ces", "sct")
-
-
-def fusion_head_loss_cat(hcat, fusion_layer, classifier, label, censorship, slide_weight, alpha: float = 0.75, eps: float = 1e-7,
-                         loss: str = "ces"):
-    """Training-step K6: -> (per-slide loss, risk, hazards, survs, Y); drive backward with `slide_weight` itself.
-    loss: 'ces' (models/loss.py:5-28, weight `alpha`) or 'sct' (models/loss.py:62-85 on Y; `alpha` unused)."""
-    if loss not in FUSED_LOSSES:
-        raise ValueError(f"fusion_head_loss_cat: loss '{loss}' has no fused head launch ({' | '.join(FUSED_LOSSES)})")
-    seq = fusion_layer.fusion_layer
-    return FusionHeadLossFn.apply(hcat, label, censorship, slide_weight, alpha, eps, loss, seq[0].weight, seq[0].bias,
-                                  seq[2].weight, seq[2].bias, classifier.weight, classifier.bias)
 
 
 def _head_rows(h, interleaved: bool):
@@ -1258,116 +1142,34 @@ def _head_rows(h, interleaved: bool):
     raise ValueError(f"fusion head: h {tuple(h.shape)} is not {'(B, 2 d)' if interleaved else '(2, B, d)'}")
 
 
+# geometry(h, interleaved, params) -> (h as the entries read it, h_omic's offset in elements | None for one pointer,
+#                                      the entries' geometry arguments, the size queries' (n_slides first, n_classes last))
+def _concat_geometry(hcat, interleaved, params):
+    b, din = hcat.shape
+    hidden, dout, c = params[0].shape[0], params[2].shape[0], params[4].shape[0]
+    return hcat.contiguous(), None, (b, din, hidden, dout, c), (b, hidden, dout, c)
+
+
+def _gated_concat_geometry(h, interleaved, params):
+    omic, ld, b, d = _head_rows(h, interleaved)
+    c = params[8].shape[0]
+    return h, omic, (ld, b, d, c), (b, d, c)
+
+
+def _bilinear_geometry(h, interleaved, params):
+    omic, ld, b, d = _head_rows(h, interleaved)
+    c = params[16].shape[0]
+    return h, omic, (ld, b, d, params[4].shape[0], params[12].shape[0], c), (b, d, c)       # (.., hidden, mm_hidden, ..)
+
+
+def _concat_params(fusion_layer, classifier):
+    seq = fusion_layer.fusion_layer
+    return seq[0].weight, seq[0].bias, seq[2].weight, seq[2].bias, classifier.weight, classifier.bias
+
+
 def _gated_concat_params(fusion_layer, classifier):
-    gates, seq = fusion_layer.gates, fusion_layer.fusion_layer
-    return (gates[0][0].weight, gates[0][0].bias, gates[1][0].weight, gates[1][0].bias, seq[0].weight, seq[0].bias,
-            seq[2].weight, seq[2].bias, classifier.weight, classifier.bias)
-
-
-class GatedConcatHeadFn(torch.autograd.Function):
-    """GatedConcatFusion's gates + K6 (MLP, classifier, survival head), one C-ABI call each way (mpo_gated_concat_head_*)."""
-
-    @staticmethod
-    def forward(ctx, h, interleaved, *params):
-        lib = L.lib()
-        ctx.set_materialize_grads(False)
-        omic, ld, b, d = _head_rows(h, interleaved)
-        ctx.interleaved = interleaved
-        c = params[8].shape[0]
-        hz = torch.empty(b, c, device=h.device, dtype=torch.float32)
-        sv, y = torch.empty_like(hz), torch.empty_like(hz)
-        saved = torch.empty(lib.mpo_gated_concat_head_saved_floats(b, d, c), device=h.device, dtype=torch.float32)
-        L.call("mpo_gated_concat_head_forward", L.ptr(h), L.ptr(h) + 4 * omic, ld, b, d, c, L.ptr_array(params), L.ptr(hz),
-               L.ptr(sv), L.ptr(y), L.ptr(saved), L.stream_of(h))
-        stats["gated_concat_head"] += 1
-        ctx.save_for_backward(h, saved, hz, sv, y, *params)
-        ctx.param_refs = params
-        return hz, sv, y
-
-    @staticmethod
-    def backward(ctx, dhz, dsv, dy):
-        lib = L.lib()
-        h, saved, hz, sv, y, *params = ctx.saved_tensors
-        omic, ld, b, d = _head_rows(h, ctx.interleaved)
-        c = params[8].shape[0]
-        d_h = torch.empty_like(h)
-        grads = [grad_out(p) for p in ctx.param_refs]
-        ws = _workspace(lib.mpo_gated_concat_head_workspace_bytes(b, d, c), h.device)
-        dhz, dsv, dy = (t.contiguous() if t is not None else None for t in (dhz, dsv, dy))
-        L.call("mpo_gated_concat_head_backward",
-            L.ptr(h), L.ptr(h) + 4 * omic, ld, b, d, c, L.ptr_array(params), L.ptr(saved), L.ptr(hz), L.ptr(sv), L.ptr(y),
-            L.ptr(dhz), L.ptr(dsv), L.ptr(dy), L.ptr(d_h), L.ptr(d_h) + 4 * omic, L.ptr_array(grads), L.ptr(ws), ws.numel(),
-            L.stream_of(h))
-        return (d_h, None, *grads)
-
-
-def gated_concat_head(h, fusion_layer, classifier, interleaved: bool = True):
-    """h (B, 2 d) = [h_path | h_omic] (`interleaved`) or (2, B, d) -> hazards, survs, Y (B, C)   (models/fusion.py:22-41 +
-    models/mcat/mcat.py:126-138); fusion_layer: a fusion.GatedConcatFusion."""
-    return GatedConcatHeadFn.apply(h, bool(interleaved), *_gated_concat_params(fusion_layer, classifier))
-
-
-class GatedConcatHeadLossFn(torch.autograd.Function):
-    """GatedConcatHeadFn for a training step, as FusionHeadLossFn is to FusionHeadFn: head, `ces` / `sct` loss and the
-    backward of both in ONE launch; backward() must be driven with the `slide_weight` tensor given to forward.
-    Returns (loss (B,), risk (B,), hazards, survs, Y); only `loss` carries gradient."""
-
-    @staticmethod
-    def forward(ctx, h, interleaved, label, censorship, slide_weight, alpha, eps, kind, *params):
-        lib = L.lib()
-        ctx.set_materialize_grads(False)
-        omic, ld, b, d = _head_rows(h, interleaved)
-        ctx.interleaved = interleaved
-        c = params[8].shape[0]
-        label = label.view(-1).to(torch.int64).contiguous()
-        censorship = censorship.view(-1).to(torch.float32).contiguous()
-        if slide_weight.shape != (b,) or slide_weight.dtype != torch.float32 or not slide_weight.is_contiguous():
-            raise ValueError("gated_concat_head_loss: slide_weight must be a contiguous fp32 tensor of one value per slide")
-        dev = h.device
-        hz = torch.empty(b, c, device=dev, dtype=torch.float32)
-        sv, y = torch.empty_like(hz), torch.empty_like(hz)
-        loss = torch.empty(b, device=dev, dtype=torch.float32)
-        risk = torch.empty(b, device=dev, dtype=torch.float32)
-        saved = torch.empty(lib.mpo_gated_concat_head_loss_saved_floats(b, d, c), device=dev, dtype=torch.float32)
-        L.call("mpo_gated_concat_head_loss_forward",
-            L.ptr(h), L.ptr(h) + 4 * omic, ld, b, d, c, L.ptr_array(params), L.ptr(label), L.ptr(censorship),
-            L.ptr(slide_weight), float(alpha), float(eps), FUSED_LOSSES.index(kind), L.ptr(hz), L.ptr(sv), L.ptr(y),
-            L.ptr(loss), L.ptr(risk), L.ptr(saved), L.stream_of(h))
-        stats["head_loss_" + kind] += 1
-        stats["gated_concat_head"] += 1
-        ctx.save_for_backward(h, saved, slide_weight, *params)
-        ctx.param_refs = params
-        ctx.mark_non_differentiable(risk, hz, sv, y)
-        return loss, risk, hz, sv, y
-
-    @staticmethod
-    def backward(ctx, d_loss, *_unused):
-        lib = L.lib()
-        h, saved, slide_weight, *params = ctx.saved_tensors
-        if d_loss is None:
-            return (None,) * (8 + len(params))
-        if d_loss.data_ptr() != slide_weight.data_ptr() or d_loss.shape != slide_weight.shape:
-            raise RuntimeError("gated_concat_head_loss: backward() must be driven with the slide_weight tensor given to "
-                               "forward (the loss gradient is folded into the forward launch)")
-        omic, ld, b, d = _head_rows(h, ctx.interleaved)
-        c = params[8].shape[0]
-        d_h = torch.empty_like(h)
-        grads = [grad_out(p) for p in ctx.param_refs]
-        ws = _workspace(lib.mpo_gated_concat_head_workspace_bytes(b, d, c), h.device)
-        L.call("mpo_gated_concat_head_loss_backward",
-            L.ptr(h), L.ptr(h) + 4 * omic, ld, b, d, c, L.ptr_array(params), L.ptr(saved), L.ptr(d_h), L.ptr(d_h) + 4 * omic,
-            L.ptr_array(grads), L.ptr(ws), ws.numel(), L.stream_of(h))
-        return (d_h, None, None, None, None, None, None, None, *grads)
-
-
-def gated_concat_head_loss(h, fusion_layer, classifier, label, censorship, slide_weight, alpha: float = 0.75, eps: float = 1e-7,
-                           loss: str = "ces", interleaved: bool = True):
-    """Training-step form of gated_concat_head: -> (per-slide loss, risk, hazards, survs, Y); drive backward with
-    `slide_weight` itself.  loss: 'ces' (weight `alpha`) or 'sct' (`alpha` unused), as fusion_head_loss_cat."""
-    if loss not in FUSED_LOSSES:
-        raise ValueError(f"gated_concat_head_loss: loss '{loss}' has no fused head launch ({' | '.join(FUSED_LOSSES)})")
-    return GatedConcatHeadLossFn.apply(h, bool(interleaved), label, censorship, slide_weight, alpha, eps, loss,
-                                       *_gated_concat_params(fusion_layer, classifier))
+    gates = fusion_layer.gates
+    return (gates[0][0].weight, gates[0][0].bias, gates[1][0].weight, gates[1][0].bias, *_concat_params(fusion_layer, classifier))
 
 
 def _bilinear_params(fusion_layer, classifier):
@@ -1388,115 +1190,197 @@ def _bilinear_drop_p(fusion_layer, training: bool) -> float:
     return float(ps.pop()) if training else 0.0
 
 
-def _bilinear_geom(h, interleaved, params):
-    omic, ld, b, d = _head_rows(h, interleaved)
-    return omic, ld, b, d, params[4].shape[0], params[12].shape[0], params[16].shape[0]     # hidden, mm_hidden, n_classes
+@dataclass(frozen=True)
+class _Head:
+    """What one fusion's head has of its own."""
+    name: str                   # mpo_<name>_* are its entries and size queries, <name>_loss names it in messages
+    loss_fn: str                # the public training-step function (named when it refuses a loss)
+    geometry: object            # see _concat_geometry
+    params: object              # (fusion_layer, classifier) -> the parameter tensors in the entries' order
+    drop_p: object = None       # (fusion_layer, training) -> the rate of the head's dropout sites; None: it has none, and its
+    #                             entries no (drop_p, seed, offset, rng_epoch); mpo_<name>_rng_span is their counter span
+    stat: Optional[str] = None  # the `stats` counter every forward bumps
+    entry_per_loss: bool = False  # K6: mpo_fusion_head_loss_forward (alpha, eps) | _sct_loss_forward (eps), no loss_kind
 
 
-class BilinearHeadFn(torch.autograd.Function):
-    """BilinearFusion + classifier + survival head, one C-ABI call each way (mpo_bilinear_head_*).  Training-mode masks are
-    a function of (seed, offset + epoch * 2^40): the backward regenerates them, nothing is stored."""
+_CONCAT = _Head("fusion_head", "fusion_head_loss_cat", _concat_geometry, _concat_params, entry_per_loss=True)
+_GATED_CONCAT = _Head("gated_concat_head", "gated_concat_head_loss", _gated_concat_geometry, _gated_concat_params,
+                      stat="gated_concat_head")
+_BILINEAR = _Head("bilinear_head", "bilinear_head_loss", _bilinear_geometry, _bilinear_params, _bilinear_drop_p, "bilinear_head")
+
+
+def _row_ptrs(t, omic):
+    return (L.ptr(t),) if omic is None else (L.ptr(t), L.ptr(t) + 4 * omic)
+
+
+def _head_begin(ctx, spec, h, interleaved, drop_p, params, slide_weight=None):
+    """What the forwards of the two forms share (slide_weight: the training-step form): geometry, the counters of the dropout
+    sites (reserved only when drop_p > 0, once), outputs and `saved` -> (h as the entries read it, hazards, survs, Y, saved)."""
+    lib = L.lib()
+    ctx.set_materialize_grads(False)
+    h, omic, geom, sizes = spec.geometry(h, interleaved, params)
+    b, c = sizes[0], sizes[-1]
+    if slide_weight is not None and (slide_weight.shape != (b,) or slide_weight.dtype != torch.float32
+                                     or not slide_weight.is_contiguous()):
+        raise ValueError(f"{spec.name}_loss: slide_weight must be a contiguous fp32 tensor of one value per slide")
+    rng = ()
+    if spec.drop_p is not None:
+        rng = (float(drop_p), *(_reserve(getattr(lib, f"mpo_{spec.name}_rng_span")(*sizes[:2])) if drop_p > 0 else (0, 0)))
+    hz = torch.empty(b, c, device=h.device, dtype=torch.float32)
+    sv, y = torch.empty_like(hz), torch.empty_like(hz)
+    query = getattr(lib, f"mpo_{spec.name}_{'loss_' if slide_weight is not None else ''}saved_floats")
+    saved = torch.empty(query(*sizes), device=h.device, dtype=torch.float32)
+    ctx.head = (spec, omic, geom, sizes, rng)
+    return h, hz, sv, y, saved
+
+
+def _head_lead(ctx, h, params):
+    """The arguments every entry starts with: row pointer(s), geometry, parameters (, dropout streams: the epoch as of now)."""
+    _, omic, geom, _, rng = ctx.head
+    return (*_row_ptrs(h, omic), *geom, L.ptr_array(params), *rng, *((_epoch(),) if rng else ()))
+
+
+def _head_end(ctx, spec, params, *tensors):
+    if spec.stat:
+        stats[spec.stat] += 1
+    ctx.save_for_backward(*tensors, *params)
+    ctx.param_refs = params
+
+
+def _head_grads(ctx, h):
+    """-> (d_h, parameter gradients, the arguments every backward entry ends with)."""
+    spec, omic, _, sizes, _ = ctx.head
+    d_h = torch.empty_like(h)
+    grads = [grad_out(p) for p in ctx.param_refs]
+    ws = _workspace(getattr(L.lib(), f"mpo_{spec.name}_workspace_bytes")(*sizes), h.device)
+    return d_h, grads, (*_row_ptrs(d_h, omic), L.ptr_array(grads), L.ptr(ws), ws.numel(), L.stream_of(h))
+
+
+class HeadFn(torch.autograd.Function):
+    """Fusion layer + classifier + survival head, one C-ABI call each way (mpo_<name>_forward / _backward).  Training-mode masks
+    (bilinear) are a function of (seed, offset + epoch * 2^40): the backward regenerates them, nothing is stored."""
 
     @staticmethod
-    def forward(ctx, h, interleaved, drop_p, *params):
-        lib = L.lib()
-        ctx.set_materialize_grads(False)
-        omic, ld, b, d, hid, mm, c = _bilinear_geom(h, interleaved, params)
-        seed, off = _reserve(lib.mpo_bilinear_head_rng_span(b, d)) if drop_p > 0 else (0, 0)
-        hz = torch.empty(b, c, device=h.device, dtype=torch.float32)
-        sv, y = torch.empty_like(hz), torch.empty_like(hz)
-        saved = torch.empty(lib.mpo_bilinear_head_saved_floats(b, d, c), device=h.device, dtype=torch.float32)
-        L.call("mpo_bilinear_head_forward", L.ptr(h), L.ptr(h) + 4 * omic, ld, b, d, hid, mm, c, L.ptr_array(params), float(drop_p),
-               seed, off, _epoch(), L.ptr(hz), L.ptr(sv), L.ptr(y), L.ptr(saved), L.stream_of(h))
-        stats["bilinear_head"] += 1
-        ctx.save_for_backward(h, saved, hz, sv, y, *params)
-        ctx.param_refs = params
-        ctx.interleaved, ctx.rng = interleaved, (float(drop_p), seed, off)
+    def forward(ctx, h, spec, interleaved, drop_p, *params):
+        h, hz, sv, y, saved = _head_begin(ctx, spec, h, interleaved, drop_p, params)
+        L.call(f"mpo_{spec.name}_forward", *_head_lead(ctx, h, params), L.ptr(hz), L.ptr(sv), L.ptr(y), L.ptr(saved),
+               L.stream_of(h))
+        _head_end(ctx, spec, params, h, saved, hz, sv, y)
         return hz, sv, y
 
     @staticmethod
     def backward(ctx, dhz, dsv, dy):
-        lib = L.lib()
         h, saved, hz, sv, y, *params = ctx.saved_tensors
-        omic, ld, b, d, hid, mm, c = _bilinear_geom(h, ctx.interleaved, params)
-        d_h = torch.empty_like(h)
-        grads = [grad_out(p) for p in ctx.param_refs]
-        ws = _workspace(lib.mpo_bilinear_head_workspace_bytes(b, d, c), h.device)
+        d_h, grads, tail = _head_grads(ctx, h)
         dhz, dsv, dy = (t.contiguous() if t is not None else None for t in (dhz, dsv, dy))
-        L.call("mpo_bilinear_head_backward",
-            L.ptr(h), L.ptr(h) + 4 * omic, ld, b, d, hid, mm, c, L.ptr_array(params), *ctx.rng, _epoch(), L.ptr(saved), L.ptr(hz),
-            L.ptr(sv), L.ptr(y), L.ptr(dhz), L.ptr(dsv), L.ptr(dy), L.ptr(d_h), L.ptr(d_h) + 4 * omic, L.ptr_array(grads), L.ptr(ws),
-            ws.numel(), L.stream_of(h))
-        return (d_h, None, None, *grads)
+        L.call(f"mpo_{ctx.head[0].name}_backward", *_head_lead(ctx, h, params), L.ptr(saved), L.ptr(hz), L.ptr(sv), L.ptr(y),
+               L.ptr(dhz), L.ptr(dsv), L.ptr(dy), *tail)
+        return (d_h, None, None, None, *grads)
 
 
-def bilinear_head(h, fusion_layer, classifier, training: bool, interleaved: bool = True):
-    """h (B, 2 d) = [h_path | h_omic] (`interleaved`) or (2, B, d) -> hazards, survs, Y (B, C)   (models/fusion.py:44-113 +
-    models/mcat/mcat.py:126-138); fusion_layer: a fusion.BilinearFusion as the models build it."""
-    return BilinearHeadFn.apply(h, bool(interleaved), _bilinear_drop_p(fusion_layer, training),
-                                *_bilinear_params(fusion_layer, classifier))
-
-
-class BilinearHeadLossFn(torch.autograd.Function):
-    """BilinearHeadFn for a training step, as FusionHeadLossFn is to FusionHeadFn: head, `ces` / `sct` loss and the backward
-    of both in ONE launch; backward() must be driven with the `slide_weight` tensor given to forward.
+class HeadLossFn(torch.autograd.Function):
+    """HeadFn for a training step: the fusion's launches, then head, `ces` / `sct` loss and the backward of both in ONE launch.
+    The gradient the caller sends into the per-slide loss must be known up front: `slide_weight` (B device floats;
+    1 / grad_acc_step in the reference's loop, models/mcat/main.py:69-70) -- backward() refuses any other gradient tensor.
     Returns (loss (B,), risk (B,), hazards, survs, Y); only `loss` carries gradient."""
 
     @staticmethod
-    def forward(ctx, h, interleaved, drop_p, label, censorship, slide_weight, alpha, eps, kind, *params):
-        lib = L.lib()
-        ctx.set_materialize_grads(False)
-        omic, ld, b, d, hid, mm, c = _bilinear_geom(h, interleaved, params)
+    def forward(ctx, h, spec, interleaved, drop_p, label, censorship, slide_weight, alpha, eps, kind, *params):
+        h, hz, sv, y, saved = _head_begin(ctx, spec, h, interleaved, drop_p, params, slide_weight)
         label = label.view(-1).to(torch.int64).contiguous()
         censorship = censorship.view(-1).to(torch.float32).contiguous()
-        if slide_weight.shape != (b,) or slide_weight.dtype != torch.float32 or not slide_weight.is_contiguous():
-            raise ValueError("bilinear_head_loss: slide_weight must be a contiguous fp32 tensor of one value per slide")
-        seed, off = _reserve(lib.mpo_bilinear_head_rng_span(b, d)) if drop_p > 0 else (0, 0)
-        dev = h.device
-        hz = torch.empty(b, c, device=dev, dtype=torch.float32)
-        sv, y = torch.empty_like(hz), torch.empty_like(hz)
-        loss = torch.empty(b, device=dev, dtype=torch.float32)
-        risk = torch.empty(b, device=dev, dtype=torch.float32)
-        saved = torch.empty(lib.mpo_bilinear_head_loss_saved_floats(b, d, c), device=dev, dtype=torch.float32)
-        L.call("mpo_bilinear_head_loss_forward",
-            L.ptr(h), L.ptr(h) + 4 * omic, ld, b, d, hid, mm, c, L.ptr_array(params), float(drop_p), seed, off, _epoch(),
-            L.ptr(label), L.ptr(censorship), L.ptr(slide_weight), float(alpha), float(eps), FUSED_LOSSES.index(kind), L.ptr(hz),
-            L.ptr(sv), L.ptr(y), L.ptr(loss), L.ptr(risk), L.ptr(saved), L.stream_of(h))
+        loss = torch.empty(hz.shape[0], device=h.device, dtype=torch.float32)
+        risk = torch.empty_like(loss)
+        entry, which = f"mpo_{spec.name}_loss_forward", (float(alpha), float(eps), FUSED_LOSSES.index(kind))
+        if spec.entry_per_loss:
+            entry, which = (entry, which[:2]) if kind == "ces" else (f"mpo_{spec.name}_sct_loss_forward", which[1:2])
+        L.call(entry, *_head_lead(ctx, h, params), L.ptr(label), L.ptr(censorship), L.ptr(slide_weight), *which, L.ptr(hz),
+               L.ptr(sv), L.ptr(y), L.ptr(loss), L.ptr(risk), L.ptr(saved), L.stream_of(h))
         stats["head_loss_" + kind] += 1
-        stats["bilinear_head"] += 1
-        ctx.save_for_backward(h, saved, slide_weight, *params)
-        ctx.param_refs = params
-        ctx.interleaved, ctx.rng = interleaved, (float(drop_p), seed, off)
+        _head_end(ctx, spec, params, h, saved, slide_weight)
         ctx.mark_non_differentiable(risk, hz, sv, y)
         return loss, risk, hz, sv, y
 
     @staticmethod
     def backward(ctx, d_loss, *_unused):
-        lib = L.lib()
         h, saved, slide_weight, *params = ctx.saved_tensors
         if d_loss is None:
-            return (None,) * (9 + len(params))
+            return (None,) * (10 + len(params))
+        name = ctx.head[0].name
         if d_loss.data_ptr() != slide_weight.data_ptr() or d_loss.shape != slide_weight.shape:
-            raise RuntimeError("bilinear_head_loss: backward() must be driven with the slide_weight tensor given to forward "
+            raise RuntimeError(f"{name}_loss: backward() must be driven with the slide_weight tensor given to forward "
                                "(the loss gradient is folded into the forward launch)")
-        omic, ld, b, d, hid, mm, c = _bilinear_geom(h, ctx.interleaved, params)
-        d_h = torch.empty_like(h)
-        grads = [grad_out(p) for p in ctx.param_refs]
-        ws = _workspace(lib.mpo_bilinear_head_workspace_bytes(b, d, c), h.device)
-        L.call("mpo_bilinear_head_loss_backward",
-            L.ptr(h), L.ptr(h) + 4 * omic, ld, b, d, hid, mm, c, L.ptr_array(params), *ctx.rng, _epoch(), L.ptr(saved), L.ptr(d_h),
-            L.ptr(d_h) + 4 * omic, L.ptr_array(grads), L.ptr(ws), ws.numel(), L.stream_of(h))
-        return (d_h, None, None, None, None, None, None, None, None, *grads)
+        d_h, grads, tail = _head_grads(ctx, h)
+        L.call(f"mpo_{name}_loss_backward", *_head_lead(ctx, h, params), L.ptr(saved), *tail)
+        return (d_h, *(None,) * 9, *grads)
+
+
+def _head(spec, h, fusion_layer, classifier, training=False, targets=None, alpha=0.75, eps=1e-7, loss="ces", interleaved=True):
+    if targets is not None and loss not in FUSED_LOSSES:
+        raise ValueError(f"{spec.loss_fn}: loss '{loss}' has no fused head launch ({' | '.join(FUSED_LOSSES)})")
+    drop_p = spec.drop_p(fusion_layer, training) if spec.drop_p else 0.0
+    params = spec.params(fusion_layer, classifier)
+    if targets is None:
+        return HeadFn.apply(h, spec, bool(interleaved), drop_p, *params)
+    return HeadLossFn.apply(h, spec, bool(interleaved), drop_p, *targets, alpha, eps, loss, *params)
+
+
+def head(h, fusion_layer, classifier, training: bool = False, targets=None, alpha: float = 0.75, eps: float = 1e-7,
+         loss: str = "ces", interleaved: bool = True):
+    """The head of `fusion_layer` (a fusion.ConcatFusion, GatedConcatFusion or BilinearFusion) on the pooled rows h, (B, 2 d) =
+    [h_path | h_omic] (`interleaved`) or (2, B, d) (the two-pointer fusions, which read h in place; concat takes a contiguous
+    hcat) -> hazards, survs, Y (B, C).  training: the layer's dropout sites draw their masks (bilinear).
+    targets = (label, censorship, slide_weight): the training-step form -> (per-slide loss, risk, hazards, survs, Y); drive
+    backward with `slide_weight` itself.  loss: 'ces' (models/loss.py:5-28, weight `alpha`) or 'sct' (models/loss.py:62-85 on Y;
+    `alpha` unused)."""
+    from . import fusion
+    for cls, spec in ((fusion.ConcatFusion, _CONCAT), (fusion.GatedConcatFusion, _GATED_CONCAT), (fusion.BilinearFusion, _BILINEAR)):
+        if isinstance(fusion_layer, cls):
+            return _head(spec, h, fusion_layer, classifier, training, targets, alpha, eps, loss, interleaved)
+    raise NotImplementedError(f"ops.head: no head for a fusion layer of type {type(fusion_layer).__name__}")
+
+
+def fusion_head(h_path, h_omic, fusion_layer, classifier):
+    """(B,d),(B,d) -> hazards, survs, Y (B, C)   (models/fusion.py:17-19 + models/mcat/mcat.py:126-138)."""
+    return _head(_CONCAT, torch.cat([h_path, h_omic], dim=-1), fusion_layer, classifier)
+
+
+def fusion_head_cat(hcat, fusion_layer, classifier):
+    """hcat (B, 2d) = [h_path | h_omic] already concatenated."""
+    return _head(_CONCAT, hcat, fusion_layer, classifier)
+
+
+def fusion_head_loss_cat(hcat, fusion_layer, classifier, label, censorship, slide_weight, alpha: float = 0.75, eps: float = 1e-7,
+                         loss: str = "ces"):
+    """Training-step K6: -> (per-slide loss, risk, hazards, survs, Y); drive backward with `slide_weight` itself.
+    loss: 'ces' (models/loss.py:5-28, weight `alpha`) or 'sct' (models/loss.py:62-85 on Y; `alpha` unused)."""
+    return _head(_CONCAT, hcat, fusion_layer, classifier, False, (label, censorship, slide_weight), alpha, eps, loss)
+
+
+def gated_concat_head(h, fusion_layer, classifier, interleaved: bool = True):
+    """h (B, 2 d) = [h_path | h_omic] (`interleaved`) or (2, B, d) -> hazards, survs, Y (B, C)   (models/fusion.py:22-41 +
+    models/mcat/mcat.py:126-138); fusion_layer: a fusion.GatedConcatFusion."""
+    return _head(_GATED_CONCAT, h, fusion_layer, classifier, interleaved=interleaved)
+
+
+def gated_concat_head_loss(h, fusion_layer, classifier, label, censorship, slide_weight, alpha: float = 0.75, eps: float = 1e-7,
+                           loss: str = "ces", interleaved: bool = True):
+    """Training-step form of gated_concat_head: -> (per-slide loss, risk, hazards, survs, Y); drive backward with
+    `slide_weight` itself.  loss: 'ces' (weight `alpha`) or 'sct' (`alpha` unused), as fusion_head_loss_cat."""
+    return _head(_GATED_CONCAT, h, fusion_layer, classifier, False, (label, censorship, slide_weight), alpha, eps, loss, interleaved)
+
+
+def bilinear_head(h, fusion_layer, classifier, training: bool, interleaved: bool = True):
+    """h (B, 2 d) = [h_path | h_omic] (`interleaved`) or (2, B, d) -> hazards, survs, Y (B, C)   (models/fusion.py:44-113 +
+    models/mcat/mcat.py:126-138); fusion_layer: a fusion.BilinearFusion as the models build it."""
+    return _head(_BILINEAR, h, fusion_layer, classifier, training, interleaved=interleaved)
 
 
 def bilinear_head_loss(h, fusion_layer, classifier, label, censorship, slide_weight, training: bool, alpha: float = 0.75,
                        eps: float = 1e-7, loss: str = "ces", interleaved: bool = True):
     """Training-step form of bilinear_head: -> (per-slide loss, risk, hazards, survs, Y); drive backward with `slide_weight`
     itself.  loss: 'ces' (weight `alpha`) or 'sct' (`alpha` unused), as fusion_head_loss_cat."""
-    if loss not in FUSED_LOSSES:
-        raise ValueError(f"bilinear_head_loss: loss '{loss}' has no fused head launch ({' | '.join(FUSED_LOSSES)})")
-    return BilinearHeadLossFn.apply(h, bool(interleaved), _bilinear_drop_p(fusion_layer, training), label, censorship, slide_weight,
-                                    alpha, eps, loss, *_bilinear_params(fusion_layer, classifier))
+    return _head(_BILINEAR, h, fusion_layer, classifier, training, (label, censorship, slide_weight), alpha, eps, loss, interleaved)
 
 
 class GeHeadLossFn(torch.autograd.Function):

@@ -104,6 +104,25 @@ def test_refusals_come_before_any_launch():
         assert rc == 1 and text in msg, (text, rc, msg)
 
 
+def _concat(name, *, hcat=FAKE, params=FAKE, label=FAKE, hz=FAKE, saved=FAKE):
+    geom = (hcat, 3, 512, 256, 256, 4, params)
+    if name == "forward":
+        return _rc("mpo_fusion_head_forward", *geom, hz, FAKE, FAKE, saved, None)
+    if name == "loss_forward":
+        return _rc("mpo_fusion_head_loss_forward", *geom, label, FAKE, FAKE, 0.75, 1e-7, hz, FAKE, FAKE, FAKE, FAKE, saved, None)
+    return _rc("mpo_fusion_head_sct_loss_forward", *geom, label, FAKE, FAKE, 1e-7, hz, FAKE, FAKE, FAKE, FAKE, saved, None)
+
+
+def test_concat_forward_entries_refuse_null_arguments():
+    """K6's three forward entries answer a missing pointer as the other two fusions' do, naming themselves (its two backward
+    entries answer an empty call with 'workspace too small', tests/test_host_cpu.py)."""
+    for name, who in (("forward", "fusion head forward"), ("loss_forward", "fusion head + loss forward"),
+                      ("sct_loss_forward", "fusion head + sct loss forward")):
+        for kw in (dict(hcat=None), dict(params=None), dict(hz=None), dict(saved=None)) + ((dict(label=None),) if name != "forward" else ()):
+            rc, msg = _concat(name, **kw)
+            assert rc == 1 and msg == who + ": null argument", (name, kw, rc, msg)
+
+
 def _golden_case():
     sd = syn.fill_state_dict(C.GATED_CONCAT_SHAPES, 720)
     hp, ho, _ = C.fusion_inputs()

@@ -548,3 +548,76 @@ def test_bilinear_fused_loss_equals_the_composed_one_and_takes_the_fused_path(de
     harness.train_window(model, bags, omics, labels, cens, 4, loss=loss)
     assert ops.stats["bilinear_head"] == before["bilinear_head"] + 1
     assert ops.stats["head_loss_" + loss] == before["head_loss_" + loss] + 1
+
+
+# =============================================================================================== the Python layer's refusals
+class _KeepsItsGradient(torch.autograd.Function):
+    """Passes `y` on and sends no gradient back to `x`: what reaches x's producer is an undefined gradient."""
+
+    @staticmethod
+    def forward(ctx, x, y):
+        return y.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        return None, g
+
+
+def _head_callers(dev, fusion, d, c):
+    """-> (plain(h), with_loss(h, label, cens, w, **kw), the modules' parameters) of ops' public functions of one fusion."""
+    from multimodal_path_omic_amd.fusion import BilinearFusion, ConcatFusion, GatedConcatFusion
+    cls = torch.nn.Linear(d, c).to(dev)
+    if fusion == "concat":
+        fus = ConcatFusion(dims=[d, d], hidden_size=d, output_size=d).to(dev).eval()
+        plain = lambda h: ops.fusion_head_cat(h, fus, cls)                                               # noqa: E731
+        with_loss = lambda h, *t, **kw: ops.fusion_head_loss_cat(h, fus, cls, *t, **kw)                  # noqa: E731
+    elif fusion == "gated_concat":
+        fus = GatedConcatFusion(dims=[d, d], hidden_size=d, output_size=d).to(dev).eval()
+        plain = lambda h: ops.gated_concat_head(h, fus, cls)                                             # noqa: E731
+        with_loss = lambda h, *t, **kw: ops.gated_concat_head_loss(h, fus, cls, *t, **kw)                # noqa: E731
+    else:
+        fus = BilinearFusion(dim1=d, dim2=d, output_size=d).to(dev).eval()
+        plain = lambda h: ops.bilinear_head(h, fus, cls, False)                                          # noqa: E731
+        with_loss = lambda h, *t, **kw: ops.bilinear_head_loss(h, fus, cls, *t, False, **kw)             # noqa: E731
+    return plain, with_loss, list(fus.parameters()) + list(cls.parameters())
+
+
+@pytest.mark.parametrize("fusion", ["concat", "gated_concat", "bilinear"])
+def test_python_layer_refusals(dev, fusion):
+    """What ops refuses on its own side of the C ABI, the same for the three fusions, and the one backward that does nothing."""
+    b, d, c = 2, min(F.D_BUILT), 4
+    name = {"concat": "fusion_head_loss", "gated_concat": "gated_concat_head_loss", "bilinear": "bilinear_head_loss"}[fusion]
+    plain, with_loss, params = _head_callers(dev, fusion, d, c)
+    h = syn.normal(syn.rng(9000), (b, 2 * d)).to(dev).requires_grad_(True)
+    label, cens = torch.arange(b, device=dev) % c, torch.zeros(b, device=dev)
+    w = torch.full((b,), 0.5, device=dev)
+    # backward is driven with the slide_weight tensor itself, nothing else
+    loss, *_ = with_loss(h, label, cens, w)
+    with pytest.raises(RuntimeError, match=name + r": backward\(\) must be driven with the slide_weight tensor"):
+        loss.backward(w.clone())
+    assert h.grad is None and all(p.grad is None for p in params)
+    # slide_weight: fp32, one value per slide
+    for bad in (w.double(), torch.full((b + 1,), 0.5, device=dev)):
+        with pytest.raises(ValueError, match=name + ": slide_weight must be a contiguous fp32 tensor of one value per slide"):
+            with_loss(h, label, cens, bad)
+    with pytest.raises(ValueError, match=name + r"\w*: loss 'nll' has no fused head launch"):
+        with_loss(h, label, cens, w, loss="nll")
+    # h is read in place by the two-pointer fusions: another shape or a strided view is refused; concat takes a copy instead
+    wide = syn.normal(syn.rng(9001), (b, 4 * d)).to(dev)
+    wide[:, :2 * d] = h.detach()
+    if fusion == "concat":
+        for got, want in zip(plain(wide[:, :2 * d]), plain(h.detach())):
+            assert torch.equal(got, want)
+    else:
+        for call in (plain, lambda t: with_loss(t, label, cens, w)):
+            with pytest.raises(ValueError, match="h must be contiguous"):
+                call(wide[:, :2 * d])
+            with pytest.raises(ValueError, match=r"is not \(B, 2 d\)"):
+                call(wide[:, :2 * d + 1].contiguous())
+            with pytest.raises(ValueError, match=r"is not \(B, 2 d\)"):
+                call(h.detach().view(2, b, d))
+    # a loss whose consumer sends no gradient back: the head's backward runs with none, launches nothing and returns none
+    loss, *_ = with_loss(h, label, cens, w)
+    probe = torch.ones(b, device=dev, requires_grad=True)
+    _KeepsItsGradient.apply(loss, probe).sum().backward()
+    assert probe.grad is not None and h.grad is None and all(p.grad is None for p in params)
