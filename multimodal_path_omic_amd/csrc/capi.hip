@@ -384,6 +384,38 @@ static int copy_cols(float* dst, size_t dst_ld, const float* src, size_t src_ld,
     return 0;
 }
 
+// What the two K2 entries start with: the checked geometry, the work plan, and column half h of a natural-layout [R][E]
+// query-side tensor.  take: the half of `src` a bag pass reads (a copy in `scratch`); put_to / put: where the producer of a half
+// of `dst` writes, and the copy that moves it home; map_to / map_add: maps are sums over the halves, the first half writes `map`,
+// a later one writes `tmp` and is added.  At NH == 1 a half is the tensor itself and nothing is copied or added.
+struct K2Call {
+    BagPlan splits;
+    int E, R, NH, EH, f32;                 // NH column halves of EH columns: 2 x 256 at embed 512, else the whole row
+    size_t half_k, half_h, half_dk;        // bytes from one half to the next of K, of the bag and of dK
+    hipStream_t stream;
+    int take(const float*& half, const float* src, float* scratch, int h) const {
+        half = NH > 1 ? scratch : src;
+        return NH > 1 ? copy_cols(scratch, EH, src + h * EH, E, R, EH, stream) : 0;
+    }
+    float* put_to(float* dst, float* scratch) const { return NH > 1 ? scratch : dst; }
+    int put(float* dst, const float* scratch, int h) const { return NH > 1 ? copy_cols(dst + h * EH, E, scratch, EH, R, EH, stream) : 0; }
+    static float* map_to(float* map, float* tmp, int h) { return h == 0 ? map : tmp; }
+    int map_add(float* map, const float* tmp, size_t n, int h) const { return h > 0 ? mpo_launch_ew_add(map, tmp, n, stream) : 0; }
+};
+// the shared checks in the entries' order (dk_dtype: the backward's; the forward passes MPO_F32)
+static int k2_begin(K2Call& c, int k_dtype, int bag_dtype, int dk_dtype, int n_slides, int total_rows, int max_rows, int n_q, int embed,
+                    float drop_p, const mpo_bag_plan* plan_, hipStream_t stream) {
+    RC(check_common(bag_dtype, n_slides, total_rows, max_rows, n_q, embed));
+    MPO_CHECK(drop_p >= 0.f && drop_p < 1.f, "attention dropout p must be in [0,1) (got %f)", (double)drop_p);
+    MPO_CHECK(k_dtype == MPO_F32, "nacagat co-attention: K must be fp32 (k_dtype %d): the narrow gate amplifies key rounding", k_dtype);
+    MPO_CHECK(dk_dtype == MPO_F32 || dk_dtype == MPO_BF16, "d_kbag dtype %d is neither MPO_F32 nor MPO_BF16", dk_dtype);
+    const int f32 = bag_dtype == MPO_F32, NH = embed == 512 ? 2 : 1, EH = embed / NH;      // (split-halves bag layout at 512)
+    const size_t half = (size_t)total_rows * EH;                                            // elements of one half of a bag
+    c = {make_plan(plan_, n_slides, max_rows), embed, n_slides * n_q, NH, EH, f32, half * 4, half * (f32 ? 4 : 2),
+         half * (dk_dtype == MPO_F32 ? 4 : 2), stream};
+    return check_plan(c.splits, n_slides);
+}
+
 int mpo_coattn_nacagat_forward(const void* kbag, int k_dtype, const void* hbag, int bag_dtype, const int32_t* cu_rows, int n_slides,
                                int total_rows, int max_rows, const float* query, int n_q, int embed,
                                const float* in_w, const float* in_b, const float* out_w, const float* out_b,
@@ -391,45 +423,37 @@ int mpo_coattn_nacagat_forward(const void* kbag, int k_dtype, const void* hbag, 
                                float* q_proj, float* out, float* attn_map, float* score_maps,
                                float* saved, const mpo_bag_plan* plan_, void* workspace, size_t workspace_bytes,
                                mpo_stream_t stream) {
-    RC(check_common(bag_dtype, n_slides, total_rows, max_rows, n_q, embed));
-    MPO_CHECK(drop_p >= 0.f && drop_p < 1.f, "attention dropout p must be in [0,1) (got %f)", (double)drop_p);
-    MPO_CHECK(k_dtype == MPO_F32, "nacagat co-attention: K must be fp32 (k_dtype %d): the narrow gate amplifies key rounding", k_dtype);
-    const int E = embed, R = n_slides * n_q, f32 = bag_dtype == MPO_F32;
-    const int NH = E == 512 ? 2 : 1, EH = E / NH;                          // column halves (split-halves bag layout at 512)
-    const size_t half_k = (size_t)total_rows * EH * 4, half_h = (size_t)total_rows * EH * (f32 ? 4 : 2);
-    const BagPlan splits = make_plan(plan_, n_slides, max_rows);          // (named `splits`: it replaces the old count)
-    RC(check_plan(splits, n_slides));
+    K2Call c;
+    RC(k2_begin(c, k_dtype, bag_dtype, MPO_F32, n_slides, total_rows, max_rows, n_q, embed, drop_p, plan_, stream));
+    const int E = c.E, R = c.R, NH = c.NH, EH = c.EH, f32 = c.f32;
+    const BagPlan& splits = c.splits;
     WsCarve ws(workspace, workspace_bytes);
     const K2FwdWs W = k2_fwd_ws(ws, R, plan_parts(splits), n_q, E, total_rows);
     MPO_CHECK(ws.ok(), "nacagat forward: workspace too small (%zu bytes)", workspace_bytes);
     Carve<kPacked> sv(saved);
     const K2Saved<float> S = k2_saved(sv, R, E);
+    const size_t map_n = (size_t)n_q * total_rows;
     float* a_map = score_maps;
-    float* g_map = score_maps + (size_t)n_q * total_rows;
+    float* g_map = score_maps + map_n;
     // q = query W_q^T + b_q  (returned: the reference hands it to the CAG, models/blocks.py:110,206)
     RC(mpo_linear_fwd(query, in_w, in_b, q_proj, R, E, E, 1.0f, MPO_ACT_NONE, stream));
     RC(mpo_launch_qprep(q_proj, S.qt, S.qs2, S.tq, R * E, 1.0f / sqrtf((float)E), stream));
     // one pass over K: a = qs2 . K and g = tanh(q) . tanh(K)   (tanh(K) is never materialised)
     for (int h = 0; h < NH; ++h) {
-        const float *r1 = S.qs2, *r2 = S.tq;
-        if (NH > 1) {
-            RC(copy_cols(W.hq1, EH, S.qs2 + h * EH, E, R, EH, stream));
-            RC(copy_cols(W.hq2, EH, S.tq + h * EH, E, R, EH, stream));
-            r1 = W.hq1; r2 = W.hq2;
-        }
-        float* am = h == 0 ? a_map : W.tmp_maps;
-        float* gm = h == 0 ? g_map : W.tmp_maps + (size_t)n_q * total_rows;
-        RC(mpo_launch_bag_rowdot_gated(static_cast<const char*>(kbag) + h * half_k, 1, cu_rows, n_slides, EH, r1, r2, am, gm, n_q,
-                                       splits, stream));
-        if (h > 0) RC(mpo_launch_ew_add(score_maps, W.tmp_maps, (size_t)2 * n_q * total_rows, stream));
+        const float *r1, *r2;
+        RC(c.take(r1, S.qs2, W.hq1, h));
+        RC(c.take(r2, S.tq, W.hq2, h));
+        RC(mpo_launch_bag_rowdot_gated(static_cast<const char*>(kbag) + h * c.half_k, 1, cu_rows, n_slides, EH, r1, r2,
+                                       c.map_to(a_map, W.tmp_maps, h), c.map_to(g_map, W.tmp_maps + map_n, h), n_q, splits, stream));
+        RC(c.map_add(score_maps, W.tmp_maps, 2 * map_n, h));
     }
     RC(mpo_launch_gated_softmax_fwd(a_map, g_map, cu_rows, attn_map, S.lse2, S.asum, n_slides, n_q, drop_p, seed, offset,
                                     reinterpret_cast<const unsigned long long*>(rng_epoch), stream));
     for (int h = 0; h < NH; ++h) {
-        RC(mpo_launch_bag_colacc(static_cast<const char*>(hbag) + h * half_h, f32, cu_rows, n_slides, EH, attn_map, W.part, n_q,
+        RC(mpo_launch_bag_colacc(static_cast<const char*>(hbag) + h * c.half_h, f32, cu_rows, n_slides, EH, attn_map, W.part, n_q,
                                  splits, stream));
-        RC(mpo_launch_coattn_bwd_reduce(W.part, NH > 1 ? W.hctx : S.ctx, n_slides, n_q, EH, splits, stream));
-        if (NH > 1) RC(copy_cols(S.ctx + h * EH, E, W.hctx, EH, R, EH, stream));
+        RC(mpo_launch_coattn_bwd_reduce(W.part, c.put_to(S.ctx, W.hctx), n_slides, n_q, EH, splits, stream));
+        RC(c.put(S.ctx, W.hctx, h));
     }
     // attn = ctx W_v^T + (sum_m A_drop) b_v ;  out = attn W_o^T + b_o
     RC(mpo_linear_fwd(S.ctx, in_w + (size_t)2 * E * E, nullptr, S.attn, R, E, E, 1.0f, MPO_ACT_NONE, stream));
@@ -446,15 +470,10 @@ int mpo_coattn_nacagat_backward(const void* kbag, int k_dtype, const void* hbag,
                                 float* d_query, int d_query_accumulate, void* d_kbag, int dk_dtype, float* d_kbag_colsum, void* d_hbag,
                                 float* d_ctx, float* d_in_w, float* d_in_b, float* d_out_w, float* d_out_b,
                                 const mpo_bag_plan* plan_, void* workspace, size_t workspace_bytes, mpo_stream_t stream) {
-    RC(check_common(bag_dtype, n_slides, total_rows, max_rows, n_q, embed));
-    MPO_CHECK(k_dtype == MPO_F32, "nacagat co-attention: K must be fp32 (k_dtype %d): the narrow gate amplifies key rounding", k_dtype);
-    MPO_CHECK(dk_dtype == MPO_F32 || dk_dtype == MPO_BF16, "d_kbag dtype %d is neither MPO_F32 nor MPO_BF16", dk_dtype);
-    const int E = embed, R = n_slides * n_q, f32 = bag_dtype == MPO_F32;
-    const int NH = E == 512 ? 2 : 1, EH = E / NH;                          // column halves (split-halves bag layout at 512)
-    const size_t half_k = (size_t)total_rows * EH * 4, half_h = (size_t)total_rows * EH * (f32 ? 4 : 2);
-    const size_t half_dk = (size_t)total_rows * EH * (dk_dtype == MPO_F32 ? 4 : 2);
-    const BagPlan splits = make_plan(plan_, n_slides, max_rows);
-    RC(check_plan(splits, n_slides));
+    K2Call c;
+    RC(k2_begin(c, k_dtype, bag_dtype, dk_dtype, n_slides, total_rows, max_rows, n_q, embed, drop_p, plan_, stream));
+    const int E = c.E, R = c.R, NH = c.NH, EH = c.EH, f32 = c.f32;
+    const BagPlan& splits = c.splits;
     MPO_CHECK(d_ctx != nullptr || d_hbag != nullptr, "nacagat backward: neither d_hbag nor d_ctx given");
     WsCarve ws(workspace, workspace_bytes);
     const K2BwdWs W = k2_bwd_ws(ws, R, plan_parts(splits), n_q, E, total_rows, d_kbag_colsum != nullptr);
@@ -478,16 +497,13 @@ int mpo_coattn_nacagat_backward(const void* kbag, int k_dtype, const void* hbag,
         RC(mpo_gemm_together(stream, mpo_args_bwd_input(W.dattn, w_v, dctx, R, E, E, 1.0f, 0),
                              mpo_args_bwd_weight(W.dattn, S.ctx, d_in_w + (size_t)2 * E * E, nullptr, R, E, E, 1.0f), &dbv, &das));
     }
-    // map side: dA = dctx . H^T (summed over the column halves at 512; hb[0], hb[1] keep the two halves of dctx)
+    // map side: dA = dctx . H^T (summed over the column halves at 512; dch keeps the two halves of dctx for the last pass)
+    const float* dch[2];
     for (int h = 0; h < NH; ++h) {
-        const float* dch = dctx;
-        if (NH > 1) {
-            RC(copy_cols(hb[h], EH, dctx + h * EH, E, R, EH, stream));
-            dch = hb[h];
-        }
-        RC(mpo_launch_bag_rowdot(static_cast<const char*>(hbag) + h * half_h, f32, cu_rows, n_slides, EH, dch,
-                                 h == 0 ? W.ds1_map : W.tmp_map, 1.0f, n_q, splits, stream));
-        if (h > 0) RC(mpo_launch_ew_add(W.ds1_map, W.tmp_map, (size_t)n_q * total_rows, stream));
+        RC(c.take(dch[h], dctx, hb[h], h));
+        RC(mpo_launch_bag_rowdot(static_cast<const char*>(hbag) + h * c.half_h, f32, cu_rows, n_slides, EH, dch[h],
+                                 c.map_to(W.ds1_map, W.tmp_map, h), 1.0f, n_q, splits, stream));
+        RC(c.map_add(W.ds1_map, W.tmp_map, (size_t)n_q * total_rows, h));
     }
     RC(mpo_launch_gated_softmax_bwd(a_map, g_map, cu_rows, S.lse2, W.dasum, d_attn_map, W.ds1_map, W.dg_map, n_slides, n_q, drop_p,
                                     seed, offset, reinterpret_cast<const unsigned long long*>(rng_epoch), stream));
@@ -496,15 +512,13 @@ int mpo_coattn_nacagat_backward(const void* kbag, int k_dtype, const void* hbag,
     // the two maps and nothing of each other, so K (491 MB per 32 x 15 000 window) is read once for the two
     const bool one_pass = g_k2_one_pass_key && NH == 1 && n_q <= 6;
     for (int h = 0; h < NH && !one_pass; ++h) {
-        RC(mpo_launch_bag_colacc_gated(static_cast<const char*>(kbag) + h * half_k, 1, cu_rows, n_slides, EH, W.ds1_map, W.dg_map,
+        RC(mpo_launch_bag_colacc_gated(static_cast<const char*>(kbag) + h * c.half_k, 1, cu_rows, n_slides, EH, W.ds1_map, W.dg_map,
                                        W.part, W.part2, n_q, splits, stream));
         BagFinish f{};
-        f.part[0] = W.part; f.out[0] = NH > 1 ? hb[2] : W.dqt; f.part[1] = W.part2; f.out[1] = NH > 1 ? hb[3] : W.dtq; f.n_red = 2;
+        f.part[0] = W.part; f.out[0] = c.put_to(W.dqt, hb[2]); f.part[1] = W.part2; f.out[1] = c.put_to(W.dtq, hb[3]); f.n_red = 2;
         RC(mpo_launch_bag_finish(f, n_slides, n_q, EH, splits, stream));
-        if (NH > 1) {
-            RC(copy_cols(W.dqt + h * EH, E, hb[2], EH, R, EH, stream));
-            RC(copy_cols(W.dtq + h * EH, E, hb[3], EH, R, EH, stream));
-        }
+        RC(c.put(W.dqt, hb[2], h));
+        RC(c.put(W.dtq, hb[3], h));
     }
     auto query_side = [&]() -> int {
         RC(mpo_launch_qprep_bwd(W.dqt, W.dtq, S.tq, d_q_proj, W.dq, R * E, 1.0f / sqrtf((float)E), stream));
@@ -515,18 +529,15 @@ int mpo_coattn_nacagat_backward(const void* kbag, int k_dtype, const void* hbag,
     // bag side: dK = ds1^T q~ + (dg^T tq) * (1 - TK^2),  dH = A_drop^T dctx
     // (one pass: tanh' from the staged K tile)
     for (int h = 0; h < NH; ++h) {
-        const float *qth = S.qt, *tqh = S.tq;
-        if (NH > 1) {
-            RC(copy_cols(hb[4], EH, S.qt + h * EH, E, R, EH, stream));
-            RC(copy_cols(hb[5], EH, S.tq + h * EH, E, R, EH, stream));
-            qth = hb[4]; tqh = hb[5];
-        }
+        const float *qth, *tqh;
+        RC(c.take(qth, S.qt, hb[4], h));
+        RC(c.take(tqh, S.tq, hb[5], h));
         if (one_pass)
             RC(mpo_launch_bag_key_grad(reinterpret_cast<const float*>(kbag), cu_rows, n_slides, EH, W.ds1_map, qth, W.dg_map, tqh,
                                        d_kbag, dk_dtype == MPO_F32, W.part_cs, W.part, W.part2, n_q, splits, stream));
         else
-            RC(mpo_launch_bag_outer_gated(reinterpret_cast<const float*>(static_cast<const char*>(kbag) + h * half_k), cu_rows,
-                                          n_slides, EH, W.ds1_map, qth, W.dg_map, tqh, static_cast<char*>(d_kbag) + h * half_dk,
+            RC(mpo_launch_bag_outer_gated(reinterpret_cast<const float*>(static_cast<const char*>(kbag) + h * c.half_k), cu_rows,
+                                          n_slides, EH, W.ds1_map, qth, W.dg_map, tqh, static_cast<char*>(d_kbag) + h * c.half_dk,
                                           dk_dtype == MPO_F32, W.part_cs, n_q, splits, stream));
         // one launch: the key bag's column sums, and (first half) zeros for the key slice of the packed in-projection (it
         // belongs to the caller's K = H W_k^T + b_k; a caller may have the key-bias gradient written straight into its slice)
@@ -542,8 +553,8 @@ int mpo_coattn_nacagat_backward(const void* kbag, int k_dtype, const void* hbag,
     if (one_pass) RC(query_side());
     if (d_ctx == nullptr)
         for (int h = 0; h < NH; ++h)
-            RC(mpo_launch_bag_outer(cu_rows, n_slides, EH, attn_map, NH > 1 ? hb[h] : dctx, nullptr, nullptr,
-                                    static_cast<char*>(d_hbag) + h * half_h, f32, n_q, splits, stream));
+            RC(mpo_launch_bag_outer(cu_rows, n_slides, EH, attn_map, dch[h], nullptr, nullptr,
+                                    static_cast<char*>(d_hbag) + h * c.half_h, f32, n_q, splits, stream));
     return 0;
 }
 

@@ -73,6 +73,13 @@ class _FusionModelBase(nn.Module):
     # the co-attention kernel can hand back d(H_bag) already multiplied by the ReLU/dropout derivative
     _fused_bag_gate = False
 
+    def _bag_gate(self, h_bags) -> float:
+        """bag_relu_gate for the co-attention over h_bags: the patch layer's keep scale (training; 1 in eval) when that
+        kernel finishes d(H_bag) with the ReLU / dropout derivative (bf16 bags), else 0."""
+        if h_bags.data.dtype == torch.bfloat16 and self._fused_bag_gate:
+            return getattr(h_bags.data, "_mpo_keep_scale", 1.0 / (1.0 - self.H[2].p)) if self.training else 1.0
+        return 0.0
+
     def _patch_fc(self, bags: BagBatch) -> BagBatch:
         x = bags.data
         lin = self.H[0]
@@ -164,10 +171,7 @@ class MultimodalCoAttentionTransformer(_FusionModelBase):
     _fused_bag_gate = True
 
     def _co_attend(self, g_bag, h_bags, inference):
-        gate = 0.0
-        if h_bags.data.dtype == torch.bfloat16:
-            gate = getattr(h_bags.data, "_mpo_keep_scale", 1.0 / (1.0 - self.H[2].p)) if self.training else 1.0
-        return self.co_attention.forward_window(g_bag, h_bags, need_weights=inference, bag_relu_gate=gate)
+        return self.co_attention.forward_window(g_bag, h_bags, need_weights=inference, bag_relu_gate=self._bag_gate(h_bags))
 
     def _token_pair(self, bags: BagBatch, omics):
         """Row f1 writes the co-attention output and the omic tokens straight into the (2, B, N, d) buffer the
@@ -207,11 +211,6 @@ class NarrowContextualAttentionGateTransformer(_FusionModelBase):
         # (the kernel that finishes d_bag with the patch layer's ReLU / dropout derivative is built for embed_dim <= 256; 'big'
         #  runs the column-half passes of csrc/capi.hip and leaves that derivative to the patch layer's own backward)
         return self.model_sizes[1] != 512
-
-    def _bag_gate(self, h_bags):
-        if h_bags.data.dtype == torch.bfloat16 and self._fused_bag_gate:
-            return getattr(h_bags.data, "_mpo_keep_scale", 1.0 / (1.0 - self.H[2].p)) if self.training else 1.0
-        return 0.0
 
     def _co_attend(self, g_bag, h_bags, inference):
         return self.co_attention.forward_window(g_bag, h_bags, bag_relu_gate=self._bag_gate(h_bags))

@@ -1,8 +1,9 @@
 """torch.autograd.Function wrappers around the C-ABI entries of libmpo_hip.so.
 
 One Function per kernel family of SURVEY.md section 2 (K1..K6).  Each forward/backward is ONE call
-across the ABI; the sequence of kernel launches lives in csrc/capi.hip.  Buffers (outputs, saved
-tensors, workspaces) are torch allocations; the library keeps nothing.
+across the ABI; the sequence of kernel launches lives in csrc/capi.hip.  K2 alone makes more: one core call
+each way, the key projection K = H W_k^T + b_k in front of it and that projection's gradients behind it, on a route
+chosen once in the forward (_key_route).  Buffers (outputs, saved tensors, workspaces) are torch allocations; the library keeps nothing.
 """
 from __future__ import annotations
 
@@ -1547,16 +1548,95 @@ class RowSampler:
         return self.batch
 
 
+# ------------------------------------------------------------------------------------ K2 (NaCAGaT co-attention)
+# K = H W_k^T + b_k is formed on this side of the ABI, in front of the one core call each way, and differentiated behind it:
+#   route        taken for                     _project_key                          _finish_key
+#   'kernel'     bf16 bag, E = 256 (medium)    mpo_key_projection                    'fused': one hand-written pass, dW_k kernel
+#   'gemm_bf16'  bf16 bag, E = 128 (small)     fp32 GEMM over a float copy           'one_pass': fp32 GEMM, one pass, dW_k kernel
+#   'gemm_f32'   fp32 bag, E <= 256            fp32 GEMM                             'gemm': two fp32 GEMMs
+#   'halves'     E = 512 (big), either dtype   two half GEMMs + the permuted bag     'gemm' after un-permuting, cast on the way out
 # False: the patch-side gradient of K2 as library GEMM + mpo_nacagat_patch_grad (the r02 path; kept for the small model and as
 # the cross-check of csrc/k2_patchgrad.hip in tools/gpu_diag_nacagat.py)
 k2_fused_patch_grad = True
 
 
+def _key_route(bag_dtype, E: int, bag_relu_gate: float) -> str:
+    """The one place that looks at (bag dtype, E, gate)."""
+    bf16 = bag_dtype == torch.bfloat16
+    if bag_relu_gate != 0.0 and not bf16:
+        raise ValueError("bag_relu_gate (fused ReLU/dropout derivative of the patch layer) needs a bf16-stored bag")
+    if E == 512 and bag_relu_gate != 0.0:
+        raise ValueError("embed_dim 512: the fused ReLU/dropout gate of the patch layer is built for embed_dim <= 256")
+    if E == 512:
+        return "halves"
+    return ("kernel" if E == 256 else "gemm_bf16") if bf16 else "gemm_f32"
+
+
+def _key_finish(route: str) -> str:
+    """How a backward of `route` finishes, read when it runs: k2_fused_patch_grad = False sends 'kernel' the 'gemm_bf16' way."""
+    if route in ("gemm_f32", "halves"):
+        return "gemm"
+    return "fused" if route == "kernel" and k2_fused_patch_grad else "one_pass"
+
+
+def _project_key(route, bag, w_k, b_k, stream):
+    """-> (K in fp32, the bag as the core call reads it: itself, or its split-halves copy)."""
+    T, E = bag.shape
+    if route == "halves":
+        # 'big' (models/nacagat/nacagat.py:17-18): both bags in the split-halves layout [2][T][256] of include/mpo_hip.h --
+        # K half h straight out of its own GEMM (rows 256 h .. of W_k), the bag as one strided copy
+        xf = bag.float().contiguous()
+        kbag = torch.empty(2, T, 256, device=bag.device, dtype=torch.float32)
+        for h in range(2):
+            L.call("mpo_linear_forward", L.ptr(xf), L.ptr(w_k[256 * h:]), L.ptr(b_k[256 * h:]), L.ptr(kbag[h]), T, E, 256, 1.0, L.ACT["none"], stream)
+        return kbag, bag.view(T, 2, 256).permute(1, 0, 2).contiguous()
+    kbag = torch.empty(T, E, device=bag.device, dtype=torch.float32)
+    if route == "kernel":
+        # HIP key projection: bf16 bag (exact) x fp32 weights split into three bf16 terms, fp32 accumulate and output
+        L.call("mpo_key_projection", L.ptr(bag), T, E, L.ptr(w_k), L.ptr(b_k), L.ptr(kbag), stream)
+    else:
+        # fp32 bag (or the small model's bf16 bag): the exact-fp32 MFMA GEMM of the token tail in its many-row form
+        L.call("mpo_linear_forward", L.ptr(bag.float().contiguous()), L.ptr(w_k), L.ptr(b_k), L.ptr(kbag), T, E, E, 1.0, L.ACT["none"], stream)
+    return kbag, bag
+
+
+def _finish_key(finish, ctx, bag, amap, w_k, d_k, d_h, d_ctx, d_wk, ws):
+    """-> d_h: back through K = H W_k^T + b_k.  The forward K stays fp32 (the gate amplifies its rounding); its GRADIENT goes
+    through bf16 operands with fp32 accumulation for a bf16 bag of E <= 256: dW_k as a batched split-K product (one 480 000-deep
+    fp32 contraction took 1.19 ms in rocBLAS), dH += dK W_k as a bf16 GEMM (0.59 ms in fp32).  (d_in_b[E:2E], the key bias
+    gradient = column sums of d_k, came out of the kernel that wrote d_k.)"""
+    (T, E), batch, gate, s = bag.shape, ctx.batch, ctx.bag_relu_gate, L.stream_of(bag)
+    if finish == "gemm":
+        # d_h += d_k W_k and dW_k = d_k^T H on the fp32 MFMA GEMMs (many-row / long-K forms); split-halves results go back to
+        # [T, 512] first (a bf16 bag: in fp32, rounded once on the way out)
+        if d_k.dim() == 3:
+            d_k, d_h = (t.permute(1, 0, 2).reshape(T, E).float().contiguous() for t in (d_k, d_h))
+        L.call("mpo_linear_backward_input", L.ptr(d_k), L.ptr(w_k), L.ptr(d_h), T, E, E, 1.0, 1, s)
+        L.call("mpo_linear_backward_weight", L.ptr(d_k), L.ptr(bag.float().contiguous()), L.ptr(d_wk), None, T, E, E, 1.0, s)
+        return d_h.to(bag.dtype)
+    # bf16 bag: dH = (dK W_k + A_drop^T dctx) (.) gate is finished by ONE pass over the bag instead of outer-product kernel ->
+    # addmm_ read-modify-write -> element-wise derivative pass
+    colsum = _bias_grad_slot(ctx.bag_bias, E, bag.device) if gate != 0.0 else None
+    head = (L.ptr(batch.cu), batch.n_slides, T, batch.max_rows, ctx.n_q, E, L.ptr(amap), L.ptr(d_ctx))
+    tail = (gate, L.ptr(colsum), batch.plan(), L.ptr(ws), ws.numel(), s)
+    if finish == "fused":                      # the product with W_k inside the pass (no library GEMM): csrc/k2_patchgrad.hip
+        d_h = torch.empty_like(d_k)
+        L.call("mpo_nacagat_patch_grad_fused", *head, L.ptr(d_k), L.ptr(w_k), L.ptr(bag), L.ptr(d_h), *tail)
+    else:                                      # the small model (E = 128): dK W_k on the fp32 MFMA GEMM (many-row form) first
+        dhf = torch.empty(T, E, device=bag.device, dtype=torch.float32)
+        L.call("mpo_linear_backward_input", L.ptr(d_k.float()), L.ptr(w_k), L.ptr(dhf), T, E, E, 1.0, 0, s)
+        d_h = dhf.to(torch.bfloat16)
+        L.call("mpo_nacagat_patch_grad", *head, L.ptr(d_h), L.ptr(bag), L.ptr(d_h), *tail)
+    if colsum is not None:
+        d_h._mpo_colsum = colsum              # the producing layer's bias gradient (PatchFcFn.backward picks it up)
+    patch_weight_grad(d_k, bag, d_wk)         # dW_k = d_k^T H_bag (hand-written for 256 x 256, bf16)
+    return d_h
+
+
 class CoAttnNaCAGaTFn(torch.autograd.Function):
     """NaCAGaT narrow-gated attention core over a ragged window (models/blocks.py:114-206).
-    Returns (q_proj, attn_out, post-dropout map).  K = H W_k^T + b_k is formed here first, by mpo_key_projection
-    (bf16 bag, embed 256) or mpo_linear_forward (everything else).  K is always fp32, also for a bf16-stored bag: the
-    gate multiplies k's rounding error (hard part 4)."""
+    Returns (q_proj, attn_out, post-dropout map).  K = H W_k^T + b_k is formed here first, by the bag's key route.  K is
+    always fp32, also for a bf16-stored bag: the gate multiplies k's rounding error (hard part 4)."""
 
     @staticmethod
     def forward(ctx, query, bag_data, in_w, in_b, out_w, out_b, batch: BagBatch, drop_p: float, bag_relu_gate: float = 0.0,
@@ -1570,31 +1650,8 @@ class CoAttnNaCAGaTFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         ctx.bag_relu_gate = float(bag_relu_gate)
         ctx.bag_bias = getattr(bag_data, "_mpo_bias_param", None)
-        if ctx.bag_relu_gate != 0.0 and bag_data.dtype != torch.bfloat16:
-            raise ValueError("bag_relu_gate (fused ReLU/dropout derivative of the patch layer) needs a bf16-stored bag")
-        big = E == 512
-        if big and ctx.bag_relu_gate != 0.0:
-            raise ValueError("embed_dim 512: the fused ReLU/dropout gate of the patch layer is built for embed_dim <= 256")
-        hb = bag_data
-        if bag_data.dtype == torch.bfloat16 and E == 256:
-            # HIP key projection: bf16 bag (exact) x fp32 weights split into three bf16 terms, fp32 accumulate and output
-            kbag = torch.empty(T, E, device=dev, dtype=torch.float32)
-            w_k, b_k = in_w[E:2 * E], in_b[E:2 * E]
-            L.call("mpo_key_projection", L.ptr(bag_data), T, E, L.ptr(w_k), L.ptr(b_k), L.ptr(kbag), L.stream_of(query))
-        elif big:
-            # 'big' (models/nacagat/nacagat.py:17-18): both bags in the split-halves layout [2][T][256] of include/mpo_hip.h --
-            # K half h straight out of its own GEMM (rows 256 h .. of W_k), the bag as one strided copy
-            xf = bag_data.float().contiguous()
-            kbag = torch.empty(2, T, 256, device=dev, dtype=torch.float32)
-            for h in range(2):
-                L.call("mpo_linear_forward", L.ptr(xf), L.ptr(in_w[E + 256 * h:E + 256 * (h + 1)]), L.ptr(in_b[E + 256 * h:E + 256 * (h + 1)]),
-                       L.ptr(kbag[h]), T, E, 256, 1.0, L.ACT["none"], L.stream_of(query))
-            hb = bag_data.view(T, 2, 256).permute(1, 0, 2).contiguous()
-        else:
-            # fp32 bag (or the small model's bf16 bag): the exact-fp32 MFMA GEMM of the token tail in its many-row form
-            kbag = torch.empty(T, E, device=dev, dtype=torch.float32)
-            L.call("mpo_linear_forward", L.ptr(bag_data.float().contiguous()), L.ptr(in_w[E:2 * E]), L.ptr(in_b[E:2 * E]), L.ptr(kbag),
-                   T, E, E, 1.0, L.ACT["none"], L.stream_of(query))
+        ctx.route = _key_route(bag_data.dtype, E, ctx.bag_relu_gate)
+        kbag, hb = _project_key(ctx.route, bag_data, in_w[E:2 * E], in_b[E:2 * E], L.stream_of(query))
         q_proj = torch.empty(R, E, device=dev, dtype=torch.float32)
         out = torch.empty(R, E, device=dev, dtype=torch.float32)
         amap = torch.empty(n_q * T, device=dev, dtype=torch.float32)
@@ -1607,8 +1664,7 @@ class CoAttnNaCAGaTFn(torch.autograd.Function):
             L.ptr(query), n_q, E, L.ptr(in_w), L.ptr(in_b), L.ptr(out_w), L.ptr(out_b), float(drop_p), seed, offset,
             _epoch(), L.ptr(q_proj), L.ptr(out), L.ptr(amap), L.ptr(score_maps), L.ptr(saved),
             batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(query))
-        ctx.save_for_backward(query, bag_data, kbag, in_w, in_b, out_w, saved, score_maps, amap)
-        ctx.hb = hb if big else None                  # (the split-halves copy of the bag: kept for the backward)
+        ctx.save_for_backward(query, bag_data, hb, kbag, in_w, in_b, out_w, saved, score_maps, amap)   # (hb: bag_data itself, or its split-halves copy)
         ctx.param_refs = (in_w, in_b, out_w, out_b)
         ctx.batch, ctx.n_q, ctx.drop = batch, n_q, (float(drop_p), seed, offset)
         ctx.qpass_owned = bool(qpass_owned)
@@ -1619,8 +1675,8 @@ class CoAttnNaCAGaTFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_qproj, d_out, d_map, d_qpass=None):
         lib = L.lib()
-        query, bag_data, kbag, in_w, in_b, out_w, saved, score_maps, amap = ctx.saved_tensors
-        batch, n_q = ctx.batch, ctx.n_q
+        query, bag_data, hb, kbag, in_w, in_b, out_w, saved, score_maps, amap = ctx.saved_tensors
+        batch, n_q, finish = ctx.batch, ctx.n_q, _key_finish(ctx.route)
         drop_p, seed, offset = ctx.drop
         R, E = query.shape
         dev, T = query.device, batch.total_rows
@@ -1628,62 +1684,19 @@ class CoAttnNaCAGaTFn(torch.autograd.Function):
         d_qproj = d_qproj.contiguous() if d_qproj is not None else None
         d_map = d_map.contiguous() if d_map is not None else None
         d_query, accumulate = _query_grad_buffer(d_qpass, ctx.qpass_owned, query)
-        d_k = torch.empty_like(kbag, dtype=bag_data.dtype)       # a bf16 bag takes its key gradient in bf16 (see below)
-        # bf16 bag: the patch-side gradient is finished by ONE pass after the dK W_k GEMM (mpo_nacagat_patch_grad) instead
-        # of outer-product kernel -> addmm_ read-modify-write -> element-wise derivative pass
-        big = E == 512
-        hb = ctx.hb if big else bag_data
-        fused_patch = bag_data.dtype == torch.bfloat16 and not big
-        d_h = None if fused_patch else torch.empty_like(hb)
-        d_ctx = torch.empty(R, E, device=dev, dtype=torch.float32) if fused_patch else None
+        d_k = torch.empty_like(kbag, dtype=bag_data.dtype)       # a bf16 bag takes its key gradient in bf16 (see _finish_key)
+        # 'gemm': the core call writes d_h and _finish_key adds to it; else it hands out d_ctx and _finish_key builds d_h
+        d_h = torch.empty_like(hb) if finish == "gemm" else None
+        d_ctx = None if finish == "gemm" else torch.empty(R, E, device=dev, dtype=torch.float32)
         d_in_w, d_in_b, d_out_w, d_out_b = (grad_out(p) for p in ctx.param_refs)
-        ws = _workspace(lib.mpo_nacagat_workspace_bytes(batch.n_slides, n_q, E, batch.max_rows, T), dev)
+        ws = _workspace(lib.mpo_nacagat_workspace_bytes(batch.n_slides, n_q, E, batch.max_rows, T), dev)   # (also the finish's)
         L.call("mpo_coattn_nacagat_backward",
             L.ptr(kbag), L.MPO_F32, L.ptr(hb), L.bag_dtype_code(bag_data), L.ptr(batch.cu), batch.n_slides, T,
             batch.max_rows, L.ptr(query), n_q, E, L.ptr(in_w), L.ptr(in_b), L.ptr(out_w), drop_p, seed, offset,
             _epoch(), L.ptr(saved), L.ptr(score_maps), L.ptr(amap), L.ptr(d_out), L.ptr(d_map), L.ptr(d_qproj),
             L.ptr(d_query), int(accumulate), L.ptr(d_k), L.bag_dtype_code(d_k), L.ptr(d_in_b[E:2 * E]), L.ptr(d_h), L.ptr(d_ctx), L.ptr(d_in_w), L.ptr(d_in_b), L.ptr(d_out_w),
             L.ptr(d_out_b), batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(query))
-        # back through the caller-side GEMM  K = H W_k^T + b_k.  The forward K stays fp32 (the gate amplifies its
-        # rounding); its GRADIENT goes through bf16 operands with fp32 accumulation for a bf16 bag: dW_k as a
-        # batched split-K product (one 480 000-deep fp32 contraction took 1.19 ms in rocBLAS), dH += dK W_k as a
-        # bf16 GEMM (0.59 ms in fp32).
-        w_k = in_w[E:2 * E]
-        if fused_patch:
-            gate = ctx.bag_relu_gate
-            colsum = _bias_grad_slot(ctx.bag_bias, E, dev) if gate != 0.0 else None
-            if E == 256 and k2_fused_patch_grad:
-                # dH = (dK W_k + A_drop^T dctx) (.) gate in ONE hand-written pass (no library GEMM): csrc/k2_patchgrad.hip
-                d_h = torch.empty_like(d_k)
-                L.call("mpo_nacagat_patch_grad_fused", L.ptr(batch.cu), batch.n_slides, T, batch.max_rows, n_q, E, L.ptr(amap),
-                       L.ptr(d_ctx), L.ptr(d_k), L.ptr(w_k), L.ptr(bag_data), L.ptr(d_h), gate,
-                       L.ptr(colsum), batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(query))
-            else:                                  # the small model (E = 128): dK W_k on the fp32 MFMA GEMM (many-row form), then the one-pass epilogue
-                dhf = torch.empty(T, E, device=dev, dtype=torch.float32)
-                L.call("mpo_linear_backward_input", L.ptr(d_k.float()), L.ptr(w_k), L.ptr(dhf), T, E, E, 1.0, 0, L.stream_of(query))
-                d_h = dhf.to(torch.bfloat16)
-                L.call("mpo_nacagat_patch_grad", L.ptr(batch.cu), batch.n_slides, T, batch.max_rows, n_q, E, L.ptr(amap),
-                       L.ptr(d_ctx), L.ptr(d_h), L.ptr(bag_data), L.ptr(d_h), gate, L.ptr(colsum),
-                       batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(query))
-            if colsum is not None:
-                d_h._mpo_colsum = colsum          # the producing layer's bias gradient (PatchFcFn.backward picks it up)
-            patch_weight_grad(d_k, bag_data, d_in_w[E:2 * E])     # dW_k = d_k^T H_bag (hand-written for 256 x 256, bf16)
-        elif big:
-            # split-halves results back to [T, 512], then the two products through the key projection on the fp32 MFMA GEMMs
-            # (a bf16 bag: in fp32, rounded once on the way out)
-            s_ = L.stream_of(query)
-            dkf = d_k.permute(1, 0, 2).reshape(T, E).float().contiguous()
-            dhf = d_h.permute(1, 0, 2).reshape(T, E).float().contiguous()
-            L.call("mpo_linear_backward_input", L.ptr(dkf), L.ptr(w_k), L.ptr(dhf), T, E, E, 1.0, 1, s_)
-            L.call("mpo_linear_backward_weight", L.ptr(dkf), L.ptr(bag_data.float().contiguous()), L.ptr(d_in_w[E:2 * E]), None, T, E, E,
-                   1.0, s_)
-            d_h = dhf.to(bag_data.dtype)
-        else:
-            # fp32 bag: d_h += d_k W_k and dW_k = d_k^T H on the fp32 MFMA GEMMs (many-row / long-K forms)
-            s_ = L.stream_of(query)
-            L.call("mpo_linear_backward_input", L.ptr(d_k), L.ptr(w_k), L.ptr(d_h), T, E, E, 1.0, 1, s_)
-            L.call("mpo_linear_backward_weight", L.ptr(d_k), L.ptr(bag_data), L.ptr(d_in_w[E:2 * E]), None, T, E, E, 1.0, s_)
-        # (d_in_b[E:2E], the key bias gradient = column sums of d_k, came out of the kernel that wrote d_k)
+        d_h = _finish_key(finish, ctx, bag_data, amap, in_w[E:2 * E], d_k, d_h, d_ctx, d_in_w[E:2 * E], ws)
         return d_query, d_h, d_in_w, d_in_b, d_out_w, d_out_b, None, None, None, None
 
 

@@ -340,3 +340,52 @@ def check_fused_patch_side_gradient(dev, n_q, gate, lengths, guard=0):
         assert torch.equal(out1, out[off:off + m]), (b, m)
         off += m
     return out.clone()
+
+
+# The four ways K = H W_k^T + b_k is formed and differentiated on the caller's side (ops._key_route), and the C entries
+# each one calls, in order, over one forward and one backward.  The one-pass / two-pass key gradient (n_q <= 6 / above) is a
+# choice inside mpo_coattn_nacagat_backward: it changes no entry.
+_K2_CORE = ["mpo_coattn_nacagat_forward", "mpo_coattn_nacagat_backward"]
+_K2_GEMM_FINISH = ["mpo_linear_backward_input", "mpo_linear_backward_weight"]
+_K2_ONE_PASS_FINISH = ["mpo_linear_backward_input", "mpo_nacagat_patch_grad", "mpo_patch_weight_grad"]
+K2_ROUTE_CALLS = {
+    # id: (bag dtype, E, ops.k2_fused_patch_grad, the ordered entries)
+    "key_projection": (torch.bfloat16, 256, True,
+                       ["mpo_key_projection"] + _K2_CORE + ["mpo_nacagat_patch_grad_fused", "mpo_patch_weight_grad"]),
+    "key_projection_unfused_finish": (torch.bfloat16, 256, False, ["mpo_key_projection"] + _K2_CORE + _K2_ONE_PASS_FINISH),
+    "gemm_bf16": (torch.bfloat16, 128, True, ["mpo_linear_forward"] + _K2_CORE + _K2_ONE_PASS_FINISH),
+    "gemm_f32": (torch.float32, 256, True, ["mpo_linear_forward"] + _K2_CORE + _K2_GEMM_FINISH),
+    "split_halves_bf16": (torch.bfloat16, 512, True, ["mpo_linear_forward"] * 2 + _K2_CORE + _K2_GEMM_FINISH),
+    "split_halves_f32": (torch.float32, 512, True, ["mpo_linear_forward"] * 2 + _K2_CORE + _K2_GEMM_FINISH),
+}
+
+
+@pytest.mark.parametrize("n_q", [6, 7])
+@pytest.mark.parametrize("route", list(K2_ROUTE_CALLS))
+def test_each_key_route_calls_its_entries_in_order(dev, monkeypatch, route, n_q):
+    """One forward and one backward of ops.coattn_nacagat per key route over a small ragged window (under 2048 rows: the
+    long-K GEMM body with its atomic adds is not taken), with n_q = 6 (one-pass key gradient) and 7 (two passes): the names
+    _lib.call receives, in order, are the route's row of K2_ROUTE_CALLS."""
+    from multimodal_path_omic_amd import _lib as L
+    from multimodal_path_omic_amd import ops
+    dtype, E, fused, want = K2_ROUTE_CALLS[route]
+    lengths = [1, 33, 700]
+    g = torch.Generator().manual_seed(E + n_q)
+    bag = torch.relu(torch.randn(sum(lengths), E, generator=g)).to(dtype).to(dev).requires_grad_(True)
+    query = torch.randn(len(lengths) * n_q, E, generator=g).to(dev).requires_grad_(True)
+    in_w, in_b, out_w, out_b = (((torch.rand(*s, generator=g) - 0.5) / 8).to(dev).requires_grad_(True)
+                                for s in ((3 * E, E), (3 * E,), (E, E), (E,)))
+    batch = ops.BagBatch.from_lengths(bag, lengths)
+    batch.plan()
+    seen, call = [], L.call
+
+    def recording_call(name, *args):
+        seen.append(name)
+        return call(name, *args)
+
+    monkeypatch.setattr(ops, "k2_fused_patch_grad", fused)
+    monkeypatch.setattr(L, "call", recording_call)
+    q_proj, out, amap = ops.coattn_nacagat(query, batch, in_w, in_b, out_w, out_b, 0.0)
+    grads = torch.autograd.grad(out.sum() + q_proj.sum() + amap.sum(), [query, bag, in_w, in_b, out_w, out_b])
+    assert seen == want, seen
+    assert all(bool(torch.isfinite(t.float()).all()) for t in grads)
