@@ -20,6 +20,9 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mpo_hip.h")
 # Companion headers mpo_hip.h includes (entries added to the ABI after its own list was closed): bound the same way.
 COMPANION_HEADER_PATHS = [os.path.join(os.path.dirname(_HERE), "include", name)
                           for name in ("mpo_bag_sample.h", "mpo_fusion_next.h")]
+# Headers registered after that list was closed in its turn (companion_symbols() and all_companion_symbols() keep naming what
+# they named): same rules, same binding, their own accessor later_symbols().
+LATER_HEADER_PATHS = [os.path.join(os.path.dirname(_HERE), "include", name) for name in ("mpo_cohort.h",)]
 
 # The closed map from the header's scalar parameter types; a new scalar type in the header needs a new line here.
 _SCALARS = {"int": c_int, "int32_t": c_int, "int64_t": c_int64, "uint64_t": c_uint64, "size_t": c_size_t, "float": c_float,
@@ -79,10 +82,11 @@ def _read_header():
     return signatures, constants, version
 
 
-def _read_companions():
-    """Entry signatures of the companion headers (no enums, no version of their own) -> (all of them, {header: its names})."""
+def _read_companions(paths, taken):
+    """Entry signatures of the companion headers `paths` (no enums, no version of their own) -> (all of them, {header: its
+    names}).  `taken`: the names declared by the headers read before these; a name declared twice anywhere is an error."""
     out, by_header = {}, {}
-    for path in COMPANION_HEADER_PATHS:
+    for path in paths:
         if not os.path.exists(path):
             raise RuntimeError(f"{path} is missing: include/mpo_hip.h includes it and the package binds its entries")
         with open(path) as f:
@@ -90,7 +94,7 @@ def _read_companions():
         if not signatures or constants or version is not None:
             raise RuntimeError(f"{path}: a companion header declares entries only (no enum, no MPO_ABI_VERSION)")
         for name in signatures:
-            if name in _signatures or name in out:
+            if name in taken or name in out:
                 raise RuntimeError(f"{path}: {name} is declared twice")
         out.update(signatures)
         by_header[os.path.basename(path)] = list(signatures)
@@ -103,7 +107,8 @@ MPO_F32, MPO_BF16 = _constants["MPO_F32"], _constants["MPO_BF16"]
 ACT = {k[len("MPO_ACT_"):-1].lower(): v for k, v in _constants.items() if k.startswith("MPO_ACT_")}      # MPO_ACT_RELU_ -> relu
 OPTIM = {k[len("MPO_OPTIM_"):].lower(): v for k, v in _constants.items() if k.startswith("MPO_OPTIM_")}
 GEMM_ROUTE = {k[len("MPO_GEMM_ROUTE_"):].lower(): v for k, v in _constants.items() if k.startswith("MPO_GEMM_ROUTE_")}
-_companion_signatures, _companion_names = _read_companions()
+_companion_signatures, _companion_names = _read_companions(COMPANION_HEADER_PATHS, _signatures)
+_later_signatures, _later_names = _read_companions(LATER_HEADER_PATHS, {**_signatures, **_companion_signatures})
 
 
 class BagPlanC(ctypes.Structure):
@@ -131,6 +136,12 @@ def all_companion_symbols():
     return list(_companion_signatures)
 
 
+def later_symbols(header: "str | None" = None):
+    """The entries of the headers in LATER_HEADER_PATHS (of one of them, by file name), in declaration order: exported and
+    bound like every other entry, named by neither companion_symbols() nor all_companion_symbols()."""
+    return list(_later_signatures) if header is None else list(_later_names[header])
+
+
 def check_abi_version(found: int, expected: int):
     if found != expected:
         raise RuntimeError(f"{LIB_PATH} reports ABI version {found}, include/mpo_hip.h describes {expected}: the library is "
@@ -144,7 +155,7 @@ def lib():
             raise RuntimeError(
                 f"{LIB_PATH} is missing: the HIP extension has not been built ({_REBUILD}). There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**_signatures, **_companion_signatures}.items():
+        for name, (res, args) in {**_signatures, **_companion_signatures, **_later_signatures}.items():
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

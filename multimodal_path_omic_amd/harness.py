@@ -10,7 +10,7 @@ from typing import List, Sequence
 import numpy as np
 import torch
 
-from .ops import BagBatch
+from .ops import BagBatch, SlideSet
 
 
 def ces_loss(hazards, survs, label, censorship, alpha: float = 0.75, eps: float = 1e-7, reduction: str = "mean"):
@@ -79,15 +79,19 @@ def make_ge_window(slides: Sequence[dict], device, bag_dtype=torch.float32):
     return bags, labels
 
 
-def sample_window_rows(model, bags: BagBatch, sample_rows) -> BagBatch:
+def sample_window_rows(model, bags, sample_rows) -> BagBatch:
     """The window a training step runs on under `sample_rows` (None / 0: off): in training mode min(sample_rows, M_b) rows
     of every slide, drawn anew on every call without replacement (ops.RowSampler, eager form); in eval mode the whole
-    window, so validation sees every patch."""
+    window, so validation sees every patch.
+    A SlideSet (separately stored slides) is gathered from where its slides lie (with `cycle`: sample_rows rows of every
+    slide, short ones lapped); wherever the whole window is needed -- eval mode, no sample_rows -- it is materialized by one
+    torch.cat, since every bag kernel reads a contiguous window."""
+    slides = isinstance(bags, SlideSet)
     if not sample_rows or not model.training:
-        return bags
+        return bags.materialize() if slides else bags
     from . import ops
-    x = bags.data
-    return ops.RowSampler(bags.n_slides, int(sample_rows), x.shape[1], x.dtype, x.device, static=False).bind(bags)()
+    return ops.RowSampler(bags.n_slides, int(sample_rows), bags.width, bags.dtype, bags.device, static=False,
+                          source="slides" if slides else "window").bind(bags)()
 
 
 def train_ge_window(model, bags: BagBatch, labels, grad_acc_step: int, l1: float = 0.0, sample_rows: "int | None" = None):
@@ -250,6 +254,11 @@ class GraphedWindowStep:
     static shape -- and everything behind it sees the same lengths, plan and grids whatever window the sampler reads.
     bind(window) then re-points the captured step at another window of the same slide count, width and dtype with at least
     k rows per slide; every replay draws a fresh sample (the device epoch).  bf16 windows, model in training mode.
+
+    A window whose first element is an ops.SlideSet (ResidentCohort.window) captures the gather from separately stored
+    slides instead: bind() then takes further SlideSet windows -- slide ids into a cohort that lives on the device, no copy
+    and no H2D transfer per window -- and a SlideSet with `cycle` may hold slides shorter than k (lapped).  A step captured
+    on one kind of window refuses the other: the two gathers read different descriptors.  train_epoch drives an epoch.
     """
 
     def __init__(self, model, bucket, window, grad_acc_step: int, opt=None, warmup: int = 2, pool=None,
@@ -289,9 +298,13 @@ class GraphedWindowStep:
             reason = self._sampling_refusal(window[0], int(sample_rows))
             if reason:
                 raise ValueError(f"GraphedWindowStep(sample_rows={sample_rows}): {reason}")
-            x = window[0].data
-            self.sampler = ops.RowSampler(window[0].n_slides, int(sample_rows), x.shape[1], x.dtype, x.device).bind(window[0])
+            bags = window[0]
+            self.sampler = ops.RowSampler(bags.n_slides, int(sample_rows), bags.width, bags.dtype, bags.device,
+                                          source="slides" if isinstance(bags, SlideSet) else "window").bind(bags)
         else:
+            if isinstance(window[0], SlideSet):
+                raise ValueError("GraphedWindowStep: a SlideSet window is read by the row sampler alone (sample_rows=k); every "
+                                 "bag kernel reads a contiguous window -- materialize() it for an unsampled step")
             window[0].plan()                  # the work plan's H2D copy must not happen inside the capture
         dev = bucket.flat.device
         if ops._rng_epoch_tensor is None:
@@ -315,8 +328,8 @@ class GraphedWindowStep:
         if rng_base is not None:
             ops._rng_calls = int(rng_base)
         self.rng_base = ops._rng_calls
-        bag_data = window[0].data
-        self._fp32_window_version = bag_data._version if bag_data.dtype == torch.float32 else None
+        # (a sampled step refuses fp32 windows: only an unsampled step's BagBatch gets here with one)
+        self._fp32_window_version = window[0].data._version if window[0].dtype == torch.float32 else None
         # thread_local: other threads (RCCL's watchdog under torch.distributed) may issue HIP calls meanwhile
         with torch.cuda.graph(self.graph, pool=pool, capture_error_mode="thread_local"):
             out = self._body(flush=not self.split)
@@ -369,7 +382,7 @@ class GraphedWindowStep:
 
     def _sampling_refusal(self, bags, k: int) -> "str | None":
         """Why a sampled step cannot run on `bags` (None: it can)."""
-        if bags.data.dtype == torch.float32:
+        if bags.dtype == torch.float32:
             return ("an fp32 window's feature scale is baked into the graph as a kernel argument; the sampled step is built "
                     "for bf16 windows")
         if not self.model.training:
@@ -384,13 +397,16 @@ class GraphedWindowStep:
         the current stream (the one that replays), the sampler's descriptor is rewritten (one tiny launch) and omics,
         labels and censorship are copied into the tensors the graph reads.  No host synchronisation.  The window's rows
         must stay valid until the replays that read them have finished.  Raises ValueError with the reason when the
-        window does not fit the capture: another slide count, a slide shorter than k, another width or dtype, fp32."""
+        window does not fit the capture: another slide count, a slide shorter than k (unless a SlideSet laps it), another
+        width or dtype, fp32, a BagBatch for a step captured on a SlideSet or the reverse.  A refused bind changes nothing."""
         if self.sampler is None:
             raise ValueError("GraphedWindowStep.bind: the step was captured without sample_rows -- its graph reads one "
                              "resident window's rows directly")
         if len(window) != len(self.window):
             raise ValueError(f"GraphedWindowStep.bind: a window of {len(window)} parts for a step captured on {len(self.window)}")
         bags = window[0]
+        if not isinstance(bags, (BagBatch, SlideSet)):
+            raise ValueError(f"GraphedWindowStep.bind: a window starts with a BagBatch or a SlideSet, not a {type(bags).__name__}")
         reason = self._sampling_refusal(bags, self.sampler.k)
         if reason:
             raise ValueError(f"GraphedWindowStep.bind: {reason}")
@@ -426,3 +442,118 @@ class GraphedWindowStep:
                                "is baked into the graph -- capture a new step for the new contents")
         self.graph.replay()
         return self.loss if self.ge else (self.loss, self.risk)
+
+
+# ------------------------------------------------------------------------------------ a cohort resident on the device
+class ResidentCohort:
+    """A cohort that lives on the device once, for shuffled epochs of the sampled, captured step: every slide's rows (in
+    slabs of at most `slab_bytes`, a slide never split), the pointer / length table csrc/bag_sample_slides.hip is addressed
+    through, omics per group (N, d_i), labels, censorship and survival_months (all (N,)).  A window is a list of slide ids:
+    nothing is copied to form it and nothing crosses PCIe (1 000 slides of 15 000 x 1024 bf16 are 30 GB).
+
+    slides: the dict layout make_window takes (synthetic.make_cohort).  cycle: the windows lap a slide shorter than the
+    step's k in its permuted order instead of refusing it (ops.SlideSet).  Only the survival layout is built; a
+    gene-expression cohort ((SlideSet, labels) windows) is not."""
+
+    def __init__(self, slides: Sequence[dict], device, bag_dtype=torch.bfloat16, cycle: bool = False, slab_bytes: int = 1 << 30):
+        if len(slides) == 0:
+            raise ValueError("ResidentCohort: no slides")
+        self.device, self.cycle = torch.device(device), bool(cycle)
+        self.lengths = [int(s["wsi"].shape[0]) for s in slides]
+        width = int(slides[0]["wsi"].shape[1])
+        row_bytes = width * torch.empty(0, dtype=bag_dtype).element_size()
+        if row_bytes % 16:
+            raise ValueError(f"ResidentCohort: a row of {row_bytes} bytes is not a multiple of 16 bytes")
+        if any(m < 1 for m in self.lengths) or any(int(s["wsi"].shape[1]) != width for s in slides):
+            raise ValueError("ResidentCohort: every slide needs at least one patch row, and all the same width")
+        self.slabs, self.rows, group = [], [], []
+
+        def flush():
+            if group:
+                slab = torch.cat([slides[i]["wsi"] for i in group]).to(device=self.device, dtype=bag_dtype, non_blocking=True)
+                self.slabs.append(slab)
+                self.rows.extend(slab.split([self.lengths[i] for i in group]))
+                group.clear()
+        filled = 0
+        for i, m in enumerate(self.lengths):
+            if group and filled + m * row_bytes > slab_bytes:
+                flush()
+                filled = 0
+            group.append(i)
+            filled += m * row_bytes
+        flush()
+        self.table_ptrs, self.table_lens = SlideSet.slide_table(self.rows)
+        n_groups = len(slides[0]["omics"])
+        self.omics = [torch.stack([s["omics"][i] for s in slides]).to(self.device, non_blocking=True) for i in range(n_groups)]
+        self.labels = torch.tensor([s["survival_class"] for s in slides], dtype=torch.int64).to(self.device, non_blocking=True)
+        self.censorship = torch.tensor([float(s["censorship"]) for s in slides]).to(self.device, non_blocking=True)
+        self.survival_months = torch.tensor([float(s["survival_months"]) for s in slides],
+                                            dtype=torch.float64).to(self.device, non_blocking=True)
+
+    @property
+    def n_slides(self):
+        return len(self.lengths)
+
+    def window(self, ids_dev, ids_host, out=None):
+        """(SlideSet, omics, labels, cens) for the slides `ids_host` (host ints) = `ids_dev` (DEVICE int32, the same values; in
+        an epoch a slice of the uploaded order): the tuple a step takes.  omics, labels and censorship are selected on the
+        device, into `out` = (omics list, labels, cens) where given (a captured step's static tensors, step.window[1:]).
+        No H2D copy and no host synchronisation.  ids_dev and ids_host are the caller's two copies of one list; nothing
+        compares them (ops.SlideSet says what a mismatch does).  With `out`, the selects overwrite those tensors here, BEFORE
+        any step.bind() has looked at the window: if that bind then refuses, the step is left with the new omics, labels and
+        censorship beside the old rows -- validate first, as train_epoch does for the whole order, or leave `out` away and let
+        bind() copy."""
+        ids_host = [int(i) for i in ids_host]
+        for i in ids_host:
+            if not 0 <= i < self.n_slides:
+                raise ValueError(f"ResidentCohort.window: slide id {i} outside the cohort's {self.n_slides} slides")
+        bags = SlideSet([self.rows[i] for i in ids_host], [self.lengths[i] for i in ids_host], self.table_ptrs, self.table_lens,
+                        ids_dev, self.cycle)
+        o_omics, o_labels, o_cens = out if out is not None else ([None] * len(self.omics), None, None)
+        omics = [torch.index_select(x, 0, ids_dev, out=o) for x, o in zip(self.omics, o_omics)]
+        labels = torch.index_select(self.labels, 0, ids_dev, out=o_labels)
+        cens = torch.index_select(self.censorship, 0, ids_dev, out=o_cens)
+        return bags, omics, labels, cens
+
+
+def train_epoch(step: "GraphedWindowStep", cohort: ResidentCohort, order):
+    """One shuffled epoch of the captured, sampled step over a resident cohort.  `order`: host sequence of slide ids (the
+    epoch's permutation), validated once -- range, and every slide at least k rows unless the cohort laps -- and uploaded
+    once.  Per window of the step's slide count the loop enqueues: the bind (one tiny launch), the selects of omics, labels
+    and censorship into the step's static tensors, one replay, two device-to-device copies of loss and risk into
+    epoch-long buffers.  No host synchronisation and no H2D copy inside the loop.
+
+    Returns (loss, risk, ids_run, leftover): loss and risk (n_run,) fp32 and ids_run (n_run,) int32 on the device, in the
+    order the slides ran; `leftover` the host ids of the final partial window, which are NOT run (the graph has one
+    shape).  Run them eagerly where they matter:
+        bags, omics, labels, cens = cohort.window(torch.tensor(leftover, dtype=torch.int32, device=dev), leftover)
+        train_window(model, bags.materialize(), omics, labels, cens, grad_acc_step, sample_rows=k)
+    -- that eager path passes a slide shorter than k whole instead of lapping it.  After one synchronise,
+    concordance_index_censored(1 - cens[ids_run], months[ids_run], risk) is the epoch's C-index."""
+    if step.sampler is None or step.sampler.source != "slides" or step.ge:
+        raise ValueError("train_epoch: the step must be a fusion-model step captured with sample_rows on a ResidentCohort window")
+    n, k = step.sampler.n_slides, step.sampler.k
+    if (int(cohort.rows[0].shape[1]), cohort.rows[0].dtype) != (step.sampler.width, step.sampler.dtype):
+        raise ValueError(f"train_epoch: the cohort's rows are {int(cohort.rows[0].shape[1])} x {cohort.rows[0].dtype}, the step was "
+                         f"captured for {step.sampler.width} x {step.sampler.dtype}")
+    order = [int(i) for i in order]
+    for i in order:
+        if not 0 <= i < cohort.n_slides:
+            raise ValueError(f"train_epoch: slide id {i} outside the cohort's {cohort.n_slides} slides")
+        if not cohort.cycle and cohort.lengths[i] < k:
+            raise ValueError(f"train_epoch: slide {i} has {cohort.lengths[i]} rows, fewer than k = {k}, and the cohort does not lap "
+                             "short slides (cycle=False)")
+    n_win = len(order) // n
+    leftover = order[n_win * n:]
+    dev = cohort.device
+    order_dev = torch.tensor(order[:n_win * n], dtype=torch.int32).to(dev, non_blocking=True)
+    loss = torch.empty(n_win * n, dtype=torch.float32, device=dev)
+    risk = torch.empty(n_win * n, dtype=torch.float32, device=dev)
+    static = step.window[1:]
+    for w in range(n_win):
+        lo, hi = w * n, (w + 1) * n
+        step.bind(cohort.window(order_dev[lo:hi], order[lo:hi], out=static))
+        loss_w, risk_w = step()
+        loss[lo:hi].copy_(loss_w.view(-1), non_blocking=True)
+        risk[lo:hi].copy_(risk_w.view(-1), non_blocking=True)
+    return loss, risk, order_dev, leftover

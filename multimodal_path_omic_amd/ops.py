@@ -81,6 +81,19 @@ class BagBatch:
     def max_rows(self):
         return max(self.lengths)
 
+    # what a window of either kind (this one, SlideSet) says about its rows
+    @property
+    def width(self):
+        return int(self.data.shape[1])
+
+    @property
+    def dtype(self):
+        return self.data.dtype
+
+    @property
+    def device(self):
+        return self.data.device
+
     @staticmethod
     def from_list(bags: "List[torch.Tensor]") -> "BagBatch":
         lengths = [int(b.shape[0]) for b in bags]
@@ -108,6 +121,86 @@ class BagBatch:
             out.append(flat_map[n_q * off:n_q * (off + m)].view(n_q, m))
             off += m
         return out
+
+
+@dataclass
+class SlideSet:
+    """A window of SEPARATELY stored slides: what a shuffled epoch over a cohort resident on the device hands to the sampled
+    step instead of a contiguous BagBatch (harness.ResidentCohort.window; csrc/bag_sample_slides.hip gathers from it).
+
+    slides   per-slide (M_b, width) row tensors or views into slabs, in window order (kept alive here);
+    lengths  host list of M_b;
+    table_ptrs / table_lens  DEVICE int64 / int32 [n_table]: address of the first row and row count of every slide the ids
+             may name (a cohort's table, written once);
+    ids      DEVICE int32 [n_slides]: the window, as indices into the table (in practice a slice of the epoch's order);
+    cycle    a slide shorter than the sampler's k is lapped in its permuted order (row j <- pi_b(j mod M_b)) instead of
+             being passed whole, so the sampled window has the static shape (n_slides * k, width) whatever the lengths.
+    Only the row sampler reads a SlideSet; every bag kernel reads a contiguous window: materialize().
+    `slides` / `lengths` (host) and `ids` (device) must name the same slides: the host side decides what RowSampler.check
+    accepts and which lengths the output batch claims, the device side what the gather reads, and nothing compares the two (that
+    would be a host synchronisation per window).  A mismatch stays in bounds -- the kernel takes lengths and pointers from the
+    table alone -- but is silent: a static step would run on rows the batch's lengths do not describe.  ResidentCohort.window
+    and from_batch build both sides from one list."""
+    slides: List[torch.Tensor]
+    lengths: List[int]
+    table_ptrs: torch.Tensor
+    table_lens: torch.Tensor
+    ids: torch.Tensor
+    cycle: bool = False
+
+    def __post_init__(self):
+        self.lengths = [int(m) for m in self.lengths]
+        if len(self.lengths) == 0 or any(m <= 0 for m in self.lengths):
+            raise ValueError(f"every slide of a window needs at least one patch row (lengths {self.lengths[:8]}...)")
+        if len(self.slides) != len(self.lengths) or int(self.ids.numel()) != len(self.lengths):
+            raise ValueError(f"SlideSet: {len(self.slides)} slides, {len(self.lengths)} lengths and {int(self.ids.numel())} ids")
+        if self.ids.dtype != torch.int32 or self.table_lens.dtype != torch.int32 or self.table_ptrs.dtype != torch.int64:
+            raise ValueError("SlideSet: ids and table_lens are int32, table_ptrs int64 (device addresses)")
+        if self.table_ptrs.numel() != self.table_lens.numel():
+            raise ValueError("SlideSet: table_ptrs and table_lens differ in length")
+
+    @property
+    def n_slides(self):
+        return len(self.lengths)
+
+    @property
+    def n_table(self):
+        return int(self.table_lens.numel())
+
+    @property
+    def width(self):
+        return int(self.slides[0].shape[1])
+
+    @property
+    def dtype(self):
+        return self.slides[0].dtype
+
+    @property
+    def device(self):
+        return self.slides[0].device
+
+    @staticmethod
+    def slide_table(slides: "List[torch.Tensor]"):
+        """(table_ptrs int64, table_lens int32) on the slides' device for row tensors that stay where they are: one small
+        H2D copy each.  Every slide contiguous, (M, width), its first row 16-byte aligned."""
+        for i, x in enumerate(slides):
+            if x.dim() != 2 or not x.is_contiguous() or x.data_ptr() % 16:
+                raise ValueError(f"SlideSet: slide {i} must be a contiguous (M, width) tensor whose first row is 16-byte aligned")
+        dev = slides[0].device
+        return (torch.tensor([x.data_ptr() for x in slides], dtype=torch.int64).to(dev, non_blocking=True),
+                torch.tensor([int(x.shape[0]) for x in slides], dtype=torch.int32).to(dev, non_blocking=True))
+
+    @staticmethod
+    def from_batch(bags: "BagBatch", cycle: bool = False) -> "SlideSet":
+        """A contiguous window presented as separately addressed slides: views of its slides, identity ids."""
+        slides = list(bags.data.split(bags.lengths))
+        ptrs, lens = SlideSet.slide_table(slides)
+        ids = torch.arange(len(slides), dtype=torch.int32).to(bags.data.device, non_blocking=True)
+        return SlideSet(slides, list(bags.lengths), ptrs, lens, ids, bool(cycle))
+
+    def materialize(self) -> "BagBatch":
+        """The contiguous window, by one torch.cat: for whatever needs every row (eval mode)."""
+        return BagBatch.from_list(list(self.slides))
 
 
 class RaggedMaps(list):
@@ -1488,11 +1581,23 @@ class RowSampler:
     capture the offset is baked and the epoch (bumped inside the graph) advances the draw.  The sampler takes exactly ONE
     value of the generator's host counter per call -- the offset is a key, not a range of counters -- so
     GraphedWindowStep.rng_base and checkpoint.save / load see it like any other stream.  `last_stream` = (seed, offset) of
-    the most recent call, for tests/row_sampling_replay.py."""
+    the most recent call, for tests/row_sampling_replay.py.
+
+    source="slides": the sampler binds SlideSet windows (separately stored slides of a cohort resident on the device) and
+    gathers with csrc/bag_sample_slides.hip; same draw, keyed by the slide's position in the window.  A SlideSet with
+    `cycle` laps a slide shorter than k in its permuted order, so the output keeps lengths [k] * n_slides: static mode
+    accepts such a window, and refuses a short slide without `cycle` as it does for a BagBatch.  A sampler binds the
+    kind of window it was built for and refuses the other."""
 
     RNG_SPAN = 0            # _reserve(0): one counter value
+    SOURCES = {"window": (BagBatch, "mpo_bag_sample_desc_bytes", "mpo_bag_sample_rows"),
+               "slides": (SlideSet, "mpo_bag_sample_slides_desc_bytes", "mpo_bag_sample_slides")}
 
-    def __init__(self, n_slides: int, k: int, width: int, dtype, device, static: bool = True):
+    def __init__(self, n_slides: int, k: int, width: int, dtype, device, static: bool = True, source: str = "window"):
+        if source not in self.SOURCES:
+            raise ValueError(f"RowSampler: source '{source}' ({' | '.join(self.SOURCES)})")
+        self.source = source
+        self.window_type, desc_bytes, self.gather = self.SOURCES[source]
         n_slides, k, width = int(n_slides), int(k), int(width)
         if n_slides < 1 or k < 1:
             raise ValueError(f"RowSampler: n_slides {n_slides} and k {k} must be at least 1")
@@ -1504,7 +1609,7 @@ class RowSampler:
         self.n_slides, self.k, self.width, self.dtype, self.static = n_slides, k, width, dtype, bool(static)
         self.device = torch.device(device)
         self.out = torch.empty(n_slides * k, width, dtype=dtype, device=self.device)
-        self.desc = torch.zeros(L.lib().mpo_bag_sample_desc_bytes(n_slides) // 8, dtype=torch.int64, device=self.device)
+        self.desc = torch.zeros(getattr(L.lib(), desc_bytes)(n_slides) // 8, dtype=torch.int64, device=self.device)
         self.bound = None
         self.last_stream = None
         self.batch = None
@@ -1512,28 +1617,37 @@ class RowSampler:
             self.batch = BagBatch(self.out, make_cu([k] * n_slides, self.device), [k] * n_slides)
             self.batch.plan()
 
-    def check(self, bags: BagBatch):
+    def check(self, bags):
         """Raise ValueError with the reason when `bags` cannot be bound."""
-        x = bags.data
+        if not isinstance(bags, self.window_type):
+            raise ValueError(f"RowSampler: the sampler was built for {self.window_type.__name__} windows (source='{self.source}': its "
+                             f"descriptor and gather address the rows that way), not for a {type(bags).__name__}")
         if bags.n_slides != self.n_slides:
             raise ValueError(f"RowSampler: the window has {bags.n_slides} slides, the sampler was built for {self.n_slides}")
-        if x.dim() != 2 or int(x.shape[1]) != self.width:
-            raise ValueError(f"RowSampler: the window's rows are {tuple(x.shape)[1:]} wide, the sampler was built for width {self.width}")
-        if x.dtype != self.dtype:
-            raise ValueError(f"RowSampler: the window is stored as {x.dtype}, the sampler was built for {self.dtype}")
-        if self.static:
+        rows = bags.slides if self.source == "slides" else [bags.data]
+        for x in rows:
+            if x.dim() != 2 or int(x.shape[1]) != self.width:
+                raise ValueError(f"RowSampler: the window's rows are {tuple(x.shape)[1:]} wide, the sampler was built for width "
+                                 f"{self.width}")
+            if x.dtype != self.dtype:
+                raise ValueError(f"RowSampler: the window is stored as {x.dtype}, the sampler was built for {self.dtype}")
+        if self.static and not getattr(bags, "cycle", False):
             for b, m in enumerate(bags.lengths):
                 if m < self.k:
                     raise ValueError(f"RowSampler: slide {b} has {m} rows, fewer than k = {self.k} (static mode neither pads "
                                      "nor samples with replacement)")
 
-    def bind(self, bags: BagBatch):
+    def bind(self, bags):
         self.check(bags)
-        L.call("mpo_bag_sample_bind", L.ptr(self.desc), L.ptr(bags.data), L.ptr(bags.cu), self.n_slides, self.k,
-               L.stream_of(self.desc))
+        if self.source == "slides":
+            L.call("mpo_bag_sample_bind_slides", L.ptr(self.desc), L.ptr(bags.table_ptrs), L.ptr(bags.table_lens), bags.n_table,
+                   L.ptr(bags.ids), self.n_slides, self.k, int(bags.cycle), L.stream_of(self.desc))
+        else:
+            L.call("mpo_bag_sample_bind", L.ptr(self.desc), L.ptr(bags.data), L.ptr(bags.cu), self.n_slides, self.k,
+                   L.stream_of(self.desc))
         self.bound = bags
         if not self.static:
-            lengths = [min(self.k, int(m)) for m in bags.lengths]
+            lengths = [self.k if getattr(bags, "cycle", False) else min(self.k, int(m)) for m in bags.lengths]
             self.batch = BagBatch(self.out[:sum(lengths)], make_cu(lengths, self.device), lengths)
         return self
 
@@ -1543,7 +1657,7 @@ class RowSampler:
         seed, off = _reserve(self.RNG_SPAN)
         self.last_stream = (seed, off)
         self.batch.data.__dict__.pop("_mpo_feature_scale", None)        # (fp32: the rows are about to change under the cache)
-        L.call("mpo_bag_sample_rows", L.ptr(self.desc), self.n_slides, self.k, self.width, self.elem_bytes, seed, off,
+        L.call(self.gather, L.ptr(self.desc), self.n_slides, self.k, self.width, self.elem_bytes, seed, off,
                _epoch(), L.ptr(self.out), L.stream_of(self.out))
         return self.batch
 
