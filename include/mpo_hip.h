@@ -128,6 +128,7 @@ int mpo_patch_fc_forward(const void* patches, const int32_t* cu_rows, int n_slid
  *             accumulator (exact); pass 2^(15 - e) for max |X| = m 2^e, m in [0.5, 1) (ops.patch_fc_f32 derives and caches it
  *             per tensor) so that the features use fp16's range; 1.0 = unscaled (|x| in ~[1e-3, 1.3e5] then).  W_H is scaled
  *             by its own maximum inside the call.  Non-finite features stay non-finite in their rows of H_bag.
+ *             (mpo_feature_range.h: the same scale found on the device, and mpo_patch_fc_f32_forward_dev, which reads it there.)
  *   backward  d_weight = g^T X, d_bias = colsum(g) with g = d_h_bag (.) [H_bag > 0] * gate; gate = 1 / (1 - realised p)
  *             (1 without dropout); h_bag NULL: g = d_h_bag.  X needs no gradient (it is data).
  * workspace: caller-owned, mpo_patch_fc_f32_workspace_bytes(backward) bytes. */
@@ -558,6 +559,10 @@ int mpo_coattn_bwd_bagpass(const void* bag, int bag_dtype, const int32_t* cu_row
 
 /* ---- patch sampling from a cohort resident on the device (csrc/bag_sample_slides.hip): likewise additive to ABI 14. */
 #include "mpo_cohort.h"
+
+/* ---- an fp32 window's feature scale found and read on the device (csrc/feature_range.hip, csrc/patch_fc_f32.hip): likewise
+ * additive to ABI 14. */
+#include "mpo_feature_range.h"
 
 #ifdef __cplusplus
 }

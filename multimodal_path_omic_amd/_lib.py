@@ -23,6 +23,9 @@ COMPANION_HEADER_PATHS = [os.path.join(os.path.dirname(_HERE), "include", name)
 # Headers registered after that list was closed in its turn (companion_symbols() and all_companion_symbols() keep naming what
 # they named): same rules, same binding, their own accessor later_symbols().
 LATER_HEADER_PATHS = [os.path.join(os.path.dirname(_HERE), "include", name) for name in ("mpo_cohort.h",)]
+# Every header registered since (the two lists above are pinned by name in the CPU suite): an open list, one accessor for
+# all of it, header_symbols().  A new companion header of mpo_hip.h goes here.
+MORE_HEADER_PATHS = [os.path.join(os.path.dirname(_HERE), "include", name) for name in ("mpo_feature_range.h",)]
 
 # The closed map from the header's scalar parameter types; a new scalar type in the header needs a new line here.
 _SCALARS = {"int": c_int, "int32_t": c_int, "int64_t": c_int64, "uint64_t": c_uint64, "size_t": c_size_t, "float": c_float,
@@ -109,6 +112,7 @@ OPTIM = {k[len("MPO_OPTIM_"):].lower(): v for k, v in _constants.items() if k.st
 GEMM_ROUTE = {k[len("MPO_GEMM_ROUTE_"):].lower(): v for k, v in _constants.items() if k.startswith("MPO_GEMM_ROUTE_")}
 _companion_signatures, _companion_names = _read_companions(COMPANION_HEADER_PATHS, _signatures)
 _later_signatures, _later_names = _read_companions(LATER_HEADER_PATHS, {**_signatures, **_companion_signatures})
+_more_signatures, _more_names = _read_companions(MORE_HEADER_PATHS, {**_signatures, **_companion_signatures, **_later_signatures})
 
 
 class BagPlanC(ctypes.Structure):
@@ -142,6 +146,12 @@ def later_symbols(header: "str | None" = None):
     return list(_later_signatures) if header is None else list(_later_names[header])
 
 
+def header_symbols(header: str):
+    """The entries of the header `header` of MORE_HEADER_PATHS (file name), in declaration order: exported and bound like
+    every other entry."""
+    return list(_more_names[header])
+
+
 def check_abi_version(found: int, expected: int):
     if found != expected:
         raise RuntimeError(f"{LIB_PATH} reports ABI version {found}, include/mpo_hip.h describes {expected}: the library is "
@@ -155,7 +165,7 @@ def lib():
             raise RuntimeError(
                 f"{LIB_PATH} is missing: the HIP extension has not been built ({_REBUILD}). There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**_signatures, **_companion_signatures, **_later_signatures}.items():
+        for name, (res, args) in {**_signatures, **_companion_signatures, **_later_signatures, **_more_signatures}.items():
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

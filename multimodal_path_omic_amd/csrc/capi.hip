@@ -271,17 +271,33 @@ int mpo_patch_fc_forward(const void* patches, const int32_t* cu_rows, int n_slid
 size_t mpo_patch_fc_f32_workspace_bytes(int backward) {
     return one_block_workspace_bytes(backward ? mpo_patch_wgrad_f32_workspace_floats() : mpo_patch_fc_f32_workspace_floats());
 }
-int mpo_patch_fc_f32_forward(const float* patches, int64_t total_rows, int patch_dim, const float* patch_weight,
-                             const float* patch_bias, int embed, float drop_p, uint64_t seed, uint64_t offset,
-                             const uint64_t* rng_epoch, float x_scale, float* h_bag, void* workspace, size_t workspace_bytes,
-                             mpo_stream_t stream) {
+// x_scale by value, or (x_scale_dev non-NULL) read on the device when the kernel starts: one kernel, the same bits
+static int patch_fc_f32_forward(const float* patches, int64_t total_rows, int patch_dim, const float* patch_weight,
+                                const float* patch_bias, int embed, float drop_p, uint64_t seed, uint64_t offset,
+                                const uint64_t* rng_epoch, float x_scale, const float* x_scale_dev, float* h_bag, void* workspace,
+                                size_t workspace_bytes, mpo_stream_t stream) {
     MPO_CHECK(patches && patch_weight && patch_bias && h_bag, "fp32 patch layer: null operand");
     MPO_CHECK(total_rows >= 1, "fp32 patch layer: total_rows %lld", (long long)total_rows);
     WsCarve ws(workspace, workspace_bytes);
     float* wpk = ws.floats(mpo_patch_fc_f32_workspace_floats());
     MPO_CHECK(ws.ok(), "fp32 patch layer: workspace too small (%zu bytes)", workspace_bytes);
     return mpo_launch_patch_fc_f32(patches, patch_weight, patch_bias, h_bag, total_rows, embed, patch_dim, drop_p, seed, offset,
-                                   reinterpret_cast<const unsigned long long*>(rng_epoch), x_scale, wpk, stream);
+                                   reinterpret_cast<const unsigned long long*>(rng_epoch), x_scale, x_scale_dev, wpk, stream);
+}
+int mpo_patch_fc_f32_forward(const float* patches, int64_t total_rows, int patch_dim, const float* patch_weight,
+                             const float* patch_bias, int embed, float drop_p, uint64_t seed, uint64_t offset,
+                             const uint64_t* rng_epoch, float x_scale, float* h_bag, void* workspace, size_t workspace_bytes,
+                             mpo_stream_t stream) {
+    return patch_fc_f32_forward(patches, total_rows, patch_dim, patch_weight, patch_bias, embed, drop_p, seed, offset, rng_epoch,
+                                x_scale, nullptr, h_bag, workspace, workspace_bytes, stream);
+}
+int mpo_patch_fc_f32_forward_dev(const float* patches, int64_t total_rows, int patch_dim, const float* patch_weight,
+                                 const float* patch_bias, int embed, float drop_p, uint64_t seed, uint64_t offset,
+                                 const uint64_t* rng_epoch, const float* x_scale, float* h_bag, void* workspace,
+                                 size_t workspace_bytes, mpo_stream_t stream) {
+    MPO_CHECK(x_scale, "fp32 patch layer: null device scale (mpo_feature_range_f32 writes it)");
+    return patch_fc_f32_forward(patches, total_rows, patch_dim, patch_weight, patch_bias, embed, drop_p, seed, offset, rng_epoch,
+                                1.0f, x_scale, h_bag, workspace, workspace_bytes, stream);
 }
 int mpo_patch_fc_f32_backward(const float* d_h_bag, const float* h_bag, const float* patches, int64_t total_rows, int embed,
                               int patch_dim, float gate, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes,

@@ -35,6 +35,19 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
 }
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
+    return v;
+}
+// The power of two that puts max |v| into [2^14, 2^15) (1 for an all-zero or non-finite maximum): the scale the fp16 operand
+// splits of patch_fc_f32.hip take for W_H and for X (feature_range.hip).
+__device__ __forceinline__ float range_scale(float vmax) {
+    if (!(vmax > 0.f) || !(vmax < INFINITY)) return 1.0f;
+    int e;
+    (void)frexpf(vmax, &e);                     // vmax = m 2^e, m in [0.5, 1)
+    return ldexpf(1.0f, min(max(15 - e, -100), 100));
+}
 
 // ---- counter-based RNG for dropout masks (seed + 64-bit element counter) ----
 // philox4x32 (Philox4x32-10) is kept for the one pass-bound kernel that still calls it (the bf16 patch epilogue of the library

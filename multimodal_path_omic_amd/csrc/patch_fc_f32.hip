@@ -64,7 +64,8 @@ __device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, bf16x8& h
 // fp16 hi / lo split of eight floats, round-to-nearest both (hi + lo carries 22 significand bits, the dropped lo * lo term
 // is 2^-22 of the product).  Range: both operands arrive scaled by a power of two that puts their largest magnitude at
 // 2^14 .. 2^15 (W_H: from its own maximum, found on the device per call; X: x_scale, which the caller derives from the window's
-// maximum -- ops.patch_fc_f32 caches it per tensor), so finite data never reach the fp16 limit and small features keep
+// maximum -- ops.patch_fc_f32 caches it per tensor -- or leaves on the device, feature_range.hip, for the kernel to read
+// through x_scale_dev), so finite data never reach the fp16 limit and small features keep
 // their bits (unscaled, features of ~1e-4 sat in fp16 subnormals: ~3e-4 relative).  The clamp only matters for a caller
 // that passes no scale (x_scale = 1: |x| up to 1.3e5 is carried by hi + lo, beyond that clipped).  NaN and infinities are
 // NOT clamped away: v - v is 0 for finite v and NaN otherwise, so a non-finite feature makes its row of H_bag non-finite,
@@ -81,14 +82,8 @@ __device__ __forceinline__ void split8h(const f32x4& a, const f32x4& b, float sc
     }
 }
 __device__ __forceinline__ f32x4 mfma_f16(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-// The power of two that puts max |v| into [2^14, 2^15) (1 for an all-zero or non-finite maximum).
-__device__ __forceinline__ float range_scale(float vmax) {
-    if (!(vmax > 0.f) || !(vmax < INFINITY)) return 1.0f;
-    int e;
-    (void)frexpf(vmax, &e);                     // vmax = m 2^e, m in [0.5, 1)
-    return ldexpf(1.0f, min(max(15 - e, -100), 100));
-}
-// scale of W_H for this call -> *scale_out (one workgroup of 1024 threads over the 256 x 1024 weight)
+// scale of W_H for this call -> *scale_out = range_scale (mpo_common.h) of its maximum (one workgroup of 1024 threads over the
+// 256 x 1024 weight)
 __global__ void weight_range_kernel(const float* __restrict__ w, float* __restrict__ scale_out) {
     __shared__ float red[16];
     float m = 0.f;
@@ -131,8 +126,11 @@ void patch_fc_f32_kernel(const float* __restrict__ x,             // [total_rows
                          float* __restrict__ h,                   // [total_rows][256]
                          long long total_rows, int rows_per_wg, float drop_p, unsigned long long seed,
                          unsigned long long offset_, const unsigned long long* __restrict__ epoch,
-                         float x_scale, const float* __restrict__ w_scale) {
+                         float x_scale_arg, const float* __restrict__ x_scale_dev,      // the scale by value, or (non-NULL) read here
+                         const float* __restrict__ w_scale) {
     __shared__ __attribute__((aligned(1024))) char lds[2 * 2 * FIMG];         // [stage][hi | lo]
+    // (wave-uniform either way: one scalar load at kernel start, as *w_scale below)
+    const float x_scale = x_scale_dev != nullptr ? *x_scale_dev : x_scale_arg;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -444,10 +442,11 @@ size_t mpo_patch_wgrad_f32_workspace_floats() { return (size_t)GRANGES * FE * FK
 
 int mpo_launch_patch_fc_f32(const float* x, const float* w, const float* bias, float* h, long long total_rows, int embed,
                             int patch_dim, float drop_p, unsigned long long seed, unsigned long long offset,
-                            const unsigned long long* epoch, float x_scale, float* ws, hipStream_t stream) {
+                            const unsigned long long* epoch, float x_scale, const float* x_scale_dev, float* ws,
+                            hipStream_t stream) {
     MPO_CHECK(embed == FE && patch_dim == FK, "fp32 patch layer kernel: built for %d -> %d (got %d -> %d)", FK, FE, patch_dim, embed);
     MPO_CHECK(drop_p >= 0.f && drop_p < 1.f, "patch-layer dropout p must be in [0,1) (got %f)", (double)drop_p);
-    {
+    if (x_scale_dev == nullptr) {              // (a device scale cannot be looked at here: it must hold what mpo_feature_range_f32 wrote)
         int e = 0;
         MPO_CHECK(x_scale > 0.f && x_scale < INFINITY && frexpf(x_scale, &e) == 0.5f, "fp32 patch layer: x_scale must be a power of two (got %g)", (double)x_scale);
     }
@@ -462,7 +461,7 @@ int mpo_launch_patch_fc_f32(const float* x, const float* w, const float* bias, f
     per = (per + FBM - 1) / FBM * FBM;
     const int grid = (int)((total_rows + per - 1) / per);
     patch_fc_f32_kernel<MPO_F32_FWD_WAVES><<<grid, 64 * MPO_F32_FWD_WAVES, 0, stream>>>(x, reinterpret_cast<const f16x8*>(ws), bias, h, total_rows, (int)per, drop_p, seed,
-                                                   offset, epoch, x_scale, w_scale);
+                                                   offset, epoch, x_scale, x_scale_dev, w_scale);
     MPO_LAUNCH_CHECK();
     return 0;
 }

@@ -240,7 +240,10 @@ class GraphedWindowStep:
 
     Static inputs: the window's tensors are resident and fixed (one captured graph per resident window).  An fp32 window's
     feature scale (ops.feature_scale) is baked into the graph as a kernel argument: a replay after an in-place write to
-    that window raises instead of computing with the stale scale.
+    that window raises instead of computing with the stale scale.  With device_feature_scale=True the body starts, behind
+    the counter bump, with the range pass over the whole window (ops.feature_scale_device: three tiny launches) and the
+    patch layer reads the scale through a pointer: a replay follows whatever the window holds -- rows that
+    ingest.WindowFeeder or copy_ refilled in place -- and never raises.
     Frozen-at-capture values that must change per step live on the device: the dropout epoch (ops.set_rng_epoch,
     bumped inside the graph) and Adam's step count (dp.FlatAdam.t_dev).  With world_size > 1 leave the optimiser
     out (`opt=None`): replay, then all-reduce the bucket and step eagerly.
@@ -253,7 +256,13 @@ class GraphedWindowStep:
     replay's sample and masks share its epoch) with the gather of ops.RowSampler -- k rows of every slide into a buffer of
     static shape -- and everything behind it sees the same lengths, plan and grids whatever window the sampler reads.
     bind(window) then re-points the captured step at another window of the same slide count, width and dtype with at least
-    k rows per slide; every replay draws a fresh sample (the device epoch).  bf16 windows, model in training mode.
+    k rows per slide; every replay draws a fresh sample (the device epoch).  Model in training mode.  bf16 windows, and
+    with device_feature_scale=True fp32 windows: the captured body is counter bump, gather, range pass over the sample
+    (the sampler's, `step.sampler.scale`), then the step -- the scale is that of the rows the step runs on, as the eager
+    sampled path finds it on the host.  A window with a non-finite value runs unscaled (scale 1; its rows of H_bag come
+    out non-finite, as ever).  An fp32 window that never reaches the scaled kernel (small / big models, patch_dim 512 /
+    2048: the exact-fp32 GEMM) has no scale: the flag only lifts the refusal, `step.sampler.scale` is None.  A step binds
+    windows of the dtype it was captured on.
 
     A window whose first element is an ops.SlideSet (ResidentCohort.window) captures the gather from separately stored
     slides instead: bind() then takes further SlideSet windows -- slide ids into a cohort that lives on the device, no copy
@@ -264,7 +273,7 @@ class GraphedWindowStep:
     def __init__(self, model, bucket, window, grad_acc_step: int, opt=None, warmup: int = 2, pool=None,
                  split_patch_grad: bool = False, prime: bool = True, loss: str = "ces", alpha: float = 0.75,
                  lambda_reg: float = 0.01, l1: "float | None" = None, rng_base: "int | None" = None,
-                 sample_rows: "int | None" = None):
+                 device_feature_scale: bool = False, sample_rows: "int | None" = None):
         """split_patch_grad (data-parallel steps, opt=None): the patch layer's weight gradient -- a 0.3 ms GEMM nobody
         downstream waits for -- is captured into a SECOND graph, `replay_tail()`.  The caller replays the main graph,
         starts the all-reduce of every other gradient (bucket.all_reduce_mean_async(lo=head)), replays the tail while
@@ -275,10 +284,15 @@ class GraphedWindowStep:
         counter stands after the warm-up).  The capture bakes stream offsets taken from that counter into the graph, so
         a step re-captured in another process at the `rng_base` the original reports (self.rng_base, stored by
         checkpoint.save) draws the masks the original would have drawn, whatever ran before; on return the counter
-        stands at the larger of its value on entry and the end of the captured streams."""
+        stands at the larger of its value on entry and the end of the captured streams.
+        device_feature_scale (fp32 windows; nothing changes for bf16): the feature scale of the rows the step runs on is
+        found inside the graph (ops.feature_scale_device) and read by the patch layer through a pointer, instead of being
+        baked in as a number -- the class docstring says what that lifts."""
         from . import ops
         calls_on_entry = ops._rng_calls
         self.model, self.bucket, self.opt = model, bucket, opt
+        self.device_feature_scale = bool(device_feature_scale)
+        self.scale = None                                   # an unsampled fp32 step's own (1,) scale tensor
         self.l1 = float(getattr(opt, "l1_lambda", 0.0) if l1 is None else l1)
         self.train_kwargs = dict(loss=loss, alpha=alpha, lambda_reg=lambda_reg, l1=self.l1)
         self.window, self.acc = window, grad_acc_step
@@ -300,12 +314,15 @@ class GraphedWindowStep:
                 raise ValueError(f"GraphedWindowStep(sample_rows={sample_rows}): {reason}")
             bags = window[0]
             self.sampler = ops.RowSampler(bags.n_slides, int(sample_rows), bags.width, bags.dtype, bags.device,
+                                          device_feature_scale=self._scaled(bags),
                                           source="slides" if isinstance(bags, SlideSet) else "window").bind(bags)
         else:
             if isinstance(window[0], SlideSet):
                 raise ValueError("GraphedWindowStep: a SlideSet window is read by the row sampler alone (sample_rows=k); every "
                                  "bag kernel reads a contiguous window -- materialize() it for an unsampled step")
             window[0].plan()                  # the work plan's H2D copy must not happen inside the capture
+            if self._scaled(window[0]):
+                self.scale = torch.ones(1, dtype=torch.float32, device=window[0].device)
         dev = bucket.flat.device
         if ops._rng_epoch_tensor is None:
             ops.set_rng_epoch(torch.zeros(1, dtype=torch.int64, device=dev))
@@ -328,8 +345,10 @@ class GraphedWindowStep:
         if rng_base is not None:
             ops._rng_calls = int(rng_base)
         self.rng_base = ops._rng_calls
-        # (a sampled step refuses fp32 windows: only an unsampled step's BagBatch gets here with one)
-        self._fp32_window_version = window[0].data._version if window[0].dtype == torch.float32 else None
+        # (without device_feature_scale a sampled step refuses fp32 windows: only an unsampled step's BagBatch gets here with
+        #  one, and the scale its graph bakes in is that of the window's contents now)
+        baked = window[0].dtype == torch.float32 and not self.device_feature_scale
+        self._fp32_window_version = window[0].data._version if baked else None
         # thread_local: other threads (RCCL's watchdog under torch.distributed) may issue HIP calls meanwhile
         with torch.cuda.graph(self.graph, pool=pool, capture_error_mode="thread_local"):
             out = self._body(flush=not self.split)
@@ -360,16 +379,22 @@ class GraphedWindowStep:
         from . import ops
         ops.bump_step_counters(self.epoch, self.opt.t_dev if self.opt is not None else None)   # one launch for both
         bags = self.window[0] if self.sampler is None else self.sampler()
+        if self.scale is not None:
+            # the range pass over the whole window as it is at this replay; the window carries the result for the length of
+            # the body only (an eager step on the same tensor afterwards finds its scale on the host, as ever)
+            bags.data._mpo_feature_scale_dev = ops.feature_scale_device(bags.data, out=self.scale)
         self.bucket.begin()
-        if self.ge:
-            out = train_ge_window(self.model, bags, self.window[1], self.acc, l1=self.l1)
-        else:
-            _, omics, labels, cens = self.window
-            ops.defer_patch_weight_grad = self.split
-            try:
+        try:
+            if self.ge:
+                out = train_ge_window(self.model, bags, self.window[1], self.acc, l1=self.l1)
+            else:
+                _, omics, labels, cens = self.window
+                ops.defer_patch_weight_grad = self.split
                 out = train_window(self.model, bags, omics, labels, cens, self.acc, **self.train_kwargs)
-            finally:
-                ops.defer_patch_weight_grad = False
+        finally:
+            ops.defer_patch_weight_grad = False
+            if self.scale is not None:
+                del bags.data._mpo_feature_scale_dev
         self.bucket.finish()
         if self.split and flush:
             ops.flush_patch_weight_grads()
@@ -380,11 +405,19 @@ class GraphedWindowStep:
                 self.opt.step(bump=False)
         return out
 
+    def _scaled(self, bags) -> bool:
+        """Whether the step finds a feature scale on the device: device_feature_scale, and an fp32 window that reaches
+        mpo_patch_fc_f32 (Linear(1024, 256); the small / big models and patch_dim 512 / 2048 run the exact-fp32 GEMM, which
+        has no scale -- for them the flag only lifts the refusals)."""
+        from . import ops
+        probe = torch.empty(0, bags.width, dtype=bags.dtype, device=bags.device)
+        return self.device_feature_scale and ops.patch_fc_f32_supported(probe, self.model.H[0].weight)
+
     def _sampling_refusal(self, bags, k: int) -> "str | None":
         """Why a sampled step cannot run on `bags` (None: it can)."""
-        if bags.dtype == torch.float32:
+        if bags.dtype == torch.float32 and not self.device_feature_scale:
             return ("an fp32 window's feature scale is baked into the graph as a kernel argument; the sampled step is built "
-                    "for bf16 windows")
+                    "for bf16 windows (device_feature_scale=True finds the scale inside the graph instead)")
         if not self.model.training:
             return ("the model is in eval mode, where the whole window is passed through (validation sees every patch): "
                     "nothing a re-pointable graph could capture")
@@ -398,7 +431,8 @@ class GraphedWindowStep:
         labels and censorship are copied into the tensors the graph reads.  No host synchronisation.  The window's rows
         must stay valid until the replays that read them have finished.  Raises ValueError with the reason when the
         window does not fit the capture: another slide count, a slide shorter than k (unless a SlideSet laps it), another
-        width or dtype, fp32, a BagBatch for a step captured on a SlideSet or the reverse.  A refused bind changes nothing."""
+        width or dtype, fp32 for a step captured without device_feature_scale, a BagBatch for a step captured on a SlideSet
+        or the reverse.  A refused bind changes nothing."""
         if self.sampler is None:
             raise ValueError("GraphedWindowStep.bind: the step was captured without sample_rows -- its graph reads one "
                              "resident window's rows directly")
@@ -439,14 +473,16 @@ class GraphedWindowStep:
     def __call__(self):
         if self._fp32_window_version is not None and self.window[0].data._version != self._fp32_window_version:
             raise RuntimeError("GraphedWindowStep: the fp32 window was written in place after capture; its feature scale "
-                               "is baked into the graph -- capture a new step for the new contents")
+                               "is baked into the graph -- capture a new step for the new contents (or capture with "
+                               "device_feature_scale=True)")
         self.graph.replay()
         return self.loss if self.ge else (self.loss, self.risk)
 
 
 # ------------------------------------------------------------------------------------ a cohort resident on the device
 class ResidentCohort:
-    """A cohort that lives on the device once, for shuffled epochs of the sampled, captured step: every slide's rows (in
+    """A cohort that lives on the device once, for shuffled epochs of the sampled, captured step (bag_dtype bf16, or fp32
+    for a step captured with device_feature_scale=True): every slide's rows (in
     slabs of at most `slab_bytes`, a slide never split), the pointer / length table csrc/bag_sample_slides.hip is addressed
     through, omics per group (N, d_i), labels, censorship and survival_months (all (N,)).  A window is a list of slide ids:
     nothing is copied to form it and nothing crosses PCIe (1 000 slides of 15 000 x 1024 bf16 are 30 GB).
@@ -517,7 +553,8 @@ class ResidentCohort:
 
 
 def train_epoch(step: "GraphedWindowStep", cohort: ResidentCohort, order):
-    """One shuffled epoch of the captured, sampled step over a resident cohort.  `order`: host sequence of slide ids (the
+    """One shuffled epoch of the captured, sampled step over a resident cohort, bf16 or fp32 (an fp32 step is captured with
+    device_feature_scale=True: every window's sample gets its own scale inside the graph).  `order`: host sequence of slide ids (the
     epoch's permutation), validated once -- range, and every slide at least k rows unless the cohort laps -- and uploaded
     once.  Per window of the step's slide count the loop enqueues: the bind (one tiny launch), the selects of omics, labels
     and censorship into the step's static tensors, one replay, two device-to-device copies of loss and risk into

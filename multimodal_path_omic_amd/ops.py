@@ -516,8 +516,13 @@ class PatchFcF32Fn(torch.autograd.Function):
         h = torch.empty(x.shape[0], weight.shape[0], device=x.device, dtype=torch.float32)
         seed, off = _reserve(h.numel() // 16 + 2) if drop_p > 0 else (0, 0)
         ws = _workspace(lib.mpo_patch_fc_f32_workspace_bytes(0), x.device)
-        L.call("mpo_patch_fc_f32_forward", L.ptr(x), x.shape[0], x.shape[1], L.ptr(weight), L.ptr(bias), weight.shape[0],
-               float(drop_p), seed, off, _epoch(), feature_scale(x), L.ptr(h), L.ptr(ws), ws.numel(),
+        # a window that carries a device scale (feature_scale_device: a sampler's output, a captured step's window) is read
+        # through it when the kernel starts; any other window's scale is found on the host and passed by value
+        scale_dev = getattr(x, "_mpo_feature_scale_dev", None)
+        entry, scale = ("mpo_patch_fc_f32_forward", feature_scale(x)) if scale_dev is None else \
+                       ("mpo_patch_fc_f32_forward_dev", L.ptr(_check_scale_tensor(scale_dev, x)))
+        L.call(entry, L.ptr(x), x.shape[0], x.shape[1], L.ptr(weight), L.ptr(bias), weight.shape[0],
+               float(drop_p), seed, off, _epoch(), scale, L.ptr(h), L.ptr(ws), ws.numel(),
                L.stream_of(x))
         ctx.save_for_backward(x, h)
         ctx.param_refs = (weight, bias)
@@ -540,7 +545,7 @@ def feature_scale(x) -> float:
     """The power of two that puts max |x| of an fp32 patch matrix into [2^14, 2^15): the fp16 operand splits of
     mpo_patch_fc_f32_forward then use fp16's range whatever the features' own scale (1e-4 or 1e4).  One reduction over the
     window and one host read, cached on the tensor (a resident window is scanned once; call it -- or one eager forward --
-    before capturing a graph).
+    before capturing a graph).  feature_scale_device finds the same number without the host read.
 
     The cache is keyed on the tensor's version counter, storage address and shape: an in-place write (mul_, copy_, a write
     through any view of the same base -- views share the counter) makes the next call scan again.  Inference tensors have
@@ -564,6 +569,27 @@ def feature_scale(x) -> float:
         except AttributeError:
             pass
     return s
+
+
+def _check_scale_tensor(scale, x):
+    if scale.shape != (1,) or scale.dtype != torch.float32 or scale.device != x.device or not scale.is_contiguous():
+        raise ValueError(f"a device feature scale is one contiguous fp32 value on the window's device (got {tuple(scale.shape)} "
+                         f"{scale.dtype} on {scale.device})")
+    return scale
+
+
+def feature_scale_device(x, out=None) -> torch.Tensor:
+    """feature_scale(x) found on the device (csrc/feature_range.hip) -> a (1,) fp32 tensor on x's device (`out`, written
+    in place, where given): the same bits for every x, with no full-size temporary and NO host read -- three tiny launches
+    on the current stream, allowed inside a stream capture.  Nothing is cached: every call reads x as it is then.
+    mpo_patch_fc_f32_forward_dev reads the result when its kernel starts; a window carries it as
+    x._mpo_feature_scale_dev (PatchFcF32Fn.forward), beside the host cache _mpo_feature_scale."""
+    if not x.is_cuda or x.dtype != torch.float32:
+        raise ValueError(f"feature_scale_device: an fp32 tensor on the GPU (got {x.dtype} on {x.device})")
+    out = torch.empty(1, dtype=torch.float32, device=x.device) if out is None else _check_scale_tensor(out, x)
+    ws = _workspace(L.lib().mpo_feature_range_workspace_bytes(), x.device)
+    L.call("mpo_feature_range_f32", L.ptr(x) if x.numel() else None, x.numel(), L.ptr(out), L.ptr(ws), ws.numel(), L.stream_of(x))
+    return out
 
 
 def patch_fc_f32_supported(x, weight) -> bool:
@@ -1587,13 +1613,19 @@ class RowSampler:
     gathers with csrc/bag_sample_slides.hip; same draw, keyed by the slide's position in the window.  A SlideSet with
     `cycle` laps a slide shorter than k in its permuted order, so the output keeps lengths [k] * n_slides: static mode
     accepts such a window, and refuses a short slide without `cycle` as it does for a BagBatch.  A sampler binds the
-    kind of window it was built for and refuses the other."""
+    kind of window it was built for and refuses the other.
+
+    device_feature_scale=True on an fp32 sampler: it owns `scale`, a (1,) fp32 tensor, runs feature_scale_device over the
+    rows it wrote after EVERY gather, eager or captured, and tags the output batch's data with it
+    (_mpo_feature_scale_dev), so that the fp32 patch layer reads the sample's scale on the device -- no host read, nothing
+    baked into a graph.  On a bf16 sampler, and without the flag, `scale` is None and nothing is added."""
 
     RNG_SPAN = 0            # _reserve(0): one counter value
     SOURCES = {"window": (BagBatch, "mpo_bag_sample_desc_bytes", "mpo_bag_sample_rows"),
                "slides": (SlideSet, "mpo_bag_sample_slides_desc_bytes", "mpo_bag_sample_slides")}
 
-    def __init__(self, n_slides: int, k: int, width: int, dtype, device, static: bool = True, source: str = "window"):
+    def __init__(self, n_slides: int, k: int, width: int, dtype, device, static: bool = True,
+                 device_feature_scale: bool = False, source: str = "window"):
         if source not in self.SOURCES:
             raise ValueError(f"RowSampler: source '{source}' ({' | '.join(self.SOURCES)})")
         self.source = source
@@ -1613,9 +1645,17 @@ class RowSampler:
         self.bound = None
         self.last_stream = None
         self.batch = None
+        # fp32 with device_feature_scale: the (1,) scale of the rows the last gather wrote; None: no range pass
+        self.scale = (torch.ones(1, dtype=torch.float32, device=self.device)
+                      if device_feature_scale and dtype == torch.float32 else None)
         if self.static:
-            self.batch = BagBatch(self.out, make_cu([k] * n_slides, self.device), [k] * n_slides)
+            self._set_batch(BagBatch(self.out, make_cu([k] * n_slides, self.device), [k] * n_slides))
             self.batch.plan()
+
+    def _set_batch(self, batch):
+        self.batch = batch
+        if self.scale is not None:
+            batch.data._mpo_feature_scale_dev = self.scale
 
     def check(self, bags):
         """Raise ValueError with the reason when `bags` cannot be bound."""
@@ -1648,7 +1688,7 @@ class RowSampler:
         self.bound = bags
         if not self.static:
             lengths = [self.k if getattr(bags, "cycle", False) else min(self.k, int(m)) for m in bags.lengths]
-            self.batch = BagBatch(self.out[:sum(lengths)], make_cu(lengths, self.device), lengths)
+            self._set_batch(BagBatch(self.out[:sum(lengths)], make_cu(lengths, self.device), lengths))
         return self
 
     def __call__(self) -> BagBatch:
@@ -1659,6 +1699,8 @@ class RowSampler:
         self.batch.data.__dict__.pop("_mpo_feature_scale", None)        # (fp32: the rows are about to change under the cache)
         L.call(self.gather, L.ptr(self.desc), self.n_slides, self.k, self.width, self.elem_bytes, seed, off,
                _epoch(), L.ptr(self.out), L.stream_of(self.out))
+        if self.scale is not None:            # over the rows the gather just wrote (ocu[n_slides] of them: the batch's)
+            feature_scale_device(self.batch.data, out=self.scale)
         return self.batch
 
 
