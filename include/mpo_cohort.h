@@ -11,7 +11,7 @@ extern "C" {
 #endif
 
 /* The gather of mpo_bag_sample.h for a window whose slides are stored SEPARATELY: a window is n_slides ids into a table of
- * slides that lives on the device, so a shuffled epoch never assembles a contiguous window (csrc/bag_sample_slides.hip).
+ * slides that lives on the device, so a shuffled epoch never assembles a contiguous window (csrc/bag_sample.hip).
  * The draw is the same: pi_b keyed by the slide's POSITION b in the window and its length M_b, so the same slides in the
  * same order with the same (seed, offset, *rng_epoch) give the bits mpo_bag_sample_rows gives on their concatenation.
  * Slides are addressed by pointer: the cohort's total row count has no 32-bit limit (a slide's own rows and the window's

@@ -557,7 +557,7 @@ int mpo_coattn_bwd_bagpass(const void* bag, int bag_dtype, const int32_t* cu_row
 /* ---- gated-concat fusion + head in one call each way (csrc/fusion_next.hip): likewise additive to ABI 14. */
 #include "mpo_fusion_next.h"
 
-/* ---- patch sampling from a cohort resident on the device (csrc/bag_sample_slides.hip): likewise additive to ABI 14. */
+/* ---- patch sampling from a cohort resident on the device (csrc/bag_sample.hip, the same gather): likewise additive to ABI 14. */
 #include "mpo_cohort.h"
 
 /* ---- an fp32 window's feature scale found and read on the device (csrc/feature_range.hip, csrc/patch_fc_f32.hip): likewise

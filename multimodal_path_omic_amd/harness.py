@@ -86,12 +86,10 @@ def sample_window_rows(model, bags, sample_rows) -> BagBatch:
     A SlideSet (separately stored slides) is gathered from where its slides lie (with `cycle`: sample_rows rows of every
     slide, short ones lapped); wherever the whole window is needed -- eval mode, no sample_rows -- it is materialized by one
     torch.cat, since every bag kernel reads a contiguous window."""
-    slides = isinstance(bags, SlideSet)
     if not sample_rows or not model.training:
-        return bags.materialize() if slides else bags
+        return bags.materialize() if isinstance(bags, SlideSet) else bags
     from . import ops
-    return ops.RowSampler(bags.n_slides, int(sample_rows), bags.width, bags.dtype, bags.device, static=False,
-                          source="slides" if slides else "window").bind(bags)()
+    return ops.RowSampler.for_window(bags, sample_rows, static=False).bind(bags)()
 
 
 def train_ge_window(model, bags: BagBatch, labels, grad_acc_step: int, l1: float = 0.0, sample_rows: "int | None" = None):
@@ -313,9 +311,7 @@ class GraphedWindowStep:
             if reason:
                 raise ValueError(f"GraphedWindowStep(sample_rows={sample_rows}): {reason}")
             bags = window[0]
-            self.sampler = ops.RowSampler(bags.n_slides, int(sample_rows), bags.width, bags.dtype, bags.device,
-                                          device_feature_scale=self._scaled(bags),
-                                          source="slides" if isinstance(bags, SlideSet) else "window").bind(bags)
+            self.sampler = ops.RowSampler.for_window(bags, sample_rows, device_feature_scale=self._scaled(bags)).bind(bags)
         else:
             if isinstance(window[0], SlideSet):
                 raise ValueError("GraphedWindowStep: a SlideSet window is read by the row sampler alone (sample_rows=k); every "
@@ -483,7 +479,7 @@ class GraphedWindowStep:
 class ResidentCohort:
     """A cohort that lives on the device once, for shuffled epochs of the sampled, captured step (bag_dtype bf16, or fp32
     for a step captured with device_feature_scale=True): every slide's rows (in
-    slabs of at most `slab_bytes`, a slide never split), the pointer / length table csrc/bag_sample_slides.hip is addressed
+    slabs of at most `slab_bytes`, a slide never split), the pointer / length table csrc/bag_sample.hip's slide gather is addressed
     through, omics per group (N, d_i), labels, censorship and survival_months (all (N,)).  A window is a list of slide ids:
     nothing is copied to form it and nothing crosses PCIe (1 000 slides of 15 000 x 1024 bf16 are 30 GB).
 

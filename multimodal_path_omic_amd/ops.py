@@ -37,6 +37,8 @@ class BagBatch:
     cu: torch.Tensor
     lengths: List[int]
     _plan: object = None
+    sampler_source = "window"       # which RowSampler reads this kind of window
+    cycle = False                   # (a contiguous window is never lapped: SlideSet.cycle)
 
     def __post_init__(self):
         # an empty bag has no softmax (the reference's nn.MultiheadAttention returns NaN for it): refuse it here, before a
@@ -94,6 +96,10 @@ class BagBatch:
     def device(self):
         return self.data.device
 
+    def row_tensors(self):
+        """The tensors that hold the window's rows (what RowSampler.check looks at)."""
+        return [self.data]
+
     @staticmethod
     def from_list(bags: "List[torch.Tensor]") -> "BagBatch":
         lengths = [int(b.shape[0]) for b in bags]
@@ -126,7 +132,7 @@ class BagBatch:
 @dataclass
 class SlideSet:
     """A window of SEPARATELY stored slides: what a shuffled epoch over a cohort resident on the device hands to the sampled
-    step instead of a contiguous BagBatch (harness.ResidentCohort.window; csrc/bag_sample_slides.hip gathers from it).
+    step instead of a contiguous BagBatch (harness.ResidentCohort.window; csrc/bag_sample.hip gathers from it).
 
     slides   per-slide (M_b, width) row tensors or views into slabs, in window order (kept alive here);
     lengths  host list of M_b;
@@ -147,6 +153,7 @@ class SlideSet:
     table_lens: torch.Tensor
     ids: torch.Tensor
     cycle: bool = False
+    sampler_source = "slides"
 
     def __post_init__(self):
         self.lengths = [int(m) for m in self.lengths]
@@ -178,6 +185,9 @@ class SlideSet:
     @property
     def device(self):
         return self.slides[0].device
+
+    def row_tensors(self):
+        return self.slides
 
     @staticmethod
     def slide_table(slides: "List[torch.Tensor]"):
@@ -1610,7 +1620,8 @@ class RowSampler:
     the most recent call, for tests/row_sampling_replay.py.
 
     source="slides": the sampler binds SlideSet windows (separately stored slides of a cohort resident on the device) and
-    gathers with csrc/bag_sample_slides.hip; same draw, keyed by the slide's position in the window.  A SlideSet with
+    gathers through their descriptor layout (same file, same kernel); same draw, keyed by the slide's position in the window.
+    Every window type names its source (`sampler_source`); for_window builds the sampler a given window needs.  A SlideSet with
     `cycle` laps a slide shorter than k in its permuted order, so the output keeps lengths [k] * n_slides: static mode
     accepts such a window, and refuses a short slide without `cycle` as it does for a BagBatch.  A sampler binds the
     kind of window it was built for and refuses the other.
@@ -1652,6 +1663,11 @@ class RowSampler:
             self._set_batch(BagBatch(self.out, make_cu([k] * n_slides, self.device), [k] * n_slides))
             self.batch.plan()
 
+    @classmethod
+    def for_window(cls, bags, k: int, **kw) -> "RowSampler":
+        """The sampler for windows like `bags` (a BagBatch or a SlideSet): its slide count, row width, dtype, device and source."""
+        return cls(bags.n_slides, int(k), bags.width, bags.dtype, bags.device, source=bags.sampler_source, **kw)
+
     def _set_batch(self, batch):
         self.batch = batch
         if self.scale is not None:
@@ -1664,14 +1680,13 @@ class RowSampler:
                              f"descriptor and gather address the rows that way), not for a {type(bags).__name__}")
         if bags.n_slides != self.n_slides:
             raise ValueError(f"RowSampler: the window has {bags.n_slides} slides, the sampler was built for {self.n_slides}")
-        rows = bags.slides if self.source == "slides" else [bags.data]
-        for x in rows:
+        for x in bags.row_tensors():
             if x.dim() != 2 or int(x.shape[1]) != self.width:
                 raise ValueError(f"RowSampler: the window's rows are {tuple(x.shape)[1:]} wide, the sampler was built for width "
                                  f"{self.width}")
             if x.dtype != self.dtype:
                 raise ValueError(f"RowSampler: the window is stored as {x.dtype}, the sampler was built for {self.dtype}")
-        if self.static and not getattr(bags, "cycle", False):
+        if self.static and not bags.cycle:
             for b, m in enumerate(bags.lengths):
                 if m < self.k:
                     raise ValueError(f"RowSampler: slide {b} has {m} rows, fewer than k = {self.k} (static mode neither pads "
@@ -1687,7 +1702,7 @@ class RowSampler:
                    L.stream_of(self.desc))
         self.bound = bags
         if not self.static:
-            lengths = [self.k if getattr(bags, "cycle", False) else min(self.k, int(m)) for m in bags.lengths]
+            lengths = [self.k if bags.cycle else min(self.k, int(m)) for m in bags.lengths]
             self._set_batch(BagBatch(self.out[:sum(lengths)], make_cu(lengths, self.device), lengths))
         return self
 

@@ -1,4 +1,4 @@
-"""CPU-only checks of the resident-cohort sampler's entries (include/mpo_cohort.h, csrc/bag_sample_slides.hip): the header and
+"""CPU-only checks of the resident-cohort sampler's entries (include/mpo_cohort.h, csrc/bag_sample.hip): the header and
 its exports, the descriptor size, the entry points' refusals, and the lapped indices restated on the host.  Nothing here
 launches a kernel."""
 import ctypes

@@ -1,4 +1,4 @@
-"""Patch sampling from a cohort resident on the device (csrc/bag_sample_slides.hip, ops.SlideSet, ops.RowSampler(source=
+"""Patch sampling from a cohort resident on the device (csrc/bag_sample.hip, ops.SlideSet, ops.RowSampler(source=
 "slides"), harness.ResidentCohort / train_epoch): the gather from separately allocated slides against x[idx] with idx restated
 on the host (tests/row_sampling_replay.py; lapped slides: the prefix tiled), bit for bit; the same bits as the contiguous
 gather; a captured gather and a captured training step following their bindings; one epoch without host synchronisation.
@@ -161,6 +161,57 @@ def test_gather_of_many_rows(dev, width, lengths, k, cycle):
     if cycle:
         counts = torch.bincount(torch.from_numpy(np.resize(R.permutation_prefix(*s.last_stream, 0, 0, 3, k), k)), minlength=3)
         assert counts.tolist() == [13333] * 3
+
+
+@pytest.mark.parametrize("bind", ["contiguous", "slides", "slides lapped"])
+@pytest.mark.parametrize("n", [1, 64, 65, 130])
+def test_output_offsets_of_both_binds_across_wave_trips(dev, n, bind):
+    """ocu of both bind kernels comes from one single-wave prefix sum, 64 slides per trip with a carry from trip to trip: one
+    trip partly filled, exactly full, one slide into the second, and into the third.  Rows of one 16-byte vector, k = 3, slide
+    lengths 1 .. 5, so some slides are shorter than k.  The descriptor's ocu words equal the host's prefix sums of the rows
+    each slide takes -- min(k, M_b); k where the slides are lapped; for an id outside the table (position 64) 0, or, lapped,
+    its k rows like every slide's, none of them written (test_gather_equals_indexing_bit_for_bit pins the same) -- the
+    gather over that binding equals indexing, bit for bit, and the rows behind ocu[n] keep their fill."""
+    width, k, stream, guard = 8, 3, (21, 4), 4
+    lapped = bind == "slides lapped"
+    table_lengths = [[1, 2, 3, 4, 5][i % 5] for i in range(n)]
+    g = torch.Generator(device="cpu").manual_seed(11)
+    slab = torch.randn(sum(table_lengths), width, generator=g).to(device=dev, dtype=torch.bfloat16)
+    before = slab.clone()
+    table_slides = list(slab.split(table_lengths))                           # (16-byte rows: every view is aligned)
+    nan = torch.full((n * k + guard, width), float("nan"), dtype=torch.bfloat16, device=dev)
+    big = nan.clone()
+    if bind == "contiguous":
+        ids, bad = list(range(n)), None
+        bags = BagBatch.from_lengths(slab, table_lengths)
+        desc = torch.zeros(L.lib().mpo_bag_sample_desc_bytes(n) // 8, dtype=torch.int64, device=dev)
+        L.call("mpo_bag_sample_bind", L.ptr(desc), L.ptr(bags.data), L.ptr(bags.cu), n, k, L.stream_of(desc))
+        L.call("mpo_bag_sample_rows", L.ptr(desc), n, k, width, 2, stream[0], stream[1], L.ptr(None), L.ptr(big), L.stream_of(big))
+        words = desc.view(torch.int32)                                       # base | cu[n + 1] | ocu[n + 1]
+        assert int(desc[0]) == slab.data_ptr() and words[2:n + 3].tolist() == bags.cu.tolist()
+        ocu = words[n + 3:2 * n + 4].tolist()
+    else:
+        ids, bad = list(reversed(range(n))), (64 if n > 64 else None)        # (position b reads table slide n - 1 - b)
+        if bad is not None:
+            ids[bad] = n
+        desc = new_desc(n, dev)
+        bind_slides(desc, SlideSet.slide_table(table_slides), int32(ids, dev), k, lapped)
+        gather_slides(desc, n, k, big, stream)
+        words = desc.view(torch.int32)                                       # ptr[n] | len[n] | ocu[n + 1]
+        assert desc[:n].tolist() == [0 if b == bad else table_slides[i].data_ptr() for b, i in enumerate(ids)]
+        assert words[2 * n:3 * n].tolist() == [0 if b == bad else table_lengths[i] for b, i in enumerate(ids)]
+        ocu = words[3 * n:4 * n + 1].tolist()
+    take, want = [], []
+    for b, i in enumerate(ids):
+        if b == bad:                            # lapped: its k rows are counted and stay as they were
+            take.append(k if lapped else 0)
+            want.append(nan[:take[-1]])
+        else:
+            take.append(k if lapped else min(k, table_lengths[i]))
+            want.append(slide_rows(table_slides[i], stream, 0, b, k, lapped))
+    assert ocu == np.concatenate([[0], np.cumsum(take)]).tolist()
+    assert same_bits(big[:ocu[-1]], torch.cat(want)) and same_bits(big[ocu[-1]:], nan[ocu[-1]:])
+    assert same_bits(slab, before)                                           # the sources are not written
 
 
 def test_captured_gather_follows_its_binding(dev):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times of the resident-cohort sampler (csrc/bag_sample_slides.hip, ops.SlideSet, harness.ResidentCohort / train_epoch) in
+"""Times of the resident-cohort sampler (csrc/bag_sample.hip, ops.SlideSet, harness.ResidentCohort / train_epoch) in
 ONE process:
   1. the gather at n_slides x M -> k rows x 1024 bf16: from n_slides separate allocations scattered through a cohort of
      `cohort_slides`, beside the contiguous gather on the same slides concatenated (the yardstick) and beside what a user
