@@ -564,6 +564,10 @@ int mpo_coattn_bwd_bagpass(const void* bag, int bag_dtype, const int32_t* cu_row
  * additive to ABI 14. */
 #include "mpo_feature_range.h"
 
+/* ---- gradient-norm clipping and the non-finite step skip of the flat optimisers (csrc/grad_guard.hip): likewise additive to
+ * ABI 14. */
+#include "mpo_grad_guard.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -324,14 +324,24 @@ class FlatOptimizer(_FlatState):
     schedule (FlatExponentialLR) and the bias correction.  `l1_lambda` > 0 folds the L1 penalty's gradient
     (training.lambda: lambda * l1_reg(model) added to every slide's loss, models/mcat/main.py:61,69, not divided by
     grad_acc_step) into the pass: g' = g + lambda * S * sign(p) + weight_decay * p, S = the window's slides over ALL ranks
-    (step(l1_slides=S)); after the data-parallel AVG all-reduce this is the reference's update."""
+    (step(l1_slides=S)); after the data-parallel AVG all-reduce this is the reference's update.
+
+    `max_grad_norm` / `skip_nonfinite` (both off by default: step() is then the one call it always was) guard the step on
+    the device, inside a captured graph as well: step() first measures g + lambda * S * sign(p) (ops.grad_norm_flat, two
+    launches) and then runs the guarded pass, which scales that sum -- not the weight decay, which torch adds after the clip --
+    by torch.nn.utils.clip_grad_norm_'s coefficient and, with skip_nonfinite, writes nothing when an element of it is an
+    infinity or a NaN; a skipped step does not count in `t_dev`.  `grad_ctl` (16 bytes on the device) holds the outcome;
+    `last_grad_norm`, `clip_coef` (fp32 (1,)) and `skipped_steps` (int32 (1,)) are views of it, read without a sync by
+    whoever wants one.  Data-parallel runs step after the all-reduce: every rank measures the same bucket."""
 
     DEFAULTS = {"adam": dict(betas=(0.9, 0.999), eps=1e-8), "adamax": dict(betas=(0.9, 0.999), eps=1e-8),
                 "adadelta": dict(betas=(0.9, 0.0), eps=1e-6), "sgd": dict(betas=(0.0, 0.0), eps=0.0)}
 
     def __init__(self, bucket: FlatGradBucket, algorithm: str = "adam", lr: float = 2e-4, weight_decay: float = 0.0,
-                 betas=None, eps=None, rho=None, l1_lambda: float = 0.0):
-        """betas / eps default to torch.optim's for the algorithm; adadelta takes rho (default 0.9) instead of betas."""
+                 betas=None, eps=None, rho=None, l1_lambda: float = 0.0, max_grad_norm: "float | None" = None,
+                 skip_nonfinite: bool = False):
+        """betas / eps default to torch.optim's for the algorithm; adadelta takes rho (default 0.9) instead of betas.
+        max_grad_norm (None / 0: no clipping) and skip_nonfinite: the class docstring."""
         if algorithm not in self.DEFAULTS:
             raise ValueError(f"unknown flat optimiser '{algorithm}' ({' | '.join(self.DEFAULTS)})")
         d = self.DEFAULTS[algorithm]
@@ -345,6 +355,20 @@ class FlatOptimizer(_FlatState):
         self._allocate(bucket, tag_params=True)
         self.lr = float(lr)
         self.lr_dev = torch.full((1,), self.lr, dtype=torch.float32, device=self.flat_p.device)
+        self.max_grad_norm = float(max_grad_norm) if max_grad_norm else None
+        if self.max_grad_norm is not None and not self.max_grad_norm > 0.0:
+            raise ValueError(f"FlatOptimizer: max_grad_norm = {max_grad_norm} (a positive norm, or None for no clipping)")
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.grad_ctl = None
+        if self.max_grad_norm is not None or self.skip_nonfinite:
+            # the control block of include/mpo_grad_guard.h: norm, coef (fp32), nonfinite, skipped (int32)
+            self.grad_ctl = torch.zeros(4, dtype=torch.int32, device=self.flat_p.device)
+            self.last_grad_norm, self.clip_coef = self.grad_ctl[0:1].view(torch.float32), self.grad_ctl[1:2].view(torch.float32)
+            self.skipped_steps = self.grad_ctl[3:4]
+
+    def state_tensors(self):
+        """_FlatState's, and the control block of a guarded optimiser (its count of skipped steps)."""
+        return super().state_tensors() + ([] if self.grad_ctl is None else [self.grad_ctl])
 
     def set_lr(self, lr: float):
         """New learning rate (host value and the device scalar a captured step reads).  Call outside graph capture."""
@@ -364,8 +388,14 @@ class FlatOptimizer(_FlatState):
             raise ValueError("FlatOptimizer.step: l1_lambda > 0 needs l1_slides (slides of the window over all ranks)")
         self._advance(bump)
         l1 = self.l1_lambda * l1_slides if self.l1_lambda else 0.0
-        ops.optim_step_flat(self.algorithm, self.flat_p, self.bucket.flat, self.state1, self.state2, self.lr, self.lr_dev,
-                            self.betas[0], self.betas[1], self.eps, self.wd, l1, 1, self.t_dev)
+        if self.grad_ctl is None:
+            ops.optim_step_flat(self.algorithm, self.flat_p, self.bucket.flat, self.state1, self.state2, self.lr, self.lr_dev,
+                                self.betas[0], self.betas[1], self.eps, self.wd, l1, 1, self.t_dev)
+            return
+        ops.grad_norm_flat(self.bucket.flat, self.grad_ctl, self.flat_p, l1, self.max_grad_norm, self.skip_nonfinite, self.t_dev)
+        ops.optim_step_flat_guarded(self.algorithm, self.flat_p, self.bucket.flat, self.state1, self.state2, self.grad_ctl,
+                                    self.lr, self.lr_dev, self.betas[0], self.betas[1], self.eps, self.wd, l1, 1, self.t_dev,
+                                    self.skip_nonfinite)
 
 
 class FlatExponentialLR:

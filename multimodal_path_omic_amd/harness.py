@@ -183,6 +183,8 @@ class TrainOptions:
     weight_decay: float
     l1: float                     # training.lambda; 0.0 = no penalty
     gamma: "float | None"         # ExponentialLR gamma, None = no schedule
+    max_grad_norm: "float | None" = None      # not the reference's: clip the global gradient norm (FlatOptimizer)
+    skip_nonfinite: bool = False              # not the reference's: drop a step whose gradient holds an inf or a NaN
 
     def train_kwargs(self) -> dict:
         return dict(loss=self.loss, alpha=self.alpha, lambda_reg=self.lambda_reg, l1=self.l1)
@@ -190,7 +192,8 @@ class TrainOptions:
     def make_optimizer(self, bucket):
         from .dp import FlatOptimizer
         wd = 0.0 if self.optimizer == "sgd" else self.weight_decay          # main.py:288-289 passes lr only
-        return FlatOptimizer(bucket, self.optimizer, lr=self.lr, weight_decay=wd, l1_lambda=self.l1)
+        return FlatOptimizer(bucket, self.optimizer, lr=self.lr, weight_decay=wd, l1_lambda=self.l1,
+                             max_grad_norm=self.max_grad_norm, skip_nonfinite=self.skip_nonfinite)
 
     def make_scheduler(self, opt):
         from .dp import FlatExponentialLR
@@ -202,7 +205,8 @@ def training_options(training: dict, model: str = "mcat") -> TrainOptions:
     'cesar' exists for NaCAGaT only and always runs with alpha 0.75, lambda_reg 0.01 (CrossEntropySurvivalAttnRegLoss());
     'ce' raises for the fusion models (CE_REFUSAL) and is the one loss of 'ge_nacagat' (models/ge_nacagat/main.py:223-227, where
     the call is well-formed); unknown optimiser names (e.g. 'rms') become 'adam'; 'sgd' gets no weight decay;
-    lambda 0 / None means no penalty; any scheduler other than 'exp' means none."""
+    lambda 0 / None means no penalty; any scheduler other than 'exp' means none.  Two keys the reference's YAML does not
+    have are read when present: max_grad_norm and skip_nonfinite (FlatOptimizer's guard; both off when absent)."""
     if model not in LOSSES:
         raise ValueError(f"model '{model}' has no training loop here ({' | '.join(LOSSES)})")
     loss = training["loss"]
@@ -215,9 +219,11 @@ def training_options(training: dict, model: str = "mcat") -> TrainOptions:
     name = name if name in OPTIMISERS else "adam"
     lam = training.get("lambda")
     gamma = float(training["gamma"]) if training.get("scheduler") == "exp" else None
+    max_norm = training.get("max_grad_norm")
     return TrainOptions(loss=loss, alpha=alpha, lambda_reg=lambda_reg, grad_acc_step=int(training["grad_acc_step"]),
                         optimizer=name, lr=float(training["lr"]), weight_decay=float(training.get("weight_decay") or 0.0),
-                        l1=float(lam) if lam else 0.0, gamma=gamma)
+                        l1=float(lam) if lam else 0.0, gamma=gamma, max_grad_norm=float(max_norm) if max_norm else None,
+                        skip_nonfinite=bool(training.get("skip_nonfinite", False)))
 
 
 _slide_weight_cache = {}

@@ -1251,6 +1251,33 @@ def optim_step_flat(algorithm: str, params, grads, state1, state2, lr: float, lr
            float(weight_decay), float(l1), int(step), L.ptr(step_dev), L.stream_of(params))
 
 
+def grad_norm_flat(grads, ctl, params=None, l1: float = 0.0, max_norm: "float | None" = None, skip_nonfinite: bool = False,
+                   step_dev=None):
+    """One mpo_grad_norm_flat (include/mpo_grad_guard.h): measures g' = grads + l1 sign(params) into the 16-byte control block
+    `ctl` (4 x 32 bits on the device: norm, coef, nonfinite, skipped).  max_norm None / 0: no clipping (coef 1).
+    skip_nonfinite with a non-finite g': ctl's skipped count goes up and step_dev (int32 (1,)), if given, down by one.
+    Deterministic (two launches, fixed partial sums, no atomics); no host sync."""
+    lib = L.lib()
+    if grads.dtype != torch.float32 or ctl.numel() * ctl.element_size() != 16:
+        raise ValueError("grad_norm_flat: fp32 gradients and a 16-byte control block")
+    ws = _workspace(lib.mpo_grad_norm_flat_workspace_bytes(grads.numel()), grads.device)
+    L.call("mpo_grad_norm_flat", L.ptr(grads), L.ptr(params) if l1 else None, grads.numel(), float(l1), float(max_norm or 0.0),
+           int(bool(skip_nonfinite)), L.ptr(step_dev), L.ptr(ctl), L.ptr(ws), ws.numel(), L.stream_of(grads))
+
+
+def optim_step_flat_guarded(algorithm: str, params, grads, state1, state2, ctl, lr: float, lr_dev=None, beta1: float = 0.9,
+                            beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0, l1: float = 0.0,
+                            step: int = 1, step_dev=None, skip_nonfinite: bool = False):
+    """One mpo_optim_step_flat_guarded (include/mpo_grad_guard.h): optim_step_flat on the clipped gradient
+    ctl.coef * (grads + l1 sign(params)) + weight_decay * params; with skip_nonfinite and ctl.nonfinite set it writes
+    nothing.  `ctl`: what grad_norm_flat wrote for the same grads, params and l1."""
+    if algorithm not in L.OPTIM:
+        raise ValueError(f"unknown flat optimiser '{algorithm}' ({' | '.join(L.OPTIM)})")
+    L.call("mpo_optim_step_flat_guarded", L.OPTIM[algorithm], L.ptr(params), L.ptr(grads), L.ptr(state1), L.ptr(state2),
+           params.numel(), float(lr), L.ptr(lr_dev), float(beta1), float(beta2), float(eps), float(weight_decay), float(l1),
+           int(step), L.ptr(step_dev), L.ptr(ctl), int(bool(skip_nonfinite)), L.stream_of(params))
+
+
 # ------------------------------------------------------------------------------------ fusion + classifier + survival head
 # The three fusions (K6 concat, gated-concat, bilinear) share one head protocol -- four C entries mpo_<name>_{forward, backward,
 # loss_forward, loss_backward}, csrc/tail_api.hip -- and one Python body for it: HeadFn / HeadLossFn over a _Head description.

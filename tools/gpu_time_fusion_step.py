@@ -8,6 +8,9 @@ repeat by repeat so that a drift of the machine lands on all of them; two untime
 then one JSON line with the medians and each fusion's own spread (max - min over its repeats).
 --only FUSION: build and replay that one step alone (`repeats * steps` replays, one timing) -- the workload for a
 `rocprofv3 --kernel-trace --stats -- python tools/gpu_time_fusion_step.py --only bilinear` run.
+--grad-guard: instead of the fusions, the first fusion's step with dp.FlatOptimizer('adam') in the graph, its gradient guard
+off and on (max_grad_norm=1.0, skip_nonfinite=True: the norm pass's two launches in front of the optimiser pass), timed the
+same alternating way: what the guard costs per step.
 The script uses nothing but the package's public training API, so the same file times an older checkout."""
 import argparse
 import json
@@ -19,7 +22,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from multimodal_path_omic_amd import harness                                                    # noqa: E402
-from multimodal_path_omic_amd.dp import FlatAdam, FlatGradBucket                                # noqa: E402
+from multimodal_path_omic_amd.dp import FlatAdam, FlatGradBucket, FlatOptimizer                 # noqa: E402
 from multimodal_path_omic_amd.models import MultimodalCoAttentionTransformer                    # noqa: E402
 from multimodal_path_omic_amd.ops import BagBatch, make_cu                                      # noqa: E402
 
@@ -30,6 +33,7 @@ ap.add_argument("--window", type=int, default=32)
 ap.add_argument("--patches", type=int, default=15000)
 ap.add_argument("--repeats", type=int, default=7)
 ap.add_argument("--steps", type=int, default=10)
+ap.add_argument("--grad-guard", action="store_true")
 a = ap.parse_args()
 fusions = [a.only] if a.only else a.fusions.split(",")
 dev = torch.device("cuda:0")
@@ -43,14 +47,21 @@ omics = [torch.randn(a.window, 256, device=dev, generator=g) for _ in range(6)]
 idx = torch.arange(a.window, device=dev)
 window = (bags, omics, idx % 4, (idx % 2).float())
 
+guards = {"guard off": {}, "guard on": dict(max_grad_norm=1.0, skip_nonfinite=True)}
 steps = {}
-for fusion in fusions:
+for label in (guards if a.grad_guard else fusions):         # (the labels below are fusions, or the two guard settings)
     torch.manual_seed(0)
-    model = MultimodalCoAttentionTransformer(omic_sizes=[256] * 6, model_size="medium", fusion=fusion,
+    model = MultimodalCoAttentionTransformer(omic_sizes=[256] * 6, model_size="medium",
+                                             fusion=fusions[0] if a.grad_guard else label,
                                              bag_dtype=torch.bfloat16).to(dev).train()
     bucket = FlatGradBucket(list(model.parameters()))
-    opt = FlatAdam(bucket, lr=2e-4, weight_decay=1e-5)
-    steps[fusion] = harness.GraphedWindowStep(model, bucket, window, a.window, opt=opt)
+    if a.grad_guard:
+        opt = FlatOptimizer(bucket, "adam", lr=2e-4, weight_decay=1e-5, **guards[label])
+    else:
+        opt = FlatAdam(bucket, lr=2e-4, weight_decay=1e-5)
+    steps[label] = harness.GraphedWindowStep(model, bucket, window, a.window, opt=opt)
+if a.grad_guard:
+    what_opt, fusions = f" fusion={fusions[0]} FlatOptimizer(adam)", list(guards)
 
 
 def timed(step, n):
@@ -63,7 +74,7 @@ def timed(step, n):
     return t0.elapsed_time(t1) / n
 
 
-what = f"mcat medium bf16 {a.window} x {a.patches}"
+what = f"mcat medium bf16 {a.window} x {a.patches}" + (what_opt if a.grad_guard else "")
 if a.only:
     ms = timed(steps[a.only], a.repeats * a.steps)
     print(json.dumps({"workload": what, "fusion": a.only, "replays": a.repeats * a.steps, "ms_per_step": round(ms, 4)}))
@@ -76,7 +87,7 @@ for _ in range(a.repeats):
     for fusion in fusions:
         times[fusion].append(timed(steps[fusion], a.steps))
 for fusion in fusions:
-    print(f"{what} fusion={fusion}: " + " ".join(f"{t:.3f}" for t in times[fusion]) + " ms/step", flush=True)
+    print(f"{what} {'' if a.grad_guard else 'fusion='}{fusion}: " + " ".join(f"{t:.3f}" for t in times[fusion]) + " ms/step", flush=True)
 print(json.dumps({"workload": what, "steps_per_repeat": a.steps,
                   "ms_per_step": {f: round(statistics.median(t), 4) for f, t in times.items()},
                   "spread_ms": {f: round(max(t) - min(t), 4) for f, t in times.items()}}))
