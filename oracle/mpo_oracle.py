@@ -47,8 +47,9 @@ def _elu(x):
 
 # --------------------------------------------------------------------------- H2
 def _store(t, dtype):
-    """Round-trip through a storage dtype (identity gradient): emulates a tensor kept in bf16."""
-    return t if dtype is None else t.to(dtype).float()
+    """Round-trip through a storage dtype (identity gradient): emulates a tensor kept in bf16.  The result has the
+    dtype of `t` (fp32, or fp64 for the fp64 oracle)."""
+    return t if dtype is None else t.to(dtype).to(t.dtype)
 
 
 def patch_fc(wsi, p, prefix="H", keep=None, storage=None, round_gemm_out=True, storage_points=("x", "w", "h")):
@@ -58,15 +59,17 @@ def patch_fc(wsi, p, prefix="H", keep=None, storage=None, round_gemm_out=True, s
     before the bias (the library-GEMM path of the small / big models; the hand-written patch-layer kernel of the medium
     models keeps the accumulator in fp32 up to the one rounding of H_bag).
     storage_points: which of the three storage points are rounded -- "x" the patch matrix, "w" the weight operand,
-    "h" H_bag (and the GEMM output under round_gemm_out) -- so a test can attribute a bf16-mode error to each of them."""
+    "h" H_bag (and the GEMM output under round_gemm_out) -- so a test can attribute a bf16-mode error to each of them.
+    keep (M, d): the dropout's pre-scaled keep mask (training mode)."""
     x = wsi.squeeze(0) if wsi.dim() == 3 else wsi
     x = _store(x.to(p[prefix + ".0.weight"].dtype), storage if "x" in storage_points else None)   # fp32 unless fp64 params
     h = x @ _store(p[prefix + ".0.weight"], storage if "w" in storage_points else None).t()
     st_h = storage if "h" in storage_points else None
     if round_gemm_out:
         h = _store(h, st_h)
-    h = _store(torch.relu(h + p[prefix + ".0.bias"]), st_h)
-    return h if keep is None else h * keep
+    h = torch.relu(h + p[prefix + ".0.bias"])
+    # (a stored H_bag is rounded ONCE, after the dropout scale, as the patch-layer kernels write it)
+    return _store(h if keep is None else h * keep, st_h)
 
 
 def _alpha_dropout(x, keep, drop_p):
@@ -262,33 +265,50 @@ def survival_head(h, p, prefix="classifier"):
 
 
 # --------------------------------------------------------------------------- H1
-def _tail(h_coattn, g_bag, a_coattn, p, fusion="concat"):
-    path = set_transformer(h_coattn, p, "path_transformer")
-    omic = set_transformer(g_bag, p, "omic_transformer")
-    a_path, h_path = gated_mil_pool(path, p, "path_attention_head", "path_rho")
-    a_omic, h_omic = gated_mil_pool(omic, p, "omic_attention_head", "omic_rho")
+def _pooled(h_coattn, g_bag, p, enc_keeps=None, pool_keeps=None):
+    """The two branches up to the fusion layer's inputs -> (A_path, h_path, A_omic, h_omic).
+    enc_keeps / pool_keeps (training mode with given masks): one set per branch, (path, omic) -- enc_keeps[i] the
+    per-layer masks of set_transformer, pool_keeps[i] = (keep_a, keep_b, keep_rho) of gated_mil_pool."""
+    k_path, k_omic = enc_keeps if enc_keeps is not None else (None, None)
+    q_path, q_omic = pool_keeps if pool_keeps is not None else ((), ())
+    path = set_transformer(h_coattn, p, "path_transformer", keeps=k_path)
+    omic = set_transformer(g_bag, p, "omic_transformer", keeps=k_omic)
+    a_path, h_path = gated_mil_pool(path, p, "path_attention_head", "path_rho", *(q_path or ()))
+    a_omic, h_omic = gated_mil_pool(omic, p, "omic_attention_head", "omic_rho", *(q_omic or ()))
+    return a_path, h_path, a_omic, h_omic
+
+
+def _tail(h_coattn, g_bag, a_coattn, p, fusion="concat", enc_keeps=None, pool_keeps=None):
+    """enc_keeps / pool_keeps: see _pooled.  The fusion layer itself is eval-mode (concat and gated_concat have no dropout
+    site; the bilinear layer's five are restated, with masks, by tests/fusion_replay.py)."""
+    a_path, h_path, a_omic, h_omic = _pooled(h_coattn, g_bag, p, enc_keeps, pool_keeps)
     h = {"concat": concat_fusion, "gated_concat": gated_concat_fusion, "bilinear": bilinear_fusion}[fusion](h_path, h_omic, p)
     hazards, survs, y = survival_head(h, p)
     return hazards, survs, y, {"coattn": a_coattn, "path": a_path, "omic": a_omic}
 
 
 def mcat_forward(p, wsi, omics, inference=False, bag_storage=None, fusion="concat", round_gemm_out=False,
-                 storage_points=("x", "w", "h")):
+                 storage_points=("x", "w", "h"), keep_h=None, ad_keeps=None, enc_keeps=None, pool_keeps=None):
     """MultimodalCoAttentionTransformer.forward, models/mcat/mcat.py:84-142 (eval mode).
-    bag_storage / round_gemm_out: see patch_fc (the fused kernel of the 'medium' model rounds H_bag once)."""
-    h_bag = patch_fc(wsi, p, storage=bag_storage, round_gemm_out=round_gemm_out, storage_points=storage_points)
-    g_bag = omic_fc(omics, p)
+    bag_storage / round_gemm_out: see patch_fc (the fused kernel of the 'medium' model rounds H_bag once).
+    Training mode with given masks (every one None: eval): keep_h (M, d) the patch layer's dropout (patch_fc), ad_keeps
+    the SNN's AlphaDropout masks (omic_fc), enc_keeps / pool_keeps the two branches' (see _tail)."""
+    h_bag = patch_fc(wsi, p, keep=keep_h, storage=bag_storage, round_gemm_out=round_gemm_out, storage_points=storage_points)
+    g_bag = omic_fc(omics, p, ad_keeps=ad_keeps)
     h_co, a_co = mcat_coattention(g_bag, h_bag, p, need_weights=inference)
-    return _tail(h_co, g_bag, a_co, p, fusion)
+    return _tail(h_co, g_bag, a_co, p, fusion, enc_keeps, pool_keeps)
 
 
-def nacagat_forward(p, wsi, omics, bag_storage=None, round_gemm_out=False, storage_points=("x", "w", "h")):
+def nacagat_forward(p, wsi, omics, bag_storage=None, round_gemm_out=False, storage_points=("x", "w", "h"), keep_h=None,
+                    ad_keeps=None, keep_map=None, enc_keeps=None, pool_keeps=None):
     """NarrowContextualAttentionGateTransformer.forward, models/nacagat/nacagat.py:80-138 (eval mode).
-    bag_storage / round_gemm_out: see patch_fc (the 'medium' model's patch-layer kernel rounds H_bag once)."""
-    h_bag = patch_fc(wsi, p, storage=bag_storage, round_gemm_out=round_gemm_out, storage_points=storage_points)
-    g_bag = omic_fc(omics, p)
-    h_co, a_co = pregating_contextual_attention(g_bag, h_bag, p)
-    return _tail(h_co, g_bag, a_co, p)
+    bag_storage / round_gemm_out: see patch_fc (the 'medium' model's patch-layer kernel rounds H_bag once).
+    Training mode with given masks: as mcat_forward, and keep_map (N, M) the co-attention map's dropout
+    (pregating_contextual_attention; the returned map is then the dropped-out one)."""
+    h_bag = patch_fc(wsi, p, keep=keep_h, storage=bag_storage, round_gemm_out=round_gemm_out, storage_points=storage_points)
+    g_bag = omic_fc(omics, p, ad_keeps=ad_keeps)
+    h_co, a_co = pregating_contextual_attention(g_bag, h_bag, p, keep=keep_map)
+    return _tail(h_co, g_bag, a_co, p, enc_keeps=enc_keeps, pool_keeps=pool_keeps)
 
 
 # --------------------------------------------------------------------------- f3
