@@ -568,6 +568,10 @@ int mpo_coattn_bwd_bagpass(const void* bag, int bag_dtype, const int32_t* cu_row
  * ABI 14. */
 #include "mpo_grad_guard.h"
 
+/* ---- validation and test epochs on the device: the concordance index and per-slide attention-map statistics
+ * (csrc/concordance.hip, csrc/map_stats.hip): likewise additive to ABI 14. */
+#include "mpo_eval.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -1120,6 +1120,37 @@ def map_block_norm(maps) -> torch.Tensor:
     return MapBlockNormFn.apply(maps.flat, maps.batch, maps.n_q)
 
 
+def map_block_stats(maps) -> torch.Tensor:
+    """maps: the RaggedMaps a window forward returns -> (n_slides, 3) fp32 [min, max, mean] of every slide's (n_q, M_b) block
+    (what the reference's test() prints of attention_scores['coattn'], models/nacagat/main.py:169-194): two launches for
+    the whole window, sums carried in fp64 in a fixed order (csrc/map_stats.hip) -- deterministic, no host sync.  Not
+    differentiable."""
+    flat, batch, n_q = maps.flat.detach(), maps.batch, int(maps.n_q)
+    if not flat.is_cuda or flat.dtype != torch.float32:
+        raise ValueError(f"map_block_stats: an fp32 map on the GPU (got {flat.dtype} on {flat.device})")
+    flat = flat.contiguous()
+    if flat.numel() != n_q * batch.total_rows:
+        raise ValueError(f"map_block_stats: {flat.numel()} map values for {n_q} queries x {batch.total_rows} rows")
+    out = torch.empty(batch.n_slides, 3, dtype=torch.float32, device=flat.device)
+    ws = _workspace(L.lib().mpo_map_block_stats_workspace_bytes(batch.n_slides, n_q, batch.max_rows), flat.device)
+    L.call("mpo_map_block_stats", L.ptr(flat), L.ptr(batch.cu), batch.n_slides, n_q, batch.max_rows, L.ptr(out), L.ptr(ws),
+           ws.numel(), L.stream_of(flat))
+    return out
+
+
+def concordance_index(censorship, time, risk):
+    """Harrell's C on the device (csrc/concordance.hip; harness.concordance_index_device is the checked front): censorship,
+    risk fp32 (n,), time fp64 (n,), contiguous on one GPU -> (c_index (1,) fp64, counts (3,) int64 = concordant, tied,
+    comparable).  Two launches, no host sync."""
+    n = int(risk.numel())
+    c_index = torch.empty(1, dtype=torch.float64, device=risk.device)
+    counts = torch.empty(3, dtype=torch.int64, device=risk.device)
+    ws = _workspace(L.lib().mpo_concordance_workspace_bytes(n), risk.device)
+    L.call("mpo_concordance_index", L.ptr(time), L.ptr(censorship), L.ptr(risk), n, L.ptr(counts), L.ptr(c_index), L.ptr(ws),
+           ws.numel(), L.stream_of(risk))
+    return c_index, counts
+
+
 class SurvivalHeadFn(torch.autograd.Function):
     """logits (B, C) -> hazards, survs, Y (models/mcat/mcat.py:130-138) on the HIP head kernels."""
 
