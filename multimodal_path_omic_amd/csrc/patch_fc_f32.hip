@@ -446,6 +446,9 @@ int mpo_launch_patch_fc_f32(const float* x, const float* w, const float* bias, f
                             hipStream_t stream) {
     MPO_CHECK(embed == FE && patch_dim == FK, "fp32 patch layer kernel: built for %d -> %d (got %d -> %d)", FK, FE, patch_dim, embed);
     MPO_CHECK(drop_p >= 0.f && drop_p < 1.f, "patch-layer dropout p must be in [0,1) (got %f)", (double)drop_p);
+    // (the kernel's own expression: at 256 every byte would be dropped and the keep scale would be 256 / 0)
+    MPO_CHECK((uint32_t)(drop_p * 256.0f + 0.5f) <= 255u, "patch-layer dropout p = %g is realised as round(256 p) / 256 = %u/256: "
+              "nothing would be kept (p must be below 1 - 1/512)", (double)drop_p, (uint32_t)(drop_p * 256.0f + 0.5f));
     if (x_scale_dev == nullptr) {              // (a device scale cannot be looked at here: it must hold what mpo_feature_range_f32 wrote)
         int e = 0;
         MPO_CHECK(x_scale > 0.f && x_scale < INFINITY && frexpf(x_scale, &e) == 0.5f, "fp32 patch layer: x_scale must be a power of two (got %g)", (double)x_scale);

@@ -555,6 +555,9 @@ int mpo_launch_patch_fc_fwd(const void* x, const void* w_packed, const float* bi
     MPO_CHECK(embed == 128 || embed == 256 || embed == 512, "patch layer: embed_dim %d not in {128, 256, 512}", embed);
     MPO_CHECK(patch_dim == 512 || patch_dim == 1024 || patch_dim == 2048, "patch layer: patch_dim %d not in {512, 1024, 2048}", patch_dim);
     MPO_CHECK(drop_p >= 0.f && drop_p < 1.f, "patch-layer dropout p must be in [0,1) (got %f)", (double)drop_p);
+    // (the kernel's own expression: at 256 every byte would be dropped and the keep scale would be 256 / 0)
+    MPO_CHECK((uint32_t)(drop_p * 256.0f + 0.5f) <= 255u, "patch-layer dropout p = %g is realised as round(256 p) / 256 = %u/256: "
+              "nothing would be kept (p must be below 1 - 1/512)", (double)drop_p, (uint32_t)(drop_p * 256.0f + 0.5f));
     MPO_CHECK(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w_packed) | reinterpret_cast<uintptr_t>(h_out)) & 15) == 0,
               "patch layer: operands must be 16-byte aligned");
     const __bf16* xb = reinterpret_cast<const __bf16*>(x);

@@ -443,15 +443,15 @@ class PatchFcFn(torch.autograd.Function):
         if batch is None:                   # a bare patch matrix: one slide
             batch = BagBatch(x, make_cu([x.shape[0]], x.device), [x.shape[0]])
         h = torch.empty(x.shape[0], weight.shape[0], device=x.device, dtype=torch.bfloat16)
+        realised = _realised_drop(drop_p) if drop_p > 0 else 0.0
         seed, off = _reserve(h.numel() // 16 + 2) if drop_p > 0 else (0, 0)
         ws = _workspace(lib.mpo_patch_fc_workspace_bytes(weight.shape[0], weight.shape[1]), x.device)
         L.call("mpo_patch_fc_forward", L.ptr(x), L.ptr(batch.cu), batch.n_slides, batch.total_rows, batch.max_rows,
                x.shape[1], L.ptr(weight), L.ptr(bias), weight.shape[0], float(drop_p), seed, off,
                _epoch(), L.ptr(h), batch.plan(), L.ptr(ws), ws.numel(), L.stream_of(x))
-        drop_p = _realised_drop(drop_p) if drop_p > 0 else 0.0
         ctx.save_for_backward(x, h)
         ctx.param_refs = (weight, bias)
-        ctx.drop_p, ctx.pre_gated = float(drop_p), bool(pre_gated_grad)
+        ctx.drop_p, ctx.pre_gated = float(realised), bool(pre_gated_grad)
         return h
 
     @staticmethod
@@ -524,6 +524,7 @@ class PatchFcF32Fn(torch.autograd.Function):
     def forward(ctx, x, weight, bias, drop_p: float):
         lib = L.lib()
         h = torch.empty(x.shape[0], weight.shape[0], device=x.device, dtype=torch.float32)
+        ctx.gate = 1.0 / (1.0 - _realised_drop(drop_p)) if drop_p > 0 else 1.0
         seed, off = _reserve(h.numel() // 16 + 2) if drop_p > 0 else (0, 0)
         ws = _workspace(lib.mpo_patch_fc_f32_workspace_bytes(0), x.device)
         # a window that carries a device scale (feature_scale_device: a sampler's output, a captured step's window) is read
@@ -536,7 +537,6 @@ class PatchFcF32Fn(torch.autograd.Function):
                L.stream_of(x))
         ctx.save_for_backward(x, h)
         ctx.param_refs = (weight, bias)
-        ctx.gate = 1.0 / (1.0 - _realised_drop(drop_p)) if drop_p > 0 else 1.0
         return h
 
     @staticmethod
@@ -635,6 +635,7 @@ class PatchCoAttnMCATFn(torch.autograd.Function):
         amap = torch.empty(n_q * T, device=dev, dtype=torch.float32) if need_weights else None
         saved = torch.empty(lib.mpo_coattn_saved_floats(n_slides, n_q, E), device=dev, dtype=torch.float32)
         ws = _workspace(lib.mpo_patch_coattn_workspace_bytes(n_slides, n_q, E, x.shape[1]), dev)
+        ctx.gate = 1.0 / (1.0 - _realised_drop(drop_p)) if drop_p > 0 else 1.0
         seed, off = _reserve(T * E // 16 + 2) if drop_p > 0 else (0, 0)
         L.call("mpo_patch_coattn_mcat_forward",
             L.ptr(x), L.ptr(batch.cu), n_slides, T, batch.max_rows, x.shape[1], L.ptr(patch_w), L.ptr(patch_b), float(drop_p),
@@ -643,7 +644,6 @@ class PatchCoAttnMCATFn(torch.autograd.Function):
         ctx.save_for_backward(x, h_bag, query, in_w, out_w, saved, amap)
         ctx.param_refs = (patch_w, patch_b, in_w, in_b, out_w, out_b)
         ctx.batch, ctx.n_q = batch, n_q
-        ctx.gate = 1.0 / (1.0 - _realised_drop(drop_p)) if drop_p > 0 else 1.0
         ctx.qpass_owned = bool(qpass_owned)
         ctx.mark_non_differentiable(h_bag)
         # the query handed on to its second consumer (the omic branch's tokens): its gradient then arrives HERE and is
@@ -705,8 +705,13 @@ class _TokenPairFn(torch.autograd.Function):
 
 
 def _realised_drop(p: float) -> float:
-    """The fused kernel draws 8 random bits per element: its drop probability is round(256 p) / 256."""
-    return float(int(p * 256.0 + 0.5)) / 256.0
+    """The fused kernel draws 8 random bits per element: its drop probability is round(256 p) / 256.  A rate that rounds to
+    256/256 would keep nothing (keep scale 256 / 0): refused here, in the C entries' words, before anything is reserved."""
+    thr8 = int(p * 256.0 + 0.5)
+    if thr8 > 255:
+        raise ValueError(f"patch-layer dropout p = {p:g} is realised as round(256 p) / 256 = {thr8}/256: nothing would be kept "
+                         f"(p must be below 1 - 1/512)")
+    return float(thr8) / 256.0
 
 
 def patch_coattn_mcat(x_bf16, batch: BagBatch, patch_w, patch_b, drop_p: float, query, in_w, in_b, out_w, out_b,

@@ -288,25 +288,26 @@ def _tail(h_coattn, g_bag, a_coattn, p, fusion="concat", enc_keeps=None, pool_ke
 
 
 def mcat_forward(p, wsi, omics, inference=False, bag_storage=None, fusion="concat", round_gemm_out=False,
-                 storage_points=("x", "w", "h"), keep_h=None, ad_keeps=None, enc_keeps=None, pool_keeps=None):
+                 storage_points=("x", "w", "h"), keep_h=None, ad_keeps=None, enc_keeps=None, pool_keeps=None, drop_p=0.25):
     """MultimodalCoAttentionTransformer.forward, models/mcat/mcat.py:84-142 (eval mode).
     bag_storage / round_gemm_out: see patch_fc (the fused kernel of the 'medium' model rounds H_bag once).
     Training mode with given masks (every one None: eval): keep_h (M, d) the patch layer's dropout (patch_fc), ad_keeps
-    the SNN's AlphaDropout masks (omic_fc), enc_keeps / pool_keeps the two branches' (see _tail)."""
+    the SNN's AlphaDropout masks (omic_fc) at the model's rate drop_p (AlphaDropout's constants depend on it; every other mask
+    arrives pre-scaled), enc_keeps / pool_keeps the two branches' (see _tail)."""
     h_bag = patch_fc(wsi, p, keep=keep_h, storage=bag_storage, round_gemm_out=round_gemm_out, storage_points=storage_points)
-    g_bag = omic_fc(omics, p, ad_keeps=ad_keeps)
+    g_bag = omic_fc(omics, p, ad_keeps=ad_keeps, drop_p=drop_p)
     h_co, a_co = mcat_coattention(g_bag, h_bag, p, need_weights=inference)
     return _tail(h_co, g_bag, a_co, p, fusion, enc_keeps, pool_keeps)
 
 
 def nacagat_forward(p, wsi, omics, bag_storage=None, round_gemm_out=False, storage_points=("x", "w", "h"), keep_h=None,
-                    ad_keeps=None, keep_map=None, enc_keeps=None, pool_keeps=None):
+                    ad_keeps=None, keep_map=None, enc_keeps=None, pool_keeps=None, drop_p=0.25):
     """NarrowContextualAttentionGateTransformer.forward, models/nacagat/nacagat.py:80-138 (eval mode).
     bag_storage / round_gemm_out: see patch_fc (the 'medium' model's patch-layer kernel rounds H_bag once).
     Training mode with given masks: as mcat_forward, and keep_map (N, M) the co-attention map's dropout
     (pregating_contextual_attention; the returned map is then the dropped-out one)."""
     h_bag = patch_fc(wsi, p, keep=keep_h, storage=bag_storage, round_gemm_out=round_gemm_out, storage_points=storage_points)
-    g_bag = omic_fc(omics, p, ad_keeps=ad_keeps)
+    g_bag = omic_fc(omics, p, ad_keeps=ad_keeps, drop_p=drop_p)
     h_co, a_co = pregating_contextual_attention(g_bag, h_bag, p, keep=keep_map)
     return _tail(h_co, g_bag, a_co, p, enc_keeps=enc_keeps, pool_keeps=pool_keeps)
 

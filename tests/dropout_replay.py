@@ -266,3 +266,23 @@ def snn_keeps(seed, off, n_slides, n_groups, d, p, epoch=0):
         k2 = kept(seed, base + stride * (2 * i + 1), n_slides * n_groups * d, p).reshape(n_slides, n_groups * d)[:, :d]
         res.append((k1, k2))
     return res
+
+
+# ------------------------------------------------------------------------------------------- K2 map (NaCAGaT)
+def map_span(n_q: int, rows: int) -> int:
+    """ops.next_dropout_stream(n_q * rows) restated: one counter per four elements of the ragged map."""
+    return _ceil4(n_q * rows)
+
+
+def map_keeps(seed, off, n_q, lengths, p, epoch=0):
+    """Per slide the (n_q, M_b) keep scale of the co-attention map's dropout.  csrc/bag_maps.hip map_keep4 is dropout_keep
+    over the ABSOLUTE element index of the ragged map -- slide b's block starts at n_q * (rows before b), query q's row at
+    q * M_b inside it -- so the whole window is ONE stream of n_q * rows elements: kept(seed, off, n_q * rows, p), scale
+    1 / (1 - p)."""
+    rows = int(sum(lengths))
+    flat = keep_scale(seed, epoch_off(off, epoch), n_q * rows, p)
+    out, at = [], 0
+    for m in lengths:
+        out.append(flat[n_q * at:n_q * (at + m)].reshape(n_q, m))
+        at += m
+    return out

@@ -11,10 +11,14 @@ no record may be left over.  `host_keeps()` then rebuilds the SNN's, the encoder
 (seed, epoch) through dropout_replay's *_keeps functions and `slide_keeps()` cuts them into the per-slide arguments of
 oracle.mpo_oracle.mcat_forward / nacagat_forward.
 
-Two masks have no host restatement and are read back from the device, as the per-stage tests do: the patch layer's from the
-training-mode H_bag (zeros are ReLU zeros or dropped elements; both carry neither value nor gradient) and the K2 map's from
-the returned post-dropout map (the softmax is positive everywhere before dropout).  `tap()` captures both, and the outputs
-of forward_window, from an eager step."""
+The patch layer's mask has no host restatement and is read back from the device, as the per-stage tests do: from the
+training-mode H_bag (zeros are ReLU zeros or dropped elements; both carry neither value nor gradient).  The K2 map's can be
+read back the same way from the returned post-dropout map (the softmax is positive everywhere before dropout) or rebuilt on
+the host (`host_keeps(..., lengths=...)`, dropout_replay.map_keeps).  `tap()` captures both device read-backs, and the outputs
+of forward_window, from an eager step.
+
+Rates: P and MAP_P are the constructors' defaults; `host_keeps`, `patch_keep` and `map_keep` take the rate of the site they
+restate (the model's own, the pooling heads', the map's), so a step at other rates is replayed with each site's own."""
 from __future__ import annotations
 
 import contextlib
@@ -79,11 +83,17 @@ def ranges_overlap(records):
     return [(a, b) for a, b in zip(r, r[1:]) if b[0] <= a[1]]
 
 
-def host_keeps(sites, seed, epoch, n_slides, n_groups, d):
-    """The masks with a host restatement, window-wide: {'snn', 'encoder', 'pool'} as dropout_replay returns them."""
-    return {"snn": R.snn_keeps(seed, sites["snn"], n_slides, n_groups, d, P, epoch),
-            "encoder": R.encoder_keeps(seed, sites["encoder"], 2, n_slides, n_groups, d, FF, HEADS, LAYERS, P, epoch),
-            "pool": R.pool_keeps(seed, sites["pool"], 2, n_slides, n_groups, d, P, P, True, epoch)}
+def host_keeps(sites, seed, epoch, n_slides, n_groups, d, p=P, p_head=P, p_map=MAP_P, lengths=None):
+    """The masks with a host restatement, window-wide: {'snn', 'encoder', 'pool'} as dropout_replay returns them.  Three rates:
+    p the model's own (the constructor's `dropout`: SNN, both encoders, rho), p_head the pooling heads' scorer dropouts
+    (AttentionNetGated.drop_p), p_map the K2 map's (PreGatingContextualAttention.dropout).  With `lengths` (the slides' row
+    counts) and a 'map' site, 'map' is added: the per-slide keep scales of dropout_replay.map_keeps."""
+    keeps = {"snn": R.snn_keeps(seed, sites["snn"], n_slides, n_groups, d, p, epoch),
+             "encoder": R.encoder_keeps(seed, sites["encoder"], 2, n_slides, n_groups, d, FF, HEADS, LAYERS, p, epoch),
+             "pool": R.pool_keeps(seed, sites["pool"], 2, n_slides, n_groups, d, p_head, p, True, epoch)}
+    if lengths is not None and "map" in sites:
+        keeps["map"] = R.map_keeps(seed, sites["map"], n_groups, lengths, p_map, epoch)
+    return keeps
 
 
 def _t(a):
@@ -98,17 +108,20 @@ def slide_keeps(keeps, b):
     return dict(ad_keeps=ad, enc_keeps=enc, pool_keeps=pool)
 
 
-def patch_keep(h):
-    """The patch layer's keep scale read off the training-mode H_bag (rows, d)."""
+def patch_keep(h, p=P):
+    """The patch layer's keep scale read off the training-mode H_bag (rows, d).  The patch-layer kernels draw 8 bits per
+    element: the realised rate is thr8 / 256 with thr8 = round(256 p), and the survivors are scaled by 256 / (256 - thr8) --
+    NOT 1 / (1 - p), which is the same number only where 256 p is an integer (0.25, 0.5)."""
     h = h.detach().float().cpu()
     zeros = float((h == 0).double().mean())
-    assert 0.3 < zeros < 0.8, zeros                        # ~half ReLU zeros, a quarter of the rest dropped
-    return (h > 0).double() / (1.0 - P)
+    thr8 = int(p * 256.0 + 0.5)
+    assert 0.3 < zeros < 0.8 and thr8 < 256, (zeros, thr8)  # ~half ReLU zeros, thr8 / 256 of the rest dropped
+    return (h > 0).double() * (256.0 / (256.0 - thr8))
 
 
-def map_keep(a):
-    """The K2 map's keep scale read off one slide's post-dropout map (N, M_b)."""
-    return (a.detach().cpu() > 0).double() / (1.0 - MAP_P)
+def map_keep(a, p=MAP_P):
+    """The K2 map's keep scale read off one slide's post-dropout map (N, M_b); 24-bit site: 1 / (1 - p)."""
+    return (a.detach().cpu() > 0).double() / (1.0 - p)
 
 
 @contextlib.contextmanager

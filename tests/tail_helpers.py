@@ -10,7 +10,8 @@ Two ways to the same kernels:
 
 Both are compared with oracle/mpo_oracle.py in fp64 (`_encoder_oracle`, `_pool_oracle`), in training mode under the masks
 tests/dropout_replay.py rebuilds from (SEED, OFF).  Bars: forward 1e-4 of the reference's largest entry, dx and every parameter
-gradient 2e-3 of that tensor's largest entry."""
+gradient 2e-3 of that tensor's largest entry.  Every check takes the rate(s) of its sites (`p`; the pooling helpers `p_head`
+and `p_rho` separately), P = 0.25 by default; the omic SNN's check lives here too (`_snn_check`)."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -89,11 +90,11 @@ def _finite(what, **tensors):
 
 
 # ------------------------------------------------------------------------------------------- encoder
-def _encoder_setup(dev, nb, ns, T, d, seed, ff=FF, heads=HEADS, training=True):
+def _encoder_setup(dev, nb, ns, T, d, seed, ff=FF, heads=HEADS, training=True, p=P):
     sds, encs = [], []
     for br in range(nb):
         sd = syn.fill_state_dict(C.encoder_shapes("enc", d=d, ff=ff), seed + br)
-        enc = make_set_transformer(d, P, nhead=heads, dim_feedforward=ff, num_layers=LAYERS)
+        enc = make_set_transformer(d, p, nhead=heads, dim_feedforward=ff, num_layers=LAYERS)
         enc.load_state_dict({k[len("enc."):]: v for k, v in sd.items()}, strict=True)
         sds.append(sd)
         encs.append(enc.to(dev).train() if training else enc.to(dev).eval())
@@ -112,9 +113,9 @@ def _encoder_gpu(dev, sds, encs, x, probe, training=True):
     return y.detach().cpu(), grads[0].cpu(), [g.cpu() for g in grads[1:]]
 
 
-def encoder_guarded(dev, sds, x, probe, ff=FF, heads=HEADS, training=True, unaligned=()):
-    """mpo_encoder_forward + mpo_encoder_backward on guarded buffers; in training mode with (SEED, OFF) as the stream, which
-    is what `_pin` gives the ops path.  unaligned: (branch, parameter name) pairs placed one float into their storage.
+def encoder_guarded(dev, sds, x, probe, ff=FF, heads=HEADS, training=True, unaligned=(), p=P):
+    """mpo_encoder_forward + mpo_encoder_backward on guarded buffers; in training mode at rate p with (SEED, OFF) as the stream,
+    which is what `_pin` gives the ops path.  unaligned: (branch, parameter name) pairs placed one float into their storage.
     -> (y, dx, [grads]) on the CPU, like _encoder_gpu."""
     lib = L.lib()
     nb, ns, T, d = x.shape
@@ -125,7 +126,7 @@ def encoder_guarded(dev, sds, x, probe, ff=FF, heads=HEADS, training=True, unali
     shapes = [tuple(v.shape) for sd in sds for v in sd.values()]
     y = G.buf(x.numel())
     saved = G.buf(lib.mpo_encoder_saved_floats(bt, T, d, ff, heads, LAYERS))
-    p, seed, off = (P, SEED, OFF) if training else (0.0, 0, 0)
+    p, seed, off = (p, SEED, OFF) if training else (0.0, 0, 0)
     pa = L.ptr_array(params)
     L.call("mpo_encoder_forward", L.ptr(xb), nb, ns, T, d, ff, heads, LAYERS, pa, float(p), seed, off, ops._epoch(), L.ptr(y),
            L.ptr(saved), L.stream_of(xb))
@@ -173,25 +174,29 @@ def encoder_compare(tag, got, ref, sds):
     return e_y, e_dx, e_g[worst]
 
 
-def _encoder_check(dev, nb, ns, T, d, seed, epoch=0, ff=FF, heads=HEADS, training=True):
-    sds, encs, x, probe = _encoder_setup(dev, nb, ns, T, d, seed, ff, heads, training)
+def _encoder_check(dev, nb, ns, T, d, seed, epoch=0, ff=FF, heads=HEADS, training=True, p=P):
+    """p: the rate of every dropout site of the encoder (the modules are built with it)."""
+    sds, encs, x, probe = _encoder_setup(dev, nb, ns, T, d, seed, ff, heads, training, p)
     y, dx, grads = _encoder_gpu(dev, sds, encs, x, probe, training)
-    keeps = R.encoder_keeps(SEED, OFF, nb, ns, T, d, ff, heads, LAYERS, P, epoch) if training else None
+    keeps = R.encoder_keeps(SEED, OFF, nb, ns, T, d, ff, heads, LAYERS, p, epoch) if training else None
     ref = _encoder_oracle(sds, x, probe, keeps, heads)
-    encoder_compare(f"encoder nb={nb} ns={ns} T={T} d={d} heads={heads} ff={ff} epoch={epoch} training={training}",
+    encoder_compare(f"encoder nb={nb} ns={ns} T={T} d={d} heads={heads} ff={ff} epoch={epoch} training={training} p={p}",
                     (y, dx, grads), ref, sds)
     return dict(sds=sds, x=x, probe=probe, y=y, keeps=keeps)
 
 
 # ------------------------------------------------------------------------------------------- gated pool
-def _pool_setup(dev, nb, ns, L_, d, seed, rho_bias=None, training=True):
+def _pool_setup(dev, nb, ns, L_, d, seed, rho_bias=None, training=True, p_head=P, p_rho=P):
+    """p_head: the scorer's two dropouts (AttentionNetGated.drop_p, hard-wired to 0.25 by the constructor and set here);
+    p_rho: rho's nn.Dropout."""
     sds, heads, rhos = [], [], []
     for br in range(nb):
         sd = syn.fill_state_dict(C.pool_shapes("head", "rho", d=d), seed + br)
         if rho_bias is not None:
             sd["rho.0.bias"] = torch.full((d,), float(rho_bias))
         head = AttentionNetGated(n_classes=1, input_dim=d, hidden_dim=d)
-        rho = nn.Sequential(nn.Linear(d, d), nn.ReLU(), nn.Dropout(P))
+        head.drop_p = float(p_head)
+        rho = nn.Sequential(nn.Linear(d, d), nn.ReLU(), nn.Dropout(p_rho))
         head.load_state_dict({k[len("head."):]: v for k, v in sd.items() if k.startswith("head.")})
         rho.load_state_dict({k[len("rho."):]: v for k, v in sd.items() if k.startswith("rho.")})
         sds.append(sd)
@@ -221,7 +226,7 @@ def _pool_gpu(dev, sds, heads, rhos, x, probe_h, probe_a, interleave, training=T
     return sc[:, :, 0].detach().cpu(), h_std.detach().cpu(), grads[0].cpu(), [g.cpu() for g in grads[1:]]
 
 
-def pool_guarded(dev, sds, x, probe_h, probe_a, interleave, training=True, backward=True):
+def pool_guarded(dev, sds, x, probe_h, probe_a, interleave, training=True, backward=True, p_head=P, p_rho=P):
     """mpo_gated_pool_forward (+ mpo_gated_pool_backward) on guarded buffers -> (scores, h (nb, ns, d), dx, [grads]) on the
     CPU like _pool_gpu; without `backward` dx and grads are None and the guarded set is returned for a refusal test:
     (scores, h, None, None, state)."""
@@ -235,9 +240,9 @@ def pool_guarded(dev, sds, x, probe_h, probe_a, interleave, training=True, backw
     scores = G.buf(bt * L_)
     h = G.buf(bt * d)
     saved = G.buf(lib.mpo_gated_pool_saved_floats(bt, L_, d))
-    p, seed, off = (P, SEED, OFF) if training else (0.0, 0, 0)
+    (p_head, p_rho), seed, off = ((p_head, p_rho), SEED, OFF) if training else ((0.0, 0.0), 0, 0)
     pa = L.ptr_array(params)
-    L.call("mpo_gated_pool_forward", L.ptr(xb), nb, ns, L_, d, pa, float(p), float(p), seed, off, ops._epoch(), L.ptr(scores),
+    L.call("mpo_gated_pool_forward", L.ptr(xb), nb, ns, L_, d, pa, float(p_head), float(p_rho), seed, off, ops._epoch(), L.ptr(scores),
            L.ptr(h), int(interleave), L.ptr(saved), L.stream_of(xb))
     h_std = (h.view(ns, nb, d).transpose(0, 1) if interleave else h.view(nb, ns, d))
     dh = G.buf(bt * d, probe_h.transpose(0, 1).contiguous() if interleave else probe_h)
@@ -249,7 +254,7 @@ def pool_guarded(dev, sds, x, probe_h, probe_a, interleave, training=True, backw
     ga = L.ptr_array(grads)
 
     def run_backward():
-        L.call("mpo_gated_pool_backward", L.ptr(xb), nb, ns, L_, d, pa, float(p), float(p), L.ptr(saved), L.ptr(h), L.ptr(dh),
+        L.call("mpo_gated_pool_backward", L.ptr(xb), nb, ns, L_, d, pa, float(p_head), float(p_rho), L.ptr(saved), L.ptr(h), L.ptr(dh),
                int(interleave), L.ptr(d_ext), L.ptr(dx), ga, L.ptr(ws), ws_bytes, L.stream_of(xb))
     if not backward:
         G.check("gated pool forward")
@@ -306,11 +311,62 @@ def pool_compare(tag, got, ref, sds, forward_only=False):
     return e_sc, e_h, e_dx, e_g[worst]
 
 
-def _pool_check(dev, ns, L_, interleave, seed, epoch=0, nb=2, d=256, training=True):
-    sds, heads, rhos, x, ph, pa = _pool_setup(dev, nb, ns, L_, d, seed, training=training)
+def _pool_check(dev, ns, L_, interleave, seed, epoch=0, nb=2, d=256, training=True, p_head=P, p_rho=P):
+    sds, heads, rhos, x, ph, pa = _pool_setup(dev, nb, ns, L_, d, seed, training=training, p_head=p_head, p_rho=p_rho)
     sc, h, dx, grads = _pool_gpu(dev, sds, heads, rhos, x, ph, pa, interleave, training)
-    keeps = R.pool_keeps(SEED, OFF, nb, ns, L_, d, P, P, interleave, epoch) if training else None
+    keeps = R.pool_keeps(SEED, OFF, nb, ns, L_, d, p_head, p_rho, interleave, epoch) if training else None
     ref = _pool_oracle(sds, x, ph, pa, keeps)
-    pool_compare(f"pool nb={nb} ns={ns} L={L_} d={d} interleave={interleave} epoch={epoch} training={training}",
+    pool_compare(f"pool nb={nb} ns={ns} L={L_} d={d} interleave={interleave} epoch={epoch} training={training} p_head={p_head} p_rho={p_rho}",
                  (sc, h, dx, grads), ref, sds)
     return dict(sds=sds, x=x, ph=ph, pa=pa, sc=sc, h=h, keeps=keeps)
+
+
+# ------------------------------------------------------------------------------------------- omic SNN
+SNN_SIZES = [100, 31, 256, 8, 300, 64]          # ragged widths (test_gpu_tail.py's)
+
+
+def _snn_setup(dev, ns, seed, p=P):
+    torch.manual_seed(seed)
+    G = nn.ModuleList([nn.Sequential(
+        nn.Sequential(nn.Linear(s, C.E), nn.ELU(), nn.AlphaDropout(p=p, inplace=False)),
+        nn.Sequential(nn.Linear(C.E, C.E), nn.ELU(), nn.AlphaDropout(p=p, inplace=False))) for s in SNN_SIZES]).to(dev)
+    G.train()
+    g = syn.rng(seed + 1)
+    xs = [syn.normal(g, (ns, s)) for s in SNN_SIZES]
+    probe = syn.normal(g, (ns, len(SNN_SIZES), C.E))
+    return G, xs, probe
+
+
+def _snn_gpu(dev, G, xs, probe):
+    _pin()
+    y = ops.omic_snn([x.to(dev) for x in xs], G, training=True)
+    grads = torch.autograd.grad((y * probe.to(dev)).sum(), list(G.parameters()))
+    return y.detach().cpu(), [g.cpu() for g in grads]
+
+
+def _snn_oracle(G, xs, probe, keeps, p=P):
+    prm = {"G." + k: v.detach().double().cpu().requires_grad_(True) for k, v in G.state_dict().items()}
+    ns = xs[0].shape[0]
+    ys = []
+    for s in range(ns):
+        ad = [(_t(k1[s]), _t(k2[s])) for k1, k2 in keeps]
+        ys.append(O.omic_fc([x[s].double() for x in xs], prm, "G", ad_keeps=ad, drop_p=p))
+    yo = torch.stack(ys)                                   # (ns, N, d)
+    (yo * probe.double()).sum().backward()
+    return yo.detach(), [prm["G." + k].grad for k, _ in G.named_parameters()]
+
+
+def _snn_check(dev, ns, seed, epoch=0, p=P):
+    G, xs, probe = _snn_setup(dev, ns, seed, p)
+    y, grads = _snn_gpu(dev, G, xs, probe)
+    keeps = R.snn_keeps(SEED, OFF, ns, len(SNN_SIZES), C.E, p, epoch)
+    yo, go = _snn_oracle(G, xs, probe, keeps, p)
+    e_y = relerr(y, yo)
+    e_g = grad_errs(grads, go)
+    names = [k for k, _ in G.named_parameters()]
+    worst = int(np.argmax(e_g))
+    print(f"omic SNN ns={ns} epoch={epoch} p={p}: y {e_y:.1e} grads max {e_g[worst]:.1e} ({names[worst]})")
+    assert e_y < FWD_TOL, e_y
+    for n, e in zip(names, e_g):
+        assert e < GRAD_TOL, (n, e)
+    return y, keeps

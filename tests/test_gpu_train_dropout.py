@@ -10,7 +10,6 @@ at the end replay deliberately wrong masks to show the comparison can fail."""
 import numpy as np
 import pytest
 import torch
-import torch.nn as nn
 
 import cases as C
 import dropout_replay as R
@@ -19,8 +18,8 @@ from multimodal_path_omic_amd import ops
 from multimodal_path_omic_amd import synthetic as syn
 from multimodal_path_omic_amd.transformer import make_set_transformer
 from oracle import mpo_oracle as O
-from tail_helpers import (FF, FWD_TOL, GRAD_TOL, HEADS, LAYERS, OFF, P, SEED, _encoder_check, _encoder_oracle, _pin, _pool_check,
-                          _pool_oracle, _pool_setup, _t, grad_errs, relerr)
+from tail_helpers import (FF, FWD_TOL, HEADS, LAYERS, OFF, P, SEED, SNN_SIZES, _encoder_check, _encoder_oracle, _pin, _pool_check,
+                          _pool_oracle, _pool_setup, _snn_check, _snn_setup, _t, grad_errs, relerr)
 
 pytestmark = pytest.mark.gpu
 
@@ -111,56 +110,6 @@ def test_pool_rho_zeros_are_exactly_the_dropped_elements(dev):
 
 
 # ------------------------------------------------------------------------------------------- omic SNN
-SNN_SIZES = [100, 31, 256, 8, 300, 64]          # ragged widths (test_gpu_tail.py's)
-
-
-def _snn_setup(dev, ns, seed):
-    torch.manual_seed(seed)
-    G = nn.ModuleList([nn.Sequential(
-        nn.Sequential(nn.Linear(s, C.E), nn.ELU(), nn.AlphaDropout(p=P, inplace=False)),
-        nn.Sequential(nn.Linear(C.E, C.E), nn.ELU(), nn.AlphaDropout(p=P, inplace=False))) for s in SNN_SIZES]).to(dev)
-    G.train()
-    g = syn.rng(seed + 1)
-    xs = [syn.normal(g, (ns, s)) for s in SNN_SIZES]
-    probe = syn.normal(g, (ns, len(SNN_SIZES), C.E))
-    return G, xs, probe
-
-
-def _snn_gpu(dev, G, xs, probe):
-    _pin()
-    y = ops.omic_snn([x.to(dev) for x in xs], G, training=True)
-    grads = torch.autograd.grad((y * probe.to(dev)).sum(), list(G.parameters()))
-    return y.detach().cpu(), [g.cpu() for g in grads]
-
-
-def _snn_oracle(G, xs, probe, keeps):
-    p = {"G." + k: v.detach().double().cpu().requires_grad_(True) for k, v in G.state_dict().items()}
-    ns = xs[0].shape[0]
-    ys = []
-    for s in range(ns):
-        ad = [(_t(k1[s]), _t(k2[s])) for k1, k2 in keeps]
-        ys.append(O.omic_fc([x[s].double() for x in xs], p, "G", ad_keeps=ad, drop_p=P))
-    yo = torch.stack(ys)                                   # (ns, N, d)
-    (yo * probe.double()).sum().backward()
-    return yo.detach(), [p["G." + k].grad for k, _ in G.named_parameters()]
-
-
-def _snn_check(dev, ns, seed, epoch=0):
-    G, xs, probe = _snn_setup(dev, ns, seed)
-    y, grads = _snn_gpu(dev, G, xs, probe)
-    keeps = R.snn_keeps(SEED, OFF, ns, len(SNN_SIZES), C.E, P, epoch)
-    yo, go = _snn_oracle(G, xs, probe, keeps)
-    e_y = relerr(y, yo)
-    e_g = grad_errs(grads, go)
-    names = [k for k, _ in G.named_parameters()]
-    worst = int(np.argmax(e_g))
-    print(f"omic SNN ns={ns} epoch={epoch}: y {e_y:.1e} grads max {e_g[worst]:.1e} ({names[worst]})")
-    assert e_y < FWD_TOL, e_y
-    for n, e in zip(names, e_g):
-        assert e < GRAD_TOL, (n, e)
-    return y, keeps
-
-
 @pytest.mark.parametrize("ns", [1, 5, 32])
 def test_omic_snn_training_equals_fp64_oracle(dev, ns):
     _snn_check(dev, ns, 700 + ns)

@@ -86,9 +86,12 @@ def _slides(lengths=LENGTHS):
                  censorship=b % 2) for b, m in enumerate(lengths)]
 
 
-def _build(dev, kind, dtype, fusion="concat"):
+def _build(dev, kind, dtype, fusion="concat", rates=None):
+    """rates: None (every site at the constructors' 0.25) or (the model's `dropout`, the pooling heads' drop_p)."""
     cls = MultimodalCoAttentionTransformer if kind == "mcat" else NarrowContextualAttentionGateTransformer
-    model = cls(omic_sizes=SIZES, bag_dtype=dtype, fusion=fusion)
+    model = cls(omic_sizes=SIZES, bag_dtype=dtype, fusion=fusion, **({} if rates is None else {"dropout": rates[0]}))
+    if rates is not None:
+        model.path_attention_head.drop_p = model.omic_attention_head.drop_p = float(rates[1])
     shapes = C.model_shapes(SIZES, kind == "nacagat") if fusion == "concat" else \
         {k: tuple(v.shape) for k, v in model.state_dict().items()}
     sd = syn.fill_state_dict(shapes, WEIGHTS)
@@ -119,7 +122,7 @@ def _pin(dev, calls, epoch):
 
 
 # ------------------------------------------------------------------------------------------- the eager step and its oracle
-_RUNS = {}          # (kind, dtype, fusion, epoch) -> the eager step's outputs and masks; computed once per case, never written afterwards
+_RUNS = {}          # (kind, dtype, fusion, epoch, rates) -> the eager step's outputs and masks; computed once per case, never written afterwards
 
 
 def _head_sites(fusion):
@@ -127,13 +130,15 @@ def _head_sites(fusion):
     return {"bilinear head": F.bilinear_span(B, D)} if fusion == "bilinear" else None
 
 
-def _eager_run(dev, kind, dtype, epoch, fusion="concat"):
-    key = (kind, dtype, fusion, epoch)
+def _eager_run(dev, kind, dtype, epoch, fusion="concat", rates=None):
+    """rates: see _build; the masks are then rebuilt at those rates (the K2 map's stays at the module's own S.MAP_P)."""
+    key = (kind, dtype, fusion, epoch, rates)
     if key in _RUNS:
         return _RUNS[key]
-    if any(k[:3] != key[:3] for k in _RUNS):                 # one case's runs at a time (each holds a model's worth of gradients)
+    if any(k[:3] != key[:3] or k[4] != rates for k in _RUNS):    # one case's runs at a time (each holds a model's worth of gradients)
         _RUNS.clear()
-    model, sd = _build(dev, kind, dtype, fusion)
+    p, p_head = (S.P, S.P) if rates is None else rates
+    model, sd = _build(dev, kind, dtype, fusion, rates)
     window = harness.make_window(_slides(), dev, dtype)
     bucket = FlatGradBucket(list(model.parameters()))
     _pin(dev, BASE, epoch)
@@ -146,11 +151,11 @@ def _eager_run(dev, kind, dtype, epoch, fusion="concat"):
     run = dict(sd=sd, fusion=fusion, records=list(records), loss=loss.detach().cpu(), risk=risk.detach().cpu(), hazards=hz.detach().cpu(),
                path=att["path"].detach().cpu(), omic=att["omic"].detach().cpu(),
                grads={n: p._mpo_grad_view.detach().cpu().clone() for n, p in model.named_parameters()},
-               keep_h=S.patch_keep(got["h"]),
+               p=p, keep_h=S.patch_keep(got["h"], p),
                keep_maps=[S.map_keep(a) for a in got["maps"]] if kind == "nacagat" else None)
     assert tuple(got["h"].shape) == (ROWS, D) and run["path"].shape == (B, 1, N)
     run["sites"] = S.match_sites(run["records"], kind, ROWS, B, N, D, _head_sites(fusion))
-    run["host"] = S.host_keeps(run["sites"], SEED, epoch or 0, B, N, D)
+    run["host"] = S.host_keeps(run["sites"], SEED, epoch or 0, B, N, D, p, p_head, S.MAP_P, LENGTHS)
     if fusion == "bilinear":
         rate = ops._bilinear_drop_p(model.fusion_layer, True)
         assert rate > 0
@@ -179,7 +184,7 @@ def _oracle(kind, dtype, run, host=None, keep_h=None, keep_maps=None, head_keeps
         if kind == "nacagat":
             kw["keep_map"] = keep_maps[b]
         fwd = O.mcat_forward if kind == "mcat" else O.nacagat_forward
-        hz, sv, _, att = fwd(p, s["wsi"], s["omics"], bag_storage=storage, **kw)
+        hz, sv, _, att = fwd(p, s["wsi"], s["omics"], bag_storage=storage, drop_p=run["p"], **kw)
         loss = O.ces_loss(hz, sv, torch.tensor([s["survival_class"]]), torch.tensor([float(s["censorship"])]))
         total = total + loss / ACC                               # slide weight 1 / grad_acc_step
         for k, v in (("loss", loss.reshape(())), ("risk", O.risk_score(sv)[0]), ("hazards", hz[0]), ("path", att["path"]),
