@@ -572,6 +572,10 @@ int mpo_coattn_bwd_bagpass(const void* bag, int bag_dtype, const int32_t* cu_row
  * (csrc/concordance.hip, csrc/map_stats.hip): likewise additive to ABI 14. */
 #include "mpo_eval.h"
 
+/* ---- classification metrics of the gene-expression model's validation and test epochs on the device
+ * (csrc/class_metrics.hip): likewise additive to ABI 14. */
+#include "mpo_classify.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -271,7 +271,8 @@ class GraphedWindowStep:
     A window whose first element is an ops.SlideSet (ResidentCohort.window) captures the gather from separately stored
     slides instead: bind() then takes further SlideSet windows -- slide ids into a cohort that lives on the device, no copy
     and no H2D transfer per window -- and a SlideSet with `cycle` may hold slides shorter than k (lapped).  A step captured
-    on one kind of window refuses the other: the two gathers read different descriptors.  train_epoch drives an epoch.
+    on one kind of window refuses the other: the two gathers read different descriptors.  train_epoch drives an epoch
+    (the gene-expression model's (SlideSet, labels) windows of a GeResidentCohort: train_ge_epoch).
     """
 
     def __init__(self, model, bucket, window, grad_acc_step: int, opt=None, warmup: int = 2, pool=None,
@@ -482,6 +483,45 @@ class GraphedWindowStep:
 
 
 # ------------------------------------------------------------------------------------ a cohort resident on the device
+def _cohort_slabs(cohort, who: str, slides: Sequence[dict], bag_dtype, slab_bytes: int):
+    """The row storage of a resident cohort (ResidentCohort, GeResidentCohort; `who` names it in the refusals), on
+    cohort.device: `lengths`, `slabs` (at most slab_bytes each, a slide never split), `rows` (per slide a view of its slab) and
+    where a slide lies, `slab_index` / `row_offset`, set on `cohort`."""
+    if len(slides) == 0:
+        raise ValueError(f"{who}: no slides")
+    cohort.lengths = [int(s["wsi"].shape[0]) for s in slides]
+    width = int(slides[0]["wsi"].shape[1])
+    row_bytes = width * torch.empty(0, dtype=bag_dtype).element_size()
+    if row_bytes % 16:
+        raise ValueError(f"{who}: a row of {row_bytes} bytes is not a multiple of 16 bytes")
+    if any(m < 1 for m in cohort.lengths) or any(int(s["wsi"].shape[1]) != width for s in slides):
+        raise ValueError(f"{who}: every slide needs at least one patch row, and all the same width")
+    cohort.slabs, cohort.rows, group = [], [], []
+    # where a slide lies: its slab and its first row there (slides of one slab lie back to back in id order, so a run of
+    # consecutive ids inside one slab is a contiguous row range: the evaluators' windows are views of it)
+    cohort.slab_index, cohort.row_offset = [], []
+
+    def flush():
+        if group:
+            slab = torch.cat([slides[i]["wsi"] for i in group]).to(device=cohort.device, dtype=bag_dtype, non_blocking=True)
+            cohort.slabs.append(slab)
+            cohort.rows.extend(slab.split([cohort.lengths[i] for i in group]))
+            first = 0
+            for i in group:
+                cohort.slab_index.append(len(cohort.slabs) - 1)
+                cohort.row_offset.append(first)
+                first += cohort.lengths[i]
+            group.clear()
+    filled = 0
+    for i, m in enumerate(cohort.lengths):
+        if group and filled + m * row_bytes > slab_bytes:
+            flush()
+            filled = 0
+        group.append(i)
+        filled += m * row_bytes
+    flush()
+
+
 class ResidentCohort:
     """A cohort that lives on the device once, for shuffled epochs of the sampled, captured step (bag_dtype bf16, or fp32
     for a step captured with device_feature_scale=True): every slide's rows (in
@@ -491,43 +531,11 @@ class ResidentCohort:
 
     slides: the dict layout make_window takes (synthetic.make_cohort).  cycle: the windows lap a slide shorter than the
     step's k in its permuted order instead of refusing it (ops.SlideSet).  Only the survival layout is built; a
-    gene-expression cohort ((SlideSet, labels) windows) is not."""
+    gene-expression cohort ((SlideSet, labels) windows) is not -- GeResidentCohort is that one, over the same storage."""
 
     def __init__(self, slides: Sequence[dict], device, bag_dtype=torch.bfloat16, cycle: bool = False, slab_bytes: int = 1 << 30):
-        if len(slides) == 0:
-            raise ValueError("ResidentCohort: no slides")
         self.device, self.cycle = torch.device(device), bool(cycle)
-        self.lengths = [int(s["wsi"].shape[0]) for s in slides]
-        width = int(slides[0]["wsi"].shape[1])
-        row_bytes = width * torch.empty(0, dtype=bag_dtype).element_size()
-        if row_bytes % 16:
-            raise ValueError(f"ResidentCohort: a row of {row_bytes} bytes is not a multiple of 16 bytes")
-        if any(m < 1 for m in self.lengths) or any(int(s["wsi"].shape[1]) != width for s in slides):
-            raise ValueError("ResidentCohort: every slide needs at least one patch row, and all the same width")
-        self.slabs, self.rows, group = [], [], []
-        # where a slide lies: its slab and its first row there (slides of one slab lie back to back in id order, so a run of
-        # consecutive ids inside one slab is a contiguous row range: CohortEvaluator's windows are views of it)
-        self.slab_index, self.row_offset = [], []
-
-        def flush():
-            if group:
-                slab = torch.cat([slides[i]["wsi"] for i in group]).to(device=self.device, dtype=bag_dtype, non_blocking=True)
-                self.slabs.append(slab)
-                self.rows.extend(slab.split([self.lengths[i] for i in group]))
-                first = 0
-                for i in group:
-                    self.slab_index.append(len(self.slabs) - 1)
-                    self.row_offset.append(first)
-                    first += self.lengths[i]
-                group.clear()
-        filled = 0
-        for i, m in enumerate(self.lengths):
-            if group and filled + m * row_bytes > slab_bytes:
-                flush()
-                filled = 0
-            group.append(i)
-            filled += m * row_bytes
-        flush()
+        _cohort_slabs(self, "ResidentCohort", slides, bag_dtype, slab_bytes)
         self.table_ptrs, self.table_lens = SlideSet.slide_table(self.rows)
         n_groups = len(slides[0]["omics"])
         self.omics = [torch.stack([s["omics"][i] for s in slides]).to(self.device, non_blocking=True) for i in range(n_groups)]
@@ -920,3 +928,317 @@ def test(model, cohort: ResidentCohort, ids, save_dir=None, name: str = "ATTN"):
 
 
 test.__test__ = False           # (a public name that starts with "test": not a pytest case where a test module imports it)
+
+
+# ------------------------------------------------------------------------------------ the gene-expression model's epochs
+def classification_metrics(y, label, loss=None):
+    """The host form of csrc/class_metrics.hip, and its definition: y (n, C) class scores, label (n,) integers, loss (n,) or
+    None, tensors anywhere (copied to the host) -> (pred (n,) int64, confusion (C, C) int64, counts (4,) int64, summary
+    (3,) fp64), CPU tensors.
+      pred_b = torch.argmax(y[b]): the first index of a NaN if the row holds one, otherwise the first index of the maximum;
+      a label is valid when 0 <= label_b < C;  confusion[label_b][pred_b] += 1 over the valid rows;
+      counts = [valid, correct, invalid labels, rows with a NaN];
+      summary[0] = correct / valid (NaN when valid == 0);  summary[1] = the mean of confusion[c][c] / support_c over the classes
+      with support_c > 0, added in class order (NaN when there is none);  summary[2] = sum(loss) / n in fp64 over all n rows
+      (NaN when loss is None; a NaN loss propagates)."""
+    y = torch.as_tensor(y).detach().to("cpu", torch.float32)
+    label = torch.as_tensor(label).detach().to("cpu", torch.int64).reshape(-1)
+    if y.dim() != 2 or int(y.shape[0]) != int(label.numel()) or y.shape[0] == 0:
+        raise ValueError(f"classification_metrics: y {tuple(y.shape)} for {int(label.numel())} labels ((n, C) and n, n at least 1)")
+    n, c = int(y.shape[0]), int(y.shape[1])
+    pred = torch.argmax(y, dim=1)
+    valid = (label >= 0) & (label < c)
+    cells = label[valid] * c + pred[valid]
+    confusion = torch.bincount(cells, minlength=c * c).view(c, c).to(torch.int64)
+    n_valid, correct = int(valid.sum()), int(confusion.diagonal().sum())
+    counts = torch.tensor([n_valid, correct, n - n_valid, int(torch.isnan(y).any(dim=1).sum())], dtype=torch.int64)
+    nan = float("nan")
+    recalls = [int(confusion[k, k]) / int(confusion[k].sum()) for k in range(c) if int(confusion[k].sum()) > 0]
+    recall_sum = 0.0
+    for r in recalls:
+        recall_sum += r
+    mean_loss = nan
+    if loss is not None:
+        loss = torch.as_tensor(loss).detach().to("cpu", torch.float64).reshape(-1)
+        if int(loss.numel()) != n:
+            raise ValueError(f"classification_metrics: {int(loss.numel())} losses for {n} rows")
+        mean_loss = float(loss.sum()) / n
+    summary = torch.tensor([correct / n_valid if n_valid else nan, recall_sum / len(recalls) if recalls else nan, mean_loss],
+                           dtype=torch.float64)
+    return pred, confusion, counts, summary
+
+
+def classification_metrics_device(y, label, loss=None, want_pred: bool = True):
+    """classification_metrics(y, label, loss) computed on the device (csrc/class_metrics.hip): y (n, C) and loss (n,) are read
+    as fp32, label as int64 (converted where they are not).  Returns (pred (n,) int64 -- None with want_pred=False --,
+    confusion (C, C) int64, counts (4,) int64 = valid, correct, invalid labels, rows with a NaN, summary (3,) fp64 =
+    accuracy, balanced accuracy, mean loss) on the device.  Two launches, no host synchronisation; capturable.  Raises
+    ValueError for what the host knows: a tensor that is not on the GPU, different devices, lengths that differ, n == 0, C
+    outside 2..8."""
+    from . import ops
+    given = [("y", y), ("label", label)] + ([("loss", loss)] if loss is not None else [])
+    for name, t in given:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"classification_metrics_device: {name} must be a tensor on the GPU "
+                             "(classification_metrics is the host form)")
+    if len({t.device for _, t in given}) != 1:
+        raise ValueError("classification_metrics_device: y, label and loss lie on different devices")
+    if y.dim() != 2:
+        raise ValueError(f"classification_metrics_device: y is (n, C), got {tuple(y.shape)}")
+    n, c = int(y.shape[0]), int(y.shape[1])
+    if n == 0 or int(label.numel()) != n or (loss is not None and int(loss.numel()) != n):
+        raise ValueError(f"classification_metrics_device: {n} rows of y, {int(label.numel())} labels"
+                         + (f" and {int(loss.numel())} losses" if loss is not None else "") + " (equal and at least one)")
+    if not 2 <= c <= 8:
+        raise ValueError(f"classification_metrics_device: {c} classes outside 2..8 (the head's range)")
+    return ops.class_metrics(y.detach().to(torch.float32).contiguous(), label.detach().reshape(-1).to(torch.int64).contiguous(),
+                             None if loss is None else loss.detach().reshape(-1).to(torch.float32).contiguous(), want_pred)
+
+
+class GeResidentCohort:
+    """ResidentCohort for the gene-expression model: every slide's rows on the device once, in the same storage -- slabs of at
+    most `slab_bytes`, a slide never split; `rows`, `lengths`, `slab_index`, `row_offset`, the pointer / length table
+    (`table_ptrs`, `table_lens`), `cycle`, `n_slides` -- and `labels` (N,) int64 on the device.
+    slides: the dict layout make_ge_window takes ({'wsi', 'gene_expr_class'}: synthetic.make_ge_cohort)."""
+
+    def __init__(self, slides: Sequence[dict], device, bag_dtype=torch.bfloat16, cycle: bool = False, slab_bytes: int = 1 << 30):
+        self.device, self.cycle = torch.device(device), bool(cycle)
+        _cohort_slabs(self, "GeResidentCohort", slides, bag_dtype, slab_bytes)
+        self.table_ptrs, self.table_lens = SlideSet.slide_table(self.rows)
+        self.labels = torch.tensor([int(s["gene_expr_class"]) for s in slides], dtype=torch.int64).to(self.device, non_blocking=True)
+
+    @property
+    def n_slides(self):
+        return len(self.lengths)
+
+    def window(self, ids_dev, ids_host, out=None):
+        """(SlideSet, labels) for the slides `ids_host` (host ints) = `ids_dev` (DEVICE int32, the same values): the tuple a
+        gene-expression step takes.  The labels are selected on the device, into `out` = (labels,) where given (a captured
+        step's static tensor, step.window[1:]).  No H2D copy and no host synchronisation; what ResidentCohort.window says
+        about the two copies of the ids and about `out` holds here."""
+        ids_host = [int(i) for i in ids_host]
+        for i in ids_host:
+            if not 0 <= i < self.n_slides:
+                raise ValueError(f"GeResidentCohort.window: slide id {i} outside the cohort's {self.n_slides} slides")
+        bags = SlideSet([self.rows[i] for i in ids_host], [self.lengths[i] for i in ids_host], self.table_ptrs, self.table_lens,
+                        ids_dev, self.cycle)
+        return bags, torch.index_select(self.labels, 0, ids_dev, out=None if out is None else out[0])
+
+
+def train_ge_epoch(step: "GraphedWindowStep", cohort: GeResidentCohort, order):
+    """train_epoch for the gene-expression model: one shuffled epoch of a step captured on a (SlideSet, labels) window of a
+    GeResidentCohort with sample_rows=k, bf16 or fp32 (an fp32 step is captured with device_feature_scale=True).  `order`:
+    host sequence of slide ids, validated once -- range, and every slide at least k rows unless the cohort laps -- and
+    uploaded once.  Per window of the step's slide count the loop enqueues the bind (one tiny launch), the label select
+    into the step's static tensor, one replay and one device-to-device copy of the per-bag loss.  No host synchronisation
+    and no H2D copy inside the loop.
+
+    Returns (loss, ids_run, leftover): loss (n_run,) fp32 and ids_run (n_run,) int32 on the device, in the order the slides
+    ran; `leftover` the host ids of the final partial window, which are NOT run (the graph has one shape) -- run them
+    eagerly where they matter:
+        bags, labels = cohort.window(torch.tensor(leftover, dtype=torch.int32, device=dev), leftover)
+        train_ge_window(model, bags.materialize(), labels, grad_acc_step, sample_rows=k)"""
+    if not step.ge or step.sampler is None or step.sampler.source != "slides":
+        raise ValueError("train_ge_epoch: the step must be a gene-expression step captured with sample_rows on a "
+                         "GeResidentCohort window")
+    if not isinstance(cohort, GeResidentCohort):
+        raise ValueError(f"train_ge_epoch: a GeResidentCohort holds the gene-expression layout, not a {type(cohort).__name__}")
+    n, k = step.sampler.n_slides, step.sampler.k
+    if (int(cohort.rows[0].shape[1]), cohort.rows[0].dtype) != (step.sampler.width, step.sampler.dtype):
+        raise ValueError(f"train_ge_epoch: the cohort's rows are {int(cohort.rows[0].shape[1])} x {cohort.rows[0].dtype}, the step "
+                         f"was captured for {step.sampler.width} x {step.sampler.dtype}")
+    order = [int(i) for i in order]
+    for i in order:
+        if not 0 <= i < cohort.n_slides:
+            raise ValueError(f"train_ge_epoch: slide id {i} outside the cohort's {cohort.n_slides} slides")
+        if not cohort.cycle and cohort.lengths[i] < k:
+            raise ValueError(f"train_ge_epoch: slide {i} has {cohort.lengths[i]} rows, fewer than k = {k}, and the cohort does not "
+                             "lap short slides (cycle=False)")
+    n_win = len(order) // n
+    leftover = order[n_win * n:]
+    dev = cohort.device
+    order_dev = torch.tensor(order[:n_win * n], dtype=torch.int32).to(dev, non_blocking=True)
+    loss = torch.empty(n_win * n, dtype=torch.float32, device=dev)
+    static = step.window[1:]
+    for w in range(n_win):
+        lo, hi = w * n, (w + 1) * n
+        step.bind(cohort.window(order_dev[lo:hi], order[lo:hi], out=static))
+        loss[lo:hi].copy_(step().view(-1), non_blocking=True)
+    return loss, order_dev, leftover
+
+
+@dataclass
+class GeEvalResult:
+    """What one evaluation of a gene-expression cohort leaves on the device, per slide in the caller's `ids` order: loss (n,),
+    Y (n, C), pred (n,) int64; and over all of them confusion (C, C) and counts (4,) int64 (valid, correct, invalid labels,
+    rows with a NaN), mean_loss, accuracy, balanced_accuracy (1,) fp64.  paths / path_stats: only where the evaluator ran
+    with need_paths (test_ge()): per slide the (1, M_b) pooling attention and (n, 3) [min, max, mean] of it.  Nothing here has
+    been read by the host."""
+    loss: torch.Tensor
+    Y: torch.Tensor
+    pred: torch.Tensor
+    confusion: torch.Tensor
+    counts: torch.Tensor
+    mean_loss: torch.Tensor
+    accuracy: torch.Tensor
+    balanced_accuracy: torch.Tensor
+    paths: "List[torch.Tensor] | None" = None
+    path_stats: "torch.Tensor | None" = None
+
+    def accuracy_value(self) -> float:
+        """The accuracy as a Python float: the one method that reads the host (it waits for the evaluation).  NaN where no
+        label was valid."""
+        return float(self.accuracy)
+
+
+class GeCohortEvaluator:
+    """CohortEvaluator for the gene-expression model: the reference's validate() (models/ge_nacagat/main.py:85-119) -- eval
+    mode, no gradients, per-slide `ce` loss and Y, accuracy over the set -- over slides of a GeResidentCohort with nothing
+    copied and nothing read by the host.
+
+    ids: host sequence of slide ids, validated and uploaded once, here; a duplicate is an error, and so is a slide shorter
+    than the model's window floor (MIN_WINDOW_ROWS).  cut_eval_windows cuts them into runs of slides that lie back to back in
+    one slab; each run's window is a BagBatch over a row slice of the slab -- a view -- whose cu, work plan and label select
+    are built once.  Results come back in the caller's `ids` order, by one device permutation.
+
+    A call runs, per window, forward_window(bags, need_maps=False) in eval mode under torch.no_grad() (the mode it found is
+    put back) with the `ce` loss riding in the head's launch (ops.ge_head_loss, forward only): no M x M map is ever
+    allocated.  l1 > 0 adds l1 * sum|W| to every reported loss.  An fp32 cohort's windows that reach the scaled patch kernel
+    find their feature scale on the device (ops.feature_scale_device).  Then one classification_metrics_device over the set.
+    Everything is enqueued on the current stream; the call returns a GeEvalResult without synchronising.
+
+    capture=True: CohortEvaluator's recipe -- one graph per window, a shared pool, capture_error_mode thread_local; parameters
+    and rows are read in place, so the evaluator follows FlatOptimizer updates (build the optimiser first).  need_paths is
+    refused under capture: the map is an output.
+    need_paths (eager only; test_ge() sets it): the result carries every slide's (1, M_b) pooling attention and
+    ops.map_block_stats of it (n_q = 1)."""
+
+    def __init__(self, model, cohort: GeResidentCohort, ids, l1: float = 0.0, max_window_rows: int = 1 << 19,
+                 max_window_slides: int = 32, capture: bool = False, pool=None, need_paths: bool = False):
+        from . import ops
+        from .models import GeneExprNarrowContextualAttentionGateTransformer
+        if not isinstance(model, GeneExprNarrowContextualAttentionGateTransformer):
+            raise ValueError(f"GeCohortEvaluator: {type(model).__name__} is not the gene-expression model; a survival model's "
+                             "validation is CohortEvaluator's")
+        if not isinstance(cohort, GeResidentCohort):
+            raise ValueError(f"GeCohortEvaluator: a GeResidentCohort holds the gene-expression layout, not a {type(cohort).__name__}")
+        if capture and need_paths:
+            raise ValueError("GeCohortEvaluator(capture=True): need_paths returns the pooling attention map, an output of the "
+                             "forward whose size follows the window: the captured evaluator keeps no map -- run it eagerly "
+                             "(capture=False)")
+        self.model, self.cohort, self.l1 = model, cohort, float(l1)
+        self.need_paths, self.capture = bool(need_paths), bool(capture)
+        self.ids = [int(i) for i in ids]
+        runs, perm = cut_eval_windows(self.ids, cohort.lengths, cohort.slab_index, max_window_rows, max_window_slides)
+        for i in self.ids:
+            if cohort.lengths[i] < model.MIN_WINDOW_ROWS:
+                raise ValueError(f"GeCohortEvaluator: slide {i} has {cohort.lengths[i]} rows, fewer than the {model.MIN_WINDOW_ROWS} "
+                                 "the gene-expression model's window forward needs (shorter bags go through forward())")
+        dev = cohort.device
+        n = len(self.ids)
+        self.perm_host = perm
+        self.perm = torch.tensor(perm, dtype=torch.int64).to(dev, non_blocking=True)
+        self.labels = cohort.labels.index_select(0, torch.tensor(self.ids, dtype=torch.int64).to(dev, non_blocking=True))
+        weight = model.H[0].weight
+        if weight.device != cohort.labels.device:
+            raise ValueError(f"GeCohortEvaluator: the model lies on {weight.device}, the cohort on {dev}")
+        self.windows, lo = [], 0
+        for run in runs:
+            w = _EvalWindow()
+            w.ids, w.lo, w.hi = run, lo, lo + len(run)
+            lo = w.hi
+            lengths = [cohort.lengths[i] for i in run]
+            w.bags = _slab_window(cohort.slabs[cohort.slab_index[run[0]]], cohort.row_offset[run[0]], lengths)
+            w.labels = cohort.labels.index_select(0, torch.tensor(run, dtype=torch.int64).to(dev, non_blocking=True))
+            w.omics = w.cens = w.scale = w.graph = None
+            if dev.type == "cuda":
+                w.bags.plan()                   # (its H2D copy happens here, never inside a call or a capture)
+                if ops.patch_fc_f32_supported(w.bags.data, weight):
+                    w.scale = torch.ones(1, dtype=torch.float32, device=dev)
+            self.windows.append(w)
+        # results in run order: every window writes its rows, one permutation per tensor puts them into `ids` order
+        self._loss = torch.empty(n, dtype=torch.float32, device=dev)
+        self._y = torch.empty(n, int(model.classifier.out_features), dtype=torch.float32, device=dev)
+        self.pool = pool
+        if self.capture:
+            self._capture(pool)
+
+    def _body(self, w):
+        """forward + loss of one window into the run-order buffers -> the window's pooling attentions (a list of (1, M_b))."""
+        from . import ops
+        bags = w.bags
+        if w.scale is not None:
+            bags.data._mpo_feature_scale_dev = ops.feature_scale_device(bags.data, out=w.scale)
+        try:
+            targets = (w.labels, _slide_weights(bags.n_slides, 1, w.labels.device))
+            y, att = self.model.forward_window(bags, need_maps=False, ce_targets=targets)
+        finally:
+            if w.scale is not None:
+                del bags.data._mpo_feature_scale_dev
+        self._loss[w.lo:w.hi].copy_(_with_penalty(self.model, att["loss"], self.l1).view(-1), non_blocking=True)
+        self._y[w.lo:w.hi].copy_(y, non_blocking=True)
+        return att["path"]
+
+    _capture = CohortEvaluator._capture
+
+    def __call__(self) -> GeEvalResult:
+        from . import ops
+        paths = None
+        if self.capture:
+            for w in self.windows:
+                w.graph.replay()
+        else:
+            was_training = self.model.training
+            self.model.eval()
+            try:
+                with torch.no_grad():
+                    paths = [self._body(w) for w in self.windows]
+            finally:
+                self.model.train(was_training)
+        loss = self._loss.index_select(0, self.perm)
+        y = self._y.index_select(0, self.perm)
+        pred, confusion, counts, summary = classification_metrics_device(y, self.labels, loss)
+        out = GeEvalResult(loss, y, pred, confusion, counts, summary[2:3], summary[0:1], summary[1:2])
+        if self.need_paths:
+            per_run = [p for window_paths in paths for p in window_paths]
+            out.paths = [per_run[k] for k in self.perm_host]
+            stats = [ops.map_block_stats(w.bags.split_map(torch.cat([p.reshape(-1) for p in window_paths]), 1))
+                     for w, window_paths in zip(self.windows, paths)]
+            out.path_stats = torch.cat(stats).index_select(0, self.perm)
+        return out
+
+
+def validate_ge(model, cohort: GeResidentCohort, ids, **options) -> GeEvalResult:
+    """The reference's validate() (models/ge_nacagat/main.py:85-119) over the slides `ids` of a resident gene-expression
+    cohort: a one-shot eager GeCohortEvaluator(model, cohort, ids, **options) and its call.  No host synchronisation;
+    result.accuracy_value() reads the accuracy.  An epoch loop that validates the same set every epoch keeps one
+    GeCohortEvaluator instead."""
+    if options.get("capture"):
+        raise ValueError("validate_ge: a one-shot evaluation has nothing to replay; build a GeCohortEvaluator(capture=True) and "
+                         "call it every epoch")
+    return GeCohortEvaluator(model, cohort, ids, **options)()
+
+
+def test_ge(model, cohort: GeResidentCohort, ids, save_dir=None, name: str = "ATTN"):
+    """The reference's test() (models/ge_nacagat/main.py:122-142) over the slides `ids` of a resident gene-expression cohort,
+    always eager.  Returns one dict per slide, in `ids` order: 'id', 'Y' ((C,)), 'pred' and 'label' (scalar tensors),
+    'attn_stats' ((3,) [min, max, mean] of the slide's pooling attention, ops.map_block_stats) and 'path' (the (1, M_b)
+    pooling attention), all on the device.  Without save_dir nothing is read by the host.  With save_dir every slide's path
+    is written with torch.save to save_dir/{name}_{id}.pt (a CPU tensor) and the file's path is the dict's 'file': THIS IS
+    THE ONE PLACE THAT SYNCHRONISES."""
+    import os
+    ev = GeCohortEvaluator(model, cohort, ids, need_paths=True)
+    r = ev()
+    out = []
+    for k, slide_id in enumerate(ev.ids):
+        out.append({"id": slide_id, "Y": r.Y[k], "pred": r.pred[k], "label": ev.labels[k], "attn_stats": r.path_stats[k],
+                    "path": r.paths[k]})
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
+        for slide in out:
+            slide["file"] = os.path.join(save_dir, f"{name}_{slide['id']}.pt")
+            torch.save(slide["path"].cpu(), slide["file"])
+    return out
+
+
+test_ge.__test__ = False

@@ -1156,6 +1156,23 @@ def concordance_index(censorship, time, risk):
     return c_index, counts
 
 
+def class_metrics(y, label, loss=None, want_pred: bool = True):
+    """Classification metrics on the device (csrc/class_metrics.hip; harness.classification_metrics_device is the checked
+    front): y fp32 (n, C), label int64 (n,), loss fp32 (n,) or None, contiguous on one GPU -> (pred (n,) int64 or None,
+    confusion (C, C) int64, counts (4,) int64 = valid, correct, invalid labels, rows with a NaN, summary (3,) fp64 =
+    accuracy, balanced accuracy, mean loss).  Two launches, no host sync."""
+    n, c = int(y.shape[0]), int(y.shape[1])
+    dev = y.device
+    pred = torch.empty(n, dtype=torch.int64, device=dev) if want_pred else None
+    confusion = torch.empty(c, c, dtype=torch.int64, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    summary = torch.empty(3, dtype=torch.float64, device=dev)
+    ws = _workspace(L.lib().mpo_class_metrics_workspace_bytes(n, c), dev)
+    L.call("mpo_class_metrics", L.ptr(y), L.ptr(label), L.ptr(loss), n, c, L.ptr(pred), L.ptr(confusion), L.ptr(counts),
+           L.ptr(summary), L.ptr(ws), ws.numel(), L.stream_of(y))
+    return pred, confusion, counts, summary
+
+
 class SurvivalHeadFn(torch.autograd.Function):
     """logits (B, C) -> hazards, survs, Y (models/mcat/mcat.py:130-138) on the HIP head kernels."""
 

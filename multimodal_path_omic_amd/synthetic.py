@@ -103,6 +103,29 @@ def make_cohort(n_slides: int, m_lo: int, m_hi: int, omic_sizes, seed: int, n_cl
     return slides
 
 
+def make_ge_cohort(n_slides: int, m_lo: int, m_hi: int, seed: int, n_classes: int = 3, patch_dim: int = PATCH_DIM):
+    """Seeded synthetic gene-expression cohort with a planted signal.
+
+    Returns a list of dicts with keys wsi (M, patch_dim) and gene_expr_class -- the pairs dataset/ge_dataset.py yields
+    (harness.make_ge_window's layout).  Every slide's patches are shifted along one direction in patch space by a latent
+    value; the class is the latent's quantile bin (n_classes bins of equal count, so that with n_slides >= n_classes every
+    class 0 .. n_classes - 1 has a slide) and a model can learn an accuracy above chance.
+    """
+    gen = rng(seed)
+    w_patch = gen.standard_normal(patch_dim) / np.sqrt(patch_dim)
+    slides, latent = [], []
+    for i in range(n_slides):
+        m = int(gen.integers(m_lo, m_hi + 1))
+        z = gen.standard_normal()
+        wsi = gen.standard_normal((m, patch_dim)) + 0.5 * z * w_patch[None, :] * np.sqrt(patch_dim) / 8
+        slides.append(dict(wsi=torch.from_numpy(wsi.astype(np.float32))))
+        latent.append(z)
+    edges = np.quantile(np.array(latent), np.linspace(0, 1, n_classes + 1)[1:-1])
+    for s, z in zip(slides, latent):
+        s["gene_expr_class"] = int(np.searchsorted(edges, z))
+    return slides
+
+
 def subsample(t: torch.Tensor, n: int = 4096) -> torch.Tensor:
     """Deterministic strided sample of a tensor's elements (fixtures store these, not full grads)."""
     flat = t.detach().reshape(-1)
