@@ -576,6 +576,9 @@ int mpo_coattn_bwd_bagpass(const void* bag, int bag_dtype, const int32_t* cu_row
  * (csrc/class_metrics.hip): likewise additive to ABI 14. */
 #include "mpo_classify.h"
 
+/* ---- the patch layer of an fp16-stored window (csrc/patch_fc_f16.hip): likewise additive to ABI 14. */
+#include "mpo_patch_f16.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,7 +26,7 @@ LATER_HEADER_PATHS = [os.path.join(os.path.dirname(_HERE), "include", name) for 
 # Every header registered since (the two lists above are pinned by name in the CPU suite): an open list, one accessor for
 # all of it, header_symbols().  A new companion header of mpo_hip.h goes here.
 MORE_HEADER_PATHS = [os.path.join(os.path.dirname(_HERE), "include", name) for name in ("mpo_feature_range.h", "mpo_grad_guard.h", "mpo_eval.h",
-                                                                                                  "mpo_classify.h")]
+                                                                                                  "mpo_classify.h", "mpo_patch_f16.h")]
 
 # The closed map from the header's scalar parameter types; a new scalar type in the header needs a new line here.
 _SCALARS = {"int": c_int, "int32_t": c_int, "int64_t": c_int64, "uint64_t": c_uint64, "size_t": c_size_t, "float": c_float,

@@ -310,6 +310,45 @@ int mpo_patch_fc_f32_backward(const float* d_h_bag, const float* h_bag, const fl
     return mpo_launch_patch_wgrad_f32(d_h_bag, h_bag, patches, total_rows, embed, patch_dim, gate, d_weight, d_bias, part, stream);
 }
 
+// fp16-stored window: the patch layer on patch_fc_f16.hip (the fp32 window's entries without a feature scale)
+size_t mpo_patch_fc_f16_workspace_bytes(int backward) {
+    return one_block_workspace_bytes(backward ? mpo_patch_wgrad_f16x_workspace_floats() : mpo_patch_fc_f16_workspace_floats());
+}
+// drop_256 = round(256 p) -> the p the launcher rounds back to that integer (exact: 256ths); refusals in the fp32 entry's words
+static int patch_f16_rate(int drop_256, float* p) {
+    *p = (float)drop_256 / 256.0f;
+    MPO_CHECK(drop_256 >= 0 && drop_256 <= 256, "patch-layer dropout p must be in [0,1) (got %f)", (double)*p);
+    MPO_CHECK(drop_256 <= 255, "patch-layer dropout p = %g is realised as round(256 p) / 256 = %u/256: "
+              "nothing would be kept (p must be below 1 - 1/512)", (double)*p, (unsigned)drop_256);
+    return 0;
+}
+int mpo_patch_fc_f16_forward(const void* patches, int64_t total_rows, int patch_dim, const float* patch_weight,
+                             const float* patch_bias, int embed, int drop_256, uint64_t seed, uint64_t offset,
+                             const uint64_t* rng_epoch, float* h_bag, void* workspace, size_t workspace_bytes, mpo_stream_t stream) {
+    MPO_CHECK(patches && patch_weight && patch_bias && h_bag, "fp16 patch layer: null operand");
+    float drop_p;
+    RC(patch_f16_rate(drop_256, &drop_p));
+    MPO_CHECK(total_rows >= 1, "fp16 patch layer: total_rows %lld", (long long)total_rows);
+    WsCarve ws(workspace, workspace_bytes);
+    float* wpk = ws.floats(mpo_patch_fc_f16_workspace_floats());
+    MPO_CHECK(ws.ok(), "fp16 patch layer: workspace too small (%zu bytes)", workspace_bytes);
+    return mpo_launch_patch_fc_f16(patches, patch_weight, patch_bias, h_bag, total_rows, embed, patch_dim, drop_p, seed, offset,
+                                   reinterpret_cast<const unsigned long long*>(rng_epoch), wpk, stream);
+}
+int mpo_patch_fc_f16_backward(const float* d_h_bag, const float* h_bag, const void* patches, int64_t total_rows, int embed,
+                              int patch_dim, int drop_256, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes,
+                              mpo_stream_t stream) {
+    MPO_CHECK(d_h_bag && patches && d_weight, "fp16 patch layer backward: null operand");
+    float drop_p;
+    RC(patch_f16_rate(drop_256, &drop_p));
+    const float gate = 256.0f / (256.0f - (float)drop_256);          // (the forward kernel's inv_keep; 1 at drop_256 = 0)
+    MPO_CHECK(total_rows >= 1, "fp16 patch layer backward: total_rows %lld", (long long)total_rows);
+    WsCarve ws(workspace, workspace_bytes);
+    float* part = ws.floats(mpo_patch_wgrad_f16x_workspace_floats());
+    MPO_CHECK(ws.ok(), "fp16 patch layer backward: workspace too small (%zu bytes)", workspace_bytes);
+    return mpo_launch_patch_wgrad_f16x(d_h_bag, h_bag, patches, total_rows, embed, patch_dim, gate, d_weight, d_bias, part, stream);
+}
+
 // the patch layer's bag pass alone, and with the co-attention's partial pass behind it (bench.py's roofline leg, profiling workloads)
 int mpo_patch_coattn_fwd_bagpass(const void* patches, const void* w_packed, const float* bias, const int32_t* cu_rows, int n_slides,
                                  const float* qk2, void* h_bag, float* part_ml, float* part_ctx, int n_q, int max_rows,

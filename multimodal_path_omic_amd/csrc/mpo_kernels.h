@@ -177,6 +177,15 @@ int mpo_launch_patch_fc_f32(const float* x, const float* w, const float* bias, f
                             float* ws, hipStream_t stream);
 int mpo_launch_patch_wgrad_f32(const float* dh, const float* hbag, const float* x, long long total_rows, int embed, int patch_dim,
                                float gate, float* d_weight, float* d_bias, float* ws, hipStream_t stream);
+// fp16-stored window: the patch layer as two-term fp16 products, its weight gradient as three-term bf16 products
+// (patch_fc_f16.hip); x: fp16 [total_rows][1024]; ws = the *_workspace_floats() below (the fp32 window's sizes)
+size_t mpo_patch_fc_f16_workspace_floats();
+size_t mpo_patch_wgrad_f16x_workspace_floats();
+int mpo_launch_patch_fc_f16(const void* x, const float* w, const float* bias, float* h, long long total_rows, int embed,
+                            int patch_dim, float drop_p, unsigned long long seed, unsigned long long offset,
+                            const unsigned long long* epoch, float* ws, hipStream_t stream);
+int mpo_launch_patch_wgrad_f16x(const float* dh, const float* hbag, const void* x, long long total_rows, int embed, int patch_dim,
+                                float gate, float* d_weight, float* d_bias, float* ws, hipStream_t stream);
 // K2's patch-side gradient with the product back through the key projection inside the pass (k2_patchgrad.hip)
 int mpo_launch_k2_patch_grad(const int* cu, const void* dk_bf16, const float* w_k, const float* amap, const float* dctx,
                              const void* hbag_bf16, void* out_bf16, float gate, float* part_colsum, int n_q, int embed,

@@ -57,7 +57,9 @@ def concordance_index_censored(event, time, risk, tied_tol: float = 1e-8) -> flo
 
 
 def make_window(slides: Sequence[dict], device, bag_dtype=torch.float32):
-    """List of slide dicts (synthetic.make_cohort layout) -> (BagBatch, omics per group (B,d_i), labels, censorship)."""
+    """List of slide dicts (synthetic.make_cohort layout) -> (BagBatch, omics per group (B,d_i), labels, censorship).
+    bag_dtype: the window's storage -- torch.float32 (the reference's), torch.bfloat16 (the benchmarked mode) or torch.float16
+    (the patch matrix alone in fp16, H_bag fp32: ops.patch_fc_f16)."""
     bags = BagBatch.from_list([s["wsi"].to(device=device, dtype=bag_dtype, non_blocking=True) for s in slides])
     n_groups = len(slides[0]["omics"])
     omics = [torch.stack([s["omics"][i] for s in slides]).to(device, non_blocking=True) for i in range(n_groups)]
@@ -73,7 +75,7 @@ CE_REFUSAL = ("loss 'ce' cannot train these models: the reference computes nn.Cr
 
 def make_ge_window(slides: Sequence[dict], device, bag_dtype=torch.float32):
     """List of gene-expression slide dicts ({'wsi': (M, 1024), 'gene_expr_class': int}, the pairs
-    dataset/ge_dataset.py yields) -> (BagBatch, labels (B,) int64)."""
+    dataset/ge_dataset.py yields) -> (BagBatch, labels (B,) int64).  bag_dtype: as make_window's (fp32, bf16 or fp16)."""
     bags = BagBatch.from_list([s["wsi"].to(device=device, dtype=bag_dtype, non_blocking=True) for s in slides])
     labels = torch.tensor([int(s["gene_expr_class"]) for s in slides], dtype=torch.int64).to(device, non_blocking=True)
     return bags, labels
@@ -523,7 +525,8 @@ def _cohort_slabs(cohort, who: str, slides: Sequence[dict], bag_dtype, slab_byte
 
 
 class ResidentCohort:
-    """A cohort that lives on the device once, for shuffled epochs of the sampled, captured step (bag_dtype bf16, or fp32
+    """A cohort that lives on the device once, for shuffled epochs of the sampled, captured step (bag_dtype bf16, fp16 -- bf16's
+    bytes, fp32 H_bag behind the patch layer, no feature scale: captured like a bf16 cohort -- or fp32
     for a step captured with device_feature_scale=True): every slide's rows (in
     slabs of at most `slab_bytes`, a slide never split), the pointer / length table csrc/bag_sample.hip's slide gather is addressed
     through, omics per group (N, d_i), labels, censorship and survival_months (all (N,)).  A window is a list of slide ids:
@@ -999,7 +1002,8 @@ class GeResidentCohort:
     """ResidentCohort for the gene-expression model: every slide's rows on the device once, in the same storage -- slabs of at
     most `slab_bytes`, a slide never split; `rows`, `lengths`, `slab_index`, `row_offset`, the pointer / length table
     (`table_ptrs`, `table_lens`), `cycle`, `n_slides` -- and `labels` (N,) int64 on the device.
-    slides: the dict layout make_ge_window takes ({'wsi', 'gene_expr_class'}: synthetic.make_ge_cohort)."""
+    slides: the dict layout make_ge_window takes ({'wsi', 'gene_expr_class'}: synthetic.make_ge_cohort).  bag_dtype: bf16, fp16
+    (captured like bf16: no feature scale) or fp32 (a step captured with device_feature_scale=True)."""
 
     def __init__(self, slides: Sequence[dict], device, bag_dtype=torch.bfloat16, cycle: bool = False, slab_bytes: int = 1 << 30):
         self.device, self.cycle = torch.device(device), bool(cycle)

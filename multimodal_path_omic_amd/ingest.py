@@ -94,7 +94,9 @@ class WindowFeeder:
     """Iterates over windows of `window` slides in `order`, yielding (BagBatch, omics, labels, censorship, ids).
 
     omics_of(ids) -> list of (B, d_i) CPU tensors; labels_of(ids) / cens_of(ids) -> 1-D CPU tensors.  The returned
-    BagBatch aliases a ring slot: it stays valid until `depth` further windows have been requested."""
+    BagBatch aliases a ring slot: it stays valid until `depth` further windows have been requested.
+    bag_dtype: the storage of the ring slots and of the windows they hand out -- bf16, fp16 (features written in fp16 cross
+    PCIe as they are) or fp32."""
 
     def __init__(self, store: SlideStore, order: Sequence[int], window: int, device, omics_of: Callable, labels_of: Callable,
                  cens_of: Callable, bag_dtype=torch.bfloat16, depth: int = 2, workers: int = 8, feat: int = 1024):

@@ -9,6 +9,9 @@ window of slides through the model as ONE ragged batch: slides are independent (
 cross-slide state: models/mcat/main.py:250), so per-slide results are unchanged while every launch is
 shared by the window.  `bag_dtype=torch.bfloat16` stores the patch matrix / H_bag in bf16 (a storage
 format: accumulation stays fp32, the 6 x d tail stays fp32 -- SURVEY.md section 0.7).
+`bag_dtype=torch.float16` stores the patch matrix alone in fp16 (bf16's bytes) and keeps H_bag and everything
+behind it in fp32: forward() converts a slide as it does for bf16; medium / patch_dim 1024 runs
+ops.patch_fc_f16, the other sizes an fp32 copy of the window through the fp32 GEMM (functional, not tuned).
 """
 from __future__ import annotations
 
@@ -89,7 +92,10 @@ class _FusionModelBase(nn.Module):
             h = ops.patch_fc(x, lin.weight, lin.bias, p, pre_gated_grad=self._fused_bag_gate, batch=bags)
         elif ops.patch_fc_f32_supported(x, lin.weight):
             h = ops.patch_fc_f32(x, lin.weight, lin.bias, p)        # fp32 window, 1024 -> 256: hand-written both ways
-        else:                                                       # fp32 window of the small / big models or of patch_dim 512 / 2048: the exact-fp32 MFMA GEMM (many-row form)
+        elif ops.patch_fc_f16_supported(x, lin.weight):
+            h = ops.patch_fc_f16(x, lin.weight, lin.bias, p)        # fp16 window, 1024 -> 256: two-term MFMA forward, fp32 H_bag
+        else:                                                       # fp32 window of the small / big models or of patch_dim 512 / 2048: the exact-fp32 MFMA GEMM (many-row form);
+            # an fp16 window of those geometries too, through an fp32 copy of the window: functional, not tuned
             h = F.dropout(ops.linear(x.float(), lin.weight, lin.bias, "relu"), p, self.training)
         return bags.with_data(h)
 

@@ -612,6 +612,57 @@ def patch_fc_f32(x, weight, bias, drop_p: float):
     return PatchFcF32Fn.apply(x, weight, bias, float(drop_p))
 
 
+class PatchFcF16Fn(torch.autograd.Function):
+    """H_bag = dropout_p(relu(X W_H^T + b)) for an fp16-stored window through Linear(1024, 256) (models/mcat/mcat.py:24-29,87),
+    hand-written both ways (csrc/patch_fc_f16.hip), H_bag in fp32: PatchFcF32Fn without a feature scale.  An fp16 feature is
+    one fp16 MFMA operand as stored, so the forward takes two terms W_hi X + W_lo X (fp32 accumulation; against the fp64
+    product of the stored operands only W's 2^-22 tail is lost) and the same dropout stream as the fp32 kernel: equal (seed,
+    offset, epoch) give equal masks.  Backward = the fp32 window's ONE pass (ReLU / dropout derivative read off H_bag,
+    dW_H = g^T X, db_H = colsum(g)) with X split exactly into bf16 hi + lo.  Like PatchFcF32Fn it computes dW_H inside
+    backward whatever ops.defer_patch_weight_grad says (the split exchange defers the bf16 window's patch_weight_grad only)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, drop_p: float):
+        lib = L.lib()
+        if not patch_fc_f16_supported(x, weight):
+            raise ValueError(f"fp16 patch layer: built for a contiguous fp16 window through Linear(1024, 256) (got {x.dtype} "
+                             f"{tuple(x.shape)} through a weight {tuple(weight.shape)})")
+        h = torch.empty(x.shape[0], weight.shape[0], device=x.device, dtype=torch.float32)
+        # the entries take the rate as the kernel realises it, in 256ths (one integer for both directions: mpo_patch_f16.h);
+        # ctx.gate is the keep scale the backward entry forms from it
+        ctx.drop_256 = int(round(_realised_drop(drop_p) * 256)) if drop_p > 0 else 0
+        ctx.gate = 256.0 / (256.0 - ctx.drop_256)
+        seed, off = _reserve(h.numel() // 16 + 2) if drop_p > 0 else (0, 0)
+        ws = _workspace(lib.mpo_patch_fc_f16_workspace_bytes(0), x.device)
+        L.call("mpo_patch_fc_f16_forward", L.ptr(x), x.shape[0], x.shape[1], L.ptr(weight), L.ptr(bias), weight.shape[0],
+               ctx.drop_256, seed, off, _epoch(), L.ptr(h), L.ptr(ws), ws.numel(), L.stream_of(x))
+        ctx.save_for_backward(x, h)
+        ctx.param_refs = (weight, bias)
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        lib = L.lib()
+        x, h = ctx.saved_tensors
+        dh = dh.contiguous()
+        dw, db = (grad_out(p) for p in ctx.param_refs)
+        ws = _workspace(lib.mpo_patch_fc_f16_workspace_bytes(1), x.device)
+        L.call("mpo_patch_fc_f16_backward", L.ptr(dh), L.ptr(h), L.ptr(x), x.shape[0], h.shape[1], x.shape[1], ctx.drop_256,
+               L.ptr(dw), L.ptr(db), L.ptr(ws), ws.numel(), L.stream_of(x))
+        return None, dw, db, None
+
+
+def patch_fc_f16_supported(x, weight) -> bool:
+    """mpo_patch_fc_f16_*: an fp16 window through Linear(1024, 256)."""
+    return x.dtype == torch.float16 and x.is_contiguous() and x.dim() == 2 and x.shape[1] == 1024 and tuple(weight.shape) == (256, 1024)
+
+
+def patch_fc_f16(x, weight, bias, drop_p: float):
+    """H_bag (fp32) = dropout(relu(x W^T + b)) of an fp16 window on the hand-written kernels (no library GEMM, no fp32 copy
+    of the window, no feature scale)."""
+    return PatchFcF16Fn.apply(x, weight, bias, float(drop_p))
+
+
 # ------------------------------------------------------------------------------------ row f1: patch layer + K1 in one call
 class PatchCoAttnMCATFn(torch.autograd.Function):
     """H_bag = dropout_p(relu(X W_H^T + b_H)) AND MCAT's co-attention over it (models/mcat/mcat.py:24-29,87,97) in ONE
@@ -1709,7 +1760,8 @@ class RowSampler:
     device_feature_scale=True on an fp32 sampler: it owns `scale`, a (1,) fp32 tensor, runs feature_scale_device over the
     rows it wrote after EVERY gather, eager or captured, and tags the output batch's data with it
     (_mpo_feature_scale_dev), so that the fp32 patch layer reads the sample's scale on the device -- no host read, nothing
-    baked into a graph.  On a bf16 sampler, and without the flag, `scale` is None and nothing is added."""
+    baked into a graph.  On a bf16 or fp16 sampler, and without the flag, `scale` is None and nothing is added (an fp16
+    window's patch layer, patch_fc_f16, takes no feature scale)."""
 
     RNG_SPAN = 0            # _reserve(0): one counter value
     SOURCES = {"window": (BagBatch, "mpo_bag_sample_desc_bytes", "mpo_bag_sample_rows"),
@@ -1724,9 +1776,9 @@ class RowSampler:
         n_slides, k, width = int(n_slides), int(k), int(width)
         if n_slides < 1 or k < 1:
             raise ValueError(f"RowSampler: n_slides {n_slides} and k {k} must be at least 1")
-        if dtype not in (torch.bfloat16, torch.float32):
-            raise ValueError(f"RowSampler: bag dtype must be float32 or bfloat16, got {dtype}")
-        self.elem_bytes = 2 if dtype == torch.bfloat16 else 4
+        if dtype not in (torch.bfloat16, torch.float16, torch.float32):
+            raise ValueError(f"RowSampler: bag dtype must be float32, float16 or bfloat16, got {dtype}")
+        self.elem_bytes = torch.empty(0, dtype=dtype).element_size()     # (the gather copies bytes: 2 or 4 per element)
         if (width * self.elem_bytes) % 16:
             raise ValueError(f"RowSampler: a row of {width} x {self.elem_bytes} bytes is not a multiple of 16 bytes")
         self.n_slides, self.k, self.width, self.dtype, self.static = n_slides, k, width, dtype, bool(static)

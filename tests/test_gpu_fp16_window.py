@@ -1,0 +1,366 @@
+"""An fp16-stored window (bag_dtype=torch.float16) through the models and the harness: the patch matrix alone is stored in fp16,
+H_bag and everything behind it is fp32 (ops.patch_fc_f16, csrc/patch_fc_f16.hip).  The oracle is fed the same stored values --
+X rounded to fp16, nothing else (bag_storage=torch.float16, storage_points=("x",)) -- and the models are then held to the bars
+the fp32-bag model tests use: the kernels' own arithmetic is the fp32 window's.  Against the fp32 REFERENCE's fixtures at the
+benchmarked bag length what remains is the storage floor of X itself (tests/test_fp16_window_cpu.py).
+
+Helpers and bars are taken from the files that own them (imported, not restated): the step replay and `_hold` rule of
+tests/test_gpu_train_step.py, the gather restatement of tests/test_gpu_cohort_sampling.py, the cohort of
+tests/test_gpu_validate.py."""
+import pytest
+import torch
+
+import cases as C
+import step_replay as S
+import test_gpu_cohort_sampling as CS
+import test_gpu_train_step as TS
+import test_gpu_validate as V
+from multimodal_path_omic_amd import harness, ops
+from multimodal_path_omic_amd import synthetic as syn
+from multimodal_path_omic_amd.dp import FlatAdam, FlatGradBucket
+from multimodal_path_omic_amd.harness import ces_loss
+from multimodal_path_omic_amd.models import (GeneExprNarrowContextualAttentionGateTransformer,
+                                             MultimodalCoAttentionTransformer, NarrowContextualAttentionGateTransformer)
+from multimodal_path_omic_amd.ops import BagBatch, SlideSet
+from oracle import mpo_oracle as O
+from test_gpu_models import relerr
+
+pytestmark = pytest.mark.gpu
+sub = syn.subsample
+F16 = torch.float16
+X_ONLY = dict(bag_storage=F16, storage_points=("x",))
+LENGTHS = [463, 33, 2000, 129]             # several 128-row blocks + a part; one 32-row tile + 1; many blocks; one row past a block
+CLS = {"mcat": MultimodalCoAttentionTransformer, "nacagat": NarrowContextualAttentionGateTransformer}
+
+
+def map_rel(a, ref):
+    return float(((a.detach().cpu() - ref).abs() / ref.clamp_min(1e-30)).max())
+
+
+@pytest.fixture
+def patch_routes():
+    """The calls of the two patch-layer routes an fp16 window can take inside the block: {'f16': count, 'linear': [(dtype of the
+    operand, weight) of every ops.linear call]}."""
+    calls = {"f16": 0, "linear": []}
+    f16, linear = ops.patch_fc_f16, ops.linear
+
+    def count_f16(*a, **k):
+        calls["f16"] += 1
+        return f16(*a, **k)
+
+    def count_linear(x, w, *a, **k):
+        calls["linear"].append((x.dtype, w))
+        return linear(x, w, *a, **k)
+    ops.patch_fc_f16, ops.linear = count_f16, count_linear
+    try:
+        yield calls
+    finally:
+        ops.patch_fc_f16, ops.linear = f16, linear
+
+
+def _fusion_eval_against_oracle(dev, kind, model, sd, omic_sizes, seed, lengths, patch_dim=1024):
+    """Slide by slide through forward() (fp32 features in: forward() converts them to the model's fp16 storage), the `ces` loss
+    summed over the slides -> worst errors over the slides, and the gradients of the sum."""
+    fwd = O.mcat_forward if kind == "mcat" else O.nacagat_forward
+    kw = dict(inference=True) if kind == "mcat" else {}
+    p = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    g = syn.rng(seed)
+    worst = dict(hazards=0.0, survs=0.0, Y=0.0, coattn=0.0, path=0.0, omic=0.0)
+    total_o = 0.0
+    for b, m in enumerate(lengths):
+        wsi = syn.normal(g, (m, patch_dim))
+        omics = [syn.normal(g, (s,)) for s in omic_sizes]
+        label, cens = torch.tensor([b % 4]), torch.tensor([float(b % 2)])
+        hz, sv, y, att = model(wsi=wsi.to(dev), omics=[o.to(dev) for o in omics], **kw)
+        ces_loss(hz, sv, label.to(dev), cens.to(dev)).backward()
+        hz_o, sv_o, y_o, att_o = fwd(p, wsi, omics, **X_ONLY, **kw)
+        total_o = total_o + O.ces_loss(hz_o, sv_o, label, cens)
+        for k, e in (("hazards", float((hz.detach().cpu() - hz_o).abs().max())), ("survs", float((sv.detach().cpu() - sv_o).abs().max())),
+                     ("Y", float((y.detach().cpu() - y_o).abs().max())), ("coattn", map_rel(att["coattn"], att_o["coattn"].detach())),
+                     ("path", relerr(att["path"], att_o["path"])), ("omic", relerr(att["omic"], att_o["omic"]))):
+            worst[k] = max(worst[k], e)
+    total_o.backward()
+    grads = {}
+    for n, prm in model.named_parameters():
+        ref = p[n].grad if p[n].grad is not None else torch.zeros_like(p[n])
+        grads[n] = float((prm.grad.cpu() - ref).abs().max()) / max(float(ref.abs().max()), 1e-5)
+    return worst, grads
+
+
+def _hold_fp32_bag_bars(tag, worst, grads):
+    """tests/test_gpu_models.py::test_model_matches_reference_golden's: hazards / survs / Y 1e-4, maps 1e-3, gradients 5e-3."""
+    n_worst = max(grads, key=grads.get)
+    print(f"[fp16 window] {tag}: " + " ".join(f"{k} {v:.1e}" for k, v in worst.items()) + f" worst gradient {grads[n_worst]:.1e} ({n_worst})")
+    for k in ("hazards", "survs", "Y"):
+        assert worst[k] < 1e-4, (k, worst[k])
+    for k in ("coattn", "path", "omic"):
+        assert worst[k] < 1e-3, (k, worst[k])
+    for n, e in grads.items():
+        assert e < 5e-3, (n, e)
+
+
+@pytest.mark.parametrize("kind", ["mcat", "nacagat"])
+def test_fusion_models_on_an_fp16_window_match_the_oracle_on_the_stored_values(dev, kind, patch_routes):
+    omic_sizes, seed = [64, 100, 256, 31, 8, 300], 5151
+    sd = syn.fill_state_dict(C.model_shapes(omic_sizes, kind == "nacagat"), seed)
+    model = CLS[kind](omic_sizes=omic_sizes, bag_dtype=F16)
+    model.load_state_dict(sd, strict=True)
+    model.to(dev).eval()
+    worst, grads = _fusion_eval_against_oracle(dev, kind, model, sd, omic_sizes, seed + 1, LENGTHS)
+    # the hand-written route, not the fp32 copy
+    assert patch_routes["f16"] == len(LENGTHS) and not any(w is model.H[0].weight for _, w in patch_routes["linear"])
+    _hold_fp32_bag_bars(f"{kind} medium", worst, grads)
+
+
+def test_gene_expression_model_on_an_fp16_window_matches_the_oracle_on_the_stored_values(dev, patch_routes):
+    """The bars of tests/test_gpu_bag_selfattn.py's fp32-bag model test.  (The oracle's gene-expression forward has no
+    storage_points argument: it is handed X as fp16 stores it, which is the same thing.)"""
+    seed = 5252
+    sd = syn.fill_state_dict(C.ge_model_shapes(), seed)
+    model = GeneExprNarrowContextualAttentionGateTransformer(bag_dtype=F16)
+    model.load_state_dict(sd, strict=True)
+    model.to(dev).eval()
+    p = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    total_o = 0.0
+    for b, m in enumerate(LENGTHS):
+        wsi, target = C.ge_model_inputs(m, seed + 1 + b)
+        y, att = model(wsi=wsi.to(dev))
+        torch.nn.functional.cross_entropy(y.unsqueeze(0), target.to(dev)).backward()
+        y_o, att_o = O.ge_nacagat_forward(p, wsi.half().float())
+        total_o = total_o + O.ge_ce_loss(y_o, target)
+        e_y, e_a = float((y.detach().cpu() - y_o).abs().max()), map_rel(att["attn"], att_o["attn"].detach())
+        e_p = relerr(att["path"], att_o["path"])
+        print(f"[fp16 window] ge_nacagat M {m}: Y {e_y:.1e} self-attention map rel {e_a:.1e} path map {e_p:.1e}")
+        assert e_y < 1e-4 and e_a < 1e-3 and e_p < 1e-3, (m, e_y, e_a, e_p)
+    assert patch_routes["f16"] == len(LENGTHS) and not any(w is model.H[0].weight for _, w in patch_routes["linear"])
+    total_o.backward()
+    for n, prm in model.named_parameters():
+        ref = p[n].grad
+        e = float((prm.grad.cpu() - ref).abs().max()) / max(float(ref.abs().max()), 1e-5)
+        assert e < 5e-3, (n, e)
+
+
+@pytest.mark.parametrize("what", ["small", "patch_dim_512"])
+def test_other_geometries_run_on_the_fallback_at_the_fp32_bars(dev, what, patch_routes):
+    """model_size='small' (1024 -> 128) and patch_dim=512 (512 -> 256) on an fp16 window: an fp32 copy of the window through
+    the fp32 GEMM -- functional, not tuned -- and the same bars."""
+    omic_sizes, seed = [64] * 6, 5353
+    d, k = (128, 1024) if what == "small" else (256, 512)
+    model = MultimodalCoAttentionTransformer(omic_sizes=omic_sizes, bag_dtype=F16, patch_dim=k,
+                                             model_size="small" if what == "small" else "medium")
+    shapes = {n: tuple(v.shape) for n, v in model.state_dict().items()}        # (as tests/test_gpu_models.py builds its small model)
+    assert shapes["H.0.weight"] == (d, k)
+    sd = syn.fill_state_dict(shapes, seed)
+    model.load_state_dict(sd, strict=True)
+    model.to(dev).eval()
+    lengths = [463, 33]
+    worst, grads = _fusion_eval_against_oracle(dev, "mcat", model, sd, omic_sizes, seed + 1, lengths, patch_dim=k)
+    through_gemm = [dt for dt, w in patch_routes["linear"] if w is model.H[0].weight]
+    assert patch_routes["f16"] == 0 and through_gemm == [torch.float32] * len(lengths)
+    _hold_fp32_bag_bars(f"mcat {what} (fallback)", worst, grads)
+
+
+@pytest.mark.parametrize("case", ["mcat_m15000", "nacagat_m15000"])
+def test_fp16_window_against_the_fp32_references_fixtures(dev, golden, case):
+    """The benchmarked bag length against the fp32 REFERENCE's own outputs, the measure of tools/cpu_storage_floor.py
+    (subsampled map, element-by-element relative error).  MCAT: the project's parity number, 1e-3 (CPU floor of fp16 at X alone:
+    4.5e-4).  NaCAGaT: DESIGN section 4's rule for a storage floor -- at most 1.25 x what the oracle makes of the same stored
+    values (4.3e-3: the narrow gate multiplies the logit error; the benchmarked bf16 mode sits at 5.1e-2)."""
+    g = golden("models")
+    kind, m, omic_sizes, seed = C.MODEL_CASES[case]
+    sd = syn.fill_state_dict(C.model_shapes(omic_sizes, kind == "nacagat"), seed)
+    model = CLS[kind](omic_sizes=omic_sizes, bag_dtype=F16)
+    model.load_state_dict(sd, strict=True)
+    model.to(dev).eval()
+    wsi, omics, _, _ = C.model_inputs(m, omic_sizes, seed + 1)
+    kw = dict(inference=True) if kind == "mcat" else {}
+    with torch.no_grad():
+        hz, sv, y, att = model(wsi=wsi.to(dev), omics=[o.to(dev) for o in omics], **kw)
+        fwd = O.mcat_forward if kind == "mcat" else O.nacagat_forward
+        _, _, _, att_s = fwd(sd, wsi, omics, **X_ONLY, **kw)
+    ga = g[f"{case}/A_coattn_sub"]
+    e_a, floor = map_rel(sub(att["coattn"]), ga), map_rel(sub(att_s["coattn"]), ga)
+    e_h = float((hz.cpu() - g[f"{case}/hazards"]).abs().max())
+    print(f"[fp16 window vs fp32 reference] {case}: coattn map rel {e_a:.2e} (oracle on the same stored values {floor:.2e}), hazards {e_h:.1e}")
+    assert e_h <= 1e-4, e_h
+    if kind == "mcat":
+        assert e_a <= 1e-3, (e_a, floor)
+    else:
+        assert e_a <= 1.25 * floor, (e_a, floor)
+
+
+# ------------------------------------------------------------------------------------------- the training step
+def _oracle_fp16(kind, run):
+    """tests/test_gpu_train_step.py::_oracle with X as fp16 stores it: the fp64 step slide by slide under the run's own masks."""
+    p = {k: v.double().requires_grad_(True) for k, v in run["sd"].items()}
+    out = dict(loss=[], risk=[], hazards=[], path=[], omic=[])
+    total, row = 0.0, 0
+    for b, s in enumerate(TS._slides()):
+        m = s["wsi"].shape[0]
+        kw = S.slide_keeps(run["host"], b)
+        kw["keep_h"] = run["keep_h"][row:row + m]
+        if kind == "nacagat":
+            kw["keep_map"] = run["keep_maps"][b]
+        fwd = O.mcat_forward if kind == "mcat" else O.nacagat_forward
+        hz, sv, _, att = fwd(p, s["wsi"], s["omics"], drop_p=run["p"], **X_ONLY, **kw)
+        loss = O.ces_loss(hz, sv, torch.tensor([s["survival_class"]]), torch.tensor([float(s["censorship"])]))
+        total = total + loss / TS.ACC
+        for k, v in (("loss", loss.reshape(())), ("risk", O.risk_score(sv)[0]), ("hazards", hz[0]), ("path", att["path"]),
+                     ("omic", att["omic"])):
+            out[k].append(v.detach())
+        row += m
+    total.backward()
+    out = {k: torch.stack(v) for k, v in out.items()}
+    out["grads"] = {n: (p[n].grad if p[n].grad is not None else torch.zeros_like(p[n])) for n in p}
+    return out
+
+
+@pytest.mark.parametrize("kind", ["mcat", "nacagat"])
+def test_eager_training_step_on_an_fp16_window_equals_fp64_oracle(dev, kind):
+    """The whole eager step, every dropout site live, against fp64 under the step's own masks (tests/step_replay.py), held to
+    the fp32 row of tests/test_gpu_train_step.py::_bars.  The control: the patch layer's mask of the next epoch must miss."""
+    with TS._generator_restored():
+        run = TS._eager_run(dev, kind, F16, 2)
+        assert not S.ranges_overlap(run["records"])
+        errs = TS._compare(run, _oracle_fp16(kind, run), torch.float32)
+        print(f"[train step] {kind} fp16 window, epoch tensor = 2: {TS._line(errs)}")
+        for k, v in errs.items():
+            assert v[0] < v[1], (k, v)
+        nxt = TS._eager_run(dev, kind, F16, 3)
+        wrong = TS._compare(run, _oracle_fp16(kind, dict(run, keep_h=nxt["keep_h"])), torch.float32)
+        assert TS._factor(wrong) > 1.0, wrong
+
+
+# ------------------------------------------------------------------------------------------- the gather
+@pytest.mark.parametrize("k", [31, 32])
+@pytest.mark.parametrize("source", ["window", "slides", "slides lapped"])
+def test_fp16_gather_equals_indexing_bit_for_bit(dev, source, k):
+    """The gather copies bytes: an fp16 row of 1024 is a bf16 row's 2 KiB.  Slides of 1, 33, 700 and 4097 rows (one shorter than
+    k, passed whole or lapped); with k = 31 a slide boundary falls inside one wave's rows."""
+    ops.set_rng_epoch(None)
+    width, lengths = 1024, [1, 33, 700, 4097]
+    slides = CS.separate_slides(lengths, width, F16, dev, 21)
+    lapped = source == "slides lapped"
+    if source == "window":
+        window = BagBatch.from_list(slides)
+        rows = list(window.data.split(lengths))
+    else:
+        table = SlideSet.slide_table(slides)
+        window = SlideSet(slides, lengths, table[0], table[1], CS.int32([0, 1, 2, 3], dev), lapped)
+        rows = slides
+    s = ops.RowSampler.for_window(window, k, static=False)
+    assert s.dtype == F16 and s.elem_bytes == 2 and s.scale is None and s.source == ("window" if source == "window" else "slides")
+    s.bind(window)
+    s.out.fill_(float("nan"))
+    out = s()
+    assert out.data.dtype == F16 and out.lengths == ([k] * 4 if lapped else [min(k, m) for m in lengths])
+    assert CS.same_bits(out.data, CS.expected_rows(rows, s.last_stream, k, 0, lapped))
+    assert bool(torch.isnan(s.out[out.total_rows:]).all())
+    first_stream, first = s.last_stream, out.data.clone()
+    again = s().data                                           # a second call takes the next counter: another draw
+    assert s.last_stream != first_stream and CS.same_bits(again, CS.expected_rows(rows, s.last_stream, k, 0, lapped))
+    assert not CS.same_bits(again, first)
+
+
+# ------------------------------------------------------------------------------------------- a resident fp16 cohort
+def test_train_epoch_on_an_fp16_cohort_equals_the_eager_twin(dev):
+    """harness.train_epoch over a ResidentCohort stored in fp16, Adam inside the graph, dropout on, the row sampler in front
+    -- captured WITHOUT device_feature_scale: an fp16 window has no feature scale, GraphedWindowStep._sampling_refusal lets it
+    through as it does a bf16 one.  Two windows of four slides; the twin steps eagerly on the rows the replays drew (restated
+    on the host, tests/row_sampling_replay.py) at the replays' offsets and epochs.  tests/test_gpu_train_step.py's `_hold`
+    rule: bit-identical where two eager runs are, within twice their difference elsewhere.  The epoch loop runs under
+    torch.cuda.set_sync_debug_mode("error")."""
+    k, B = 32, TS.B
+    with TS._generator_restored():
+        slides = syn.make_cohort(8, 200, 700, TS.SIZES, 56)
+        slides[5]["wsi"] = slides[5]["wsi"][:20]                # lapped
+        cohort = harness.ResidentCohort(slides, dev, bag_dtype=F16, cycle=True)
+        assert cohort.rows[0].dtype == F16
+        first = [0, 1, 2, 3]
+
+        def adam(bucket):
+            return FlatAdam(bucket, lr=1e-3, weight_decay=1e-5)
+        step, model, bucket, captured = TS._capture(dev, "mcat", F16, CS.window_of(cohort, first), extra={"sampler": 0}, rows=B * k,
+                                                    sample_rows=k, opt=adam)
+        assert step.sampler.dtype == F16 and step.sampler.scale is None and not step.device_feature_scale
+        assert captured[0] == (0, step.rng_base)
+        after_sampler, stream = captured[1][1], step.sampler.last_stream
+        order = [6, 5, 0, 3, 7, 1, 4, 2]
+        probe = torch.ones(1, device=dev)
+        torch.cuda.synchronize()
+        torch.cuda.set_sync_debug_mode("error")
+        try:
+            with pytest.raises(RuntimeError):
+                int(probe)                                       # the mode is honoured
+            loss, risk, ids_run, leftover = harness.train_epoch(step, cohort, order)
+        finally:
+            torch.cuda.set_sync_debug_mode("default")
+        torch.cuda.synchronize()
+        assert leftover == [] and ids_run.tolist() == order and int(step.opt.t_dev) == 2 and int(step.epoch) == 2
+        got = TS._snapshot(model, bucket, step.loss, step.risk, step.opt)
+        got["epoch_loss"], got["epoch_risk"] = loss.clone(), risk.clone()
+        runs = []
+        for _ in range(2):
+            twin, _ = TS._build(dev, "mcat", F16)
+            twin_bucket = FlatGradBucket(list(twin.parameters()))
+            opt = adam(twin_bucket)
+            losses, risks = [], []
+            for e, ids in ((1, order[:4]), (2, order[4:])):
+                sample = CS.expected_rows([cohort.rows[i] for i in ids], stream, k, e, True)
+                fresh = CS.window_of(cohort, ids)
+                snap = TS._twin_step(dev, twin, twin_bucket, (BagBatch.from_lengths(sample, [k] * B), *fresh[1:]), after_sampler, e, opt)
+                losses.append(snap["loss"].view(-1))
+                risks.append(snap["risk"].view(-1))
+            snap["epoch_loss"], snap["epoch_risk"] = torch.cat(losses), torch.cat(risks)
+            runs.append(snap)
+        bad, noise, rel = TS._misses(runs[0], runs[1], got)
+        print(f"[fp16 cohort epoch] eager to eager max |diff| {noise:.1e}; graph against twin max rel {rel:.1e}, {len(bad)} tensors miss")
+        assert not bad, bad[:8]
+        assert float(got["exp_avg_sq"].max()) > 0
+
+
+def _eval_model(kind, dev):
+    model = CLS[kind](omic_sizes=V.OMIC_SIZES, bag_dtype=F16)
+    model.load_state_dict(V.state_dict(kind))
+    return model.to(dev).eval()
+
+
+def _fp16_cohort(dev):
+    return V.cached(("cohort", "f16"), lambda: harness.ResidentCohort(V.slides_once(), dev, bag_dtype=F16, slab_bytes=V.SLAB_ROWS * 2048))
+
+
+@pytest.mark.parametrize("kind", ["mcat", "nacagat"])
+def test_cohort_evaluator_on_an_fp16_cohort(dev, kind):
+    """Eager and captured against the model's own forward(), slide by slide, at tests/test_gpu_validate.py's fp32-bag bar
+    (H_bag is fp32 here); captured against eager bit for bit; no host synchronisation in either."""
+    model, cohort = _eval_model(kind, dev), _fp16_cohort(dev)
+    ids = V.IDS["across_a_slab_boundary"] + [13, 7, 0]
+    slides = V.slides_once()
+    kw = dict(inference=True) if kind == "mcat" else {}
+    rows = []
+    with torch.no_grad():
+        for i in ids:
+            hz, sv, y, _ = model(wsi=slides[i]["wsi"].to(dev), omics=[o.to(dev) for o in slides[i]["omics"]], **kw)
+            rows.append((hz[0], sv[0], y[0]))
+    ref = {k: torch.stack([r[j] for r in rows]).cpu() for j, k in enumerate(("hazards", "survs", "Y"))}
+    eager_ev = harness.CohortEvaluator(model, cohort, ids)
+    captured_ev = harness.CohortEvaluator(model, cohort, ids, capture=True)
+    eager, captured = eager_ev(), captured_ev()
+    V.assert_same_result(eager, captured)
+    figures = {k: V.worst(getattr(eager, k), ref[k]) for k in ref}
+    figures["risk"] = V.worst(eager.risk, -ref["survs"].sum(1))
+    print(f"[validate {kind} fp16 cohort] " + ", ".join(f"{k} {v:.2e}" for k, v in figures.items()))
+    for k, v in figures.items():
+        assert v < V.BAR["f32"], (k, v)
+    probe = torch.ones(1, device=dev)
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        with pytest.raises(RuntimeError):
+            int(probe)
+        again = (eager_ev(), captured_ev())
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    torch.cuda.synchronize()
+    for r in again:
+        V.assert_same_result(r, eager)
