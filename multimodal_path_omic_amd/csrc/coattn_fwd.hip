@@ -314,13 +314,19 @@ void coattn_combine_kernel(const float* __restrict__ part_ml, const float* __res
     }
     *reinterpret_cast<f32x4*>(&accs[sg][4 * dg]) = a;
     __syncthreads();
+    int bad = 0;
     for (int d = tid; d < E_; d += 256) {
         float t = 0.f;
 #pragma unroll
         for (int g = 0; g < NSG; ++g) t += accs[g][d];
-        ctx[((size_t)b * n_q + q) * E_ + d] = t / lt;
+        t /= lt;
+        ctx[((size_t)b * n_q + q) * E_ + d] = t;
+        bad |= !(fabsf(t) < INFINITY);
     }
-    if (tid == 0) lse2[(size_t)b * n_q + q] = mt + __builtin_amdgcn_logf(lt);
+    // A non-finite bag element can leave this query's scores at -inf (weight 0, a finite map row) where torch, which forms
+    // K = H W_k^T first, has NaN scores; the context has met it either way (0 x inf): the map row follows the context.
+    bad = __syncthreads_or(bad);
+    if (tid == 0) lse2[(size_t)b * n_q + q] = bad ? NAN : mt + __builtin_amdgcn_logf(lt);
 }
 
 // A[n][m] = 2^(S2[n][m] - lse2[n]) in place over the ragged [n_q][M_b] blocks; optional

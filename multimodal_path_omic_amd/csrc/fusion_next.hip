@@ -277,7 +277,7 @@ bilinear_kron_fc1_fwd_kernel(const float* __restrict__ o, const float* __restric
         for (int e = lane; e < kBilKron; e += 64) acc = fmaf(W1[(size_t)m * kBilKron + e], kr[e], acc);
         acc = wave_sum(acc);
         if (lane == 0) {
-            float u = fmaxf(acc + b1[m], 0.f);
+            float u = relu_keep_nan(acc + b1[m]);
             if (D.p > 0.f) u *= dropout_keep(D.seed, base + 3 * D.stride, (unsigned long long)b * kBilM + m, D.p, inv_keep);
             cat[(size_t)b * kBilCat + m] = u;
         }
@@ -301,7 +301,9 @@ bilinear_kron_fc1_bwd_rows_kernel(const float* __restrict__ o, const float* __re
     const unsigned long long base = epoch_offset(D.off, D.epoch);
     if (threadIdx.x < kBilM) {
         const int m = threadIdx.x;
-        const float v = cat[(size_t)b * kBilCat + m] > 0.f ? dcat[(size_t)b * kBilCat + m] * inv_keep : 0.f;
+        // (a NaN activation gives a NaN gradient: db1 has no activation factor that would carry the slide's NaN otherwise)
+        const float c = cat[(size_t)b * kBilCat + m];
+        const float v = c > 0.f ? dcat[(size_t)b * kBilCat + m] * inv_keep : (c == c ? 0.f : c);
         du[m] = v;
         dupre[(size_t)b * kBilM + m] = v;
     }

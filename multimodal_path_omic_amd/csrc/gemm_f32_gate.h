@@ -8,7 +8,7 @@ namespace {
 
 __device__ __forceinline__ float apply_act(float v, int act) {
     switch (act) {
-        case MPO_ACT_RELU: return fmaxf(v, 0.f);
+        case MPO_ACT_RELU: return relu_keep_nan(v);
         case MPO_ACT_ELU: return v > 0.f ? v : expm1f(v);
         case MPO_ACT_TANH: return tanhf(v);
         case MPO_ACT_SIGMOID: return 1.0f / (1.0f + __expf(-v));

@@ -40,6 +40,11 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
     for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
     return v;
 }
+// max(v, 0) and max(v, lo) that keep a NaN, as torch.relu and torch.clamp(min=lo) do (fmaxf returns the other operand: a
+// corrupt slide would come out as an ordinary number).  On every other operand they return what fmaxf returns, up to the
+// sign of a zero.  relu_keep_nan is one v_maximum3_f32, the patch-layer kernels' epilogue form.
+__device__ __forceinline__ float relu_keep_nan(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+__device__ __forceinline__ float clamp_min_keep_nan(float v, float lo) { return v < lo ? lo : v; }
 // The power of two that puts max |v| into [2^14, 2^15) (1 for an all-zero or non-finite maximum): the scale the fp16 operand
 // splits of patch_fc_f32.hip take for W_H and for X (feature_range.hip).
 __device__ __forceinline__ float range_scale(float vmax) {

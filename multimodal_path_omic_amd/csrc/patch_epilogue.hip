@@ -28,7 +28,7 @@ __global__ void bias_relu_dropout_bf16_kernel(bf16x8* __restrict__ h, const floa
         const uint32_t rw[4] = {r0.x, r0.y, r0.z, r0.w};
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            float x = fmaxf((float)v[j] + bv[j], 0.f);
+            float x = relu_keep_nan((float)v[j] + bv[j]);
             if (drop_p > 0.f) x = (((rw[j >> 1] >> (16 * (j & 1))) & 0xFFFFu) >= thr) ? x * inv_keep : 0.f;
             v[j] = (__bf16)x;
         }

@@ -626,7 +626,7 @@ __global__ void head_bwd_kernel(const float* __restrict__ hazards, const float* 
         if (dsv) tail += dsv[o + i] * survs[o + i];
         const float hz = hazards[o + i];
         float dh = dhz ? dhz[o + i] : 0.f;
-        dh -= tail / fmaxf(1.0f - hz, 1e-30f);
+        dh -= tail / clamp_min_keep_nan(1.0f - hz, 1e-30f);
         dl[i] = dh * hz * (1.0f - hz) + (dy ? y[o + i] * (dy[o + i] - ydot) : 0.f);
     }
     for (int i = 0; i < C; ++i) dlogits[o + i] = dl[i];
@@ -645,8 +645,8 @@ __global__ void ces_loss_fwd_kernel(const float* __restrict__ hazards, const flo
     const int y = (int)label[b];
     const float c = cens[b];
     const float s_prev = y == 0 ? 1.0f : survs[o + y - 1];
-    const float reg = -(1.0f - c) * (logf(fmaxf(s_prev, eps)) + logf(fmaxf(hazards[o + y], eps)));
-    const float sy = fmaxf(survs[o + y], eps);
+    const float reg = -(1.0f - c) * (logf(clamp_min_keep_nan(s_prev, eps)) + logf(clamp_min_keep_nan(hazards[o + y], eps)));
+    const float sy = clamp_min_keep_nan(survs[o + y], eps);
     const float ce = -(c * logf(sy) + (1.0f - c) * logf(1.0f - sy));
     loss[b] = (1.0f - alpha) * ce + alpha * reg;
     if (risk) {
@@ -704,8 +704,8 @@ __global__ void head_loss_kernel(const float* __restrict__ logits, const long lo
     const int yb = (int)label[b];
     const float c = cens[b];
     const float s_prev = yb == 0 ? 1.0f : sv[yb - 1];
-    const float reg = -(1.0f - c) * (logf(fmaxf(s_prev, eps)) + logf(fmaxf(hz[yb], eps)));
-    const float sy = fmaxf(sv[yb], eps);
+    const float reg = -(1.0f - c) * (logf(clamp_min_keep_nan(s_prev, eps)) + logf(clamp_min_keep_nan(hz[yb], eps)));
+    const float sy = clamp_min_keep_nan(sv[yb], eps);
     const float ce = -(c * logf(sy) + (1.0f - c) * logf(1.0f - sy));
     loss[b] = (1.0f - alpha) * ce + alpha * reg;
     if (risk) risk[b] = r;
@@ -721,7 +721,7 @@ __global__ void head_loss_kernel(const float* __restrict__ logits, const long lo
         }
         if (i == yb - 1 && sv[i] >= eps) dsv += -alpha * (1.0f - c) * g / sv[i];
         tail += dsv * sv[i];
-        dh -= tail / fmaxf(1.0f - hz[i], 1e-30f);
+        dh -= tail / clamp_min_keep_nan(1.0f - hz[i], 1e-30f);
         dl[i] = dh * hz[i] * (1.0f - hz[i]);
     }
     for (int i = 0; i < C; ++i) dlogits[o + i] = dl[i];

@@ -18,6 +18,8 @@ GRAD_TOL_PEAKY = 6e-3
 GRAD_TOL_PEAKY_BF16 = 1e-2
 GRAD_TOL_BF16_BAG = 7e-3
 GRAD_TOL_BF16_PARAM = 5e-3
+# check_nacagat_forward_backward's other bars: the output, the map (element by element, relative), gradients on an fp32 bag
+OUT_TOL, MAP_REL_TOL, GRAD_TOL = 2e-4, 1e-3, 2e-3
 sub = syn.subsample
 
 
@@ -84,13 +86,13 @@ def check_nacagat_forward_backward(dev, golden, case, dtype, to_dev=None):
     assert a.shape == (C.N_OMIC, m)
     f32 = dtype == torch.float32
     peaky = "peaky" in case
-    assert relerr(out, out_o) < (1e-3 if peaky else 2e-4), relerr(out, out_o)
+    assert relerr(out, out_o) < (1e-3 if peaky else OUT_TOL), relerr(out, out_o)
     rel_a = ((a.detach().cpu() - a_o.detach()).abs() / a_o.detach().clamp_min(1e-30)).max().item()
     # both score products run on the fp32-input MFMA (bag_rowdot_gated_exact) and a bf16 bag reaches K through the
     # three-term key projection (fp32-exact weights): the map holds the north-star 1e-3 on the deliberately peaky
     # fixture in both storage modes (measured r02: 2.3e-4 fp32 bag, 5.4e-4 bf16 bag)
     print(f"[K2 map] {case} {dtype}: rel_a {rel_a:.3e}")
-    assert rel_a < 1e-3, rel_a
+    assert rel_a < MAP_REL_TOL, rel_a
     torch.testing.assert_close(a.sum(1).cpu(), torch.ones(C.N_OMIC), rtol=1e-4, atol=1e-4)
     params = dict(mod.named_parameters())
     tensors = [qd, bd] + [params[k[len("co_attention."):]] for k in p]
@@ -98,7 +100,7 @@ def check_nacagat_forward_backward(dev, golden, case, dtype, to_dev=None):
     gs = torch.autograd.grad((out * p_out.to(dev)).sum() + (a * p_a.to(dev)).sum(), tensors)
     worst = {}
     for n, gr in zip(names, gs):
-        tol = GRAD_TOL_PEAKY if peaky else 2e-3
+        tol = GRAD_TOL_PEAKY if peaky else GRAD_TOL
         if not f32:
             # bf16 bag: d_bag is emitted in bf16 and the key-projection gradients (dW_k, dH += dK W_k) run
             # through bf16 operands with fp32 accumulation

@@ -21,6 +21,9 @@ sub = syn.subsample
 # The bars tests/test_gpu_sct_loss.py holds the fp32 `sct` entries to against fp64 (restated, not imported): loss and Y are
 # softmax / log of O(1) values, a few ulps relative; gradient entries are O(w) with a few fp32 roundings.
 LOSS_RTOL, GRAD_ATOL = 1e-5, 1e-6
+# loss and Y of a whole model on an fp32 window (test_forward_window_with_targets_matches_reference_golden below); Y on a bf16 window
+# against the oracle fed the same stored values (tests/test_gpu_bag_selfattn.py::test_ge_model_bf16_bag_against_the_oracle)
+GOLDEN_ABS, BF16_SAME_STORAGE_ABS = 1e-4, 2e-4
 # tests/test_gpu_graph.py: replayed against eager steps
 GRAPH_LOSS_TOL, GRAPH_PARAM_TOL = dict(rtol=2e-3, atol=2e-4), dict(rtol=5e-3, atol=5e-4)
 # tests/test_gpu_train_options.py: the first window (no optimiser step yet) and a trajectory behind Adam steps.  That file
@@ -120,7 +123,7 @@ def test_forward_window_with_targets_matches_reference_golden(dev, golden, case)
     e_loss = abs(att["loss"].item() - float(g[f"{case}/loss"]))
     e_y = float((y[0].detach().cpu() - g[f"{case}/Y"]).abs().max())
     print(f"[ge golden {case}] |loss - ref| {e_loss:.1e}, |Y - ref| {e_y:.1e}")
-    assert e_loss < 1e-4 and e_y < 1e-4
+    assert e_loss < GOLDEN_ABS and e_y < GOLDEN_ABS
     att["loss"].backward(w)
     for n, prm in model.named_parameters():
         ref = g[f"{case}/grad/{n}"]

@@ -11,6 +11,7 @@ from multimodal_path_omic_amd import _lib as L
 
 pytestmark = pytest.mark.gpu
 WIDTHS = [8 * d for d in (1, 2, 4, 8, 16, 32, 64, 128, 256)]       # 8 * every divisor of 256
+COLSUM_REL = 1e-6                                                    # fp32 column sums against fp64, relative to sum |x|
 PAD = 8                                                              # NaN rows either side (keeps 16-byte alignment)
 
 
@@ -42,7 +43,7 @@ def test_colsum_bf16_matches_fp64(dev, cols, edge):
     # fp32 partial sums (a thread's rows, a workgroup's 256 lanes, fp32 atomics across workgroups): rounding errors of
     # ~1e-8 of sum |x| with random signs; one row lost or counted twice moves a column by ~1 / rows of it
     err = float(((out.double() - ref).abs() / scale.clamp_min(1e-30)).max())
-    assert err < 1e-6, err
+    assert err < COLSUM_REL, err
     # integer-valued entries: every partial sum is exact in fp32 (|sum| < 2^24), so the result must be too
     x.copy_(torch.randint(-8, 9, (rows, cols), device=dev, generator=gen).to(torch.bfloat16))
     _colsum(x, out)
@@ -107,7 +108,7 @@ def test_epilogue_dropout_rate_scale_and_backward_mask(dev):
     ref_g = torch.where(kept, (dy.float() * scale.to(dev)).bfloat16(), torch.zeros_like(dy))
     assert torch.equal(g, ref_g)
     ref_b = g.double().sum(0)
-    assert float(((d_bias.double() - ref_b).abs() / g.double().abs().sum(0)).max()) < 1e-6
+    assert float(((d_bias.double() - ref_b).abs() / g.double().abs().sum(0)).max()) < COLSUM_REL
     g0 = torch.empty_like(dy)
     _epilogue_backward(h, dy, g0, p)                                   # without the column sums
     assert torch.equal(g0, g)

@@ -184,6 +184,7 @@ def test_gated_pool_refuses_interleaved_output_off_the_4_grid(dev):
 # ---------------------------------------------------------------------------------------------------------------- head, losses
 EPS = 1e-7
 HEAD_ABS = 1e-5                                   # hazards, survs, Y (test_fusion_head_matches_golden)
+RISK = dict(rtol=1e-6, atol=1e-6)                 # risk = -sum_j survs_j of the given survs
 CES_LOSS, CES_GRAD = dict(rtol=1e-5, atol=1e-6), dict(rtol=1e-5, atol=1e-7)            # test_ces_loss_kernel_matches_...
 SCT_LOSS, SCT_GRAD = dict(rtol=1e-5, atol=1e-6), dict(rtol=0, atol=1e-6)               # test_standalone_sct_matches_fp64
 FUSED_LOSS, FUSED_GRAD = dict(rtol=1e-4, atol=1e-4), dict(rtol=0, atol=1e-6)           # test_fused_sct_head_matches_fp64
@@ -269,7 +270,7 @@ def test_ces_loss_edges(dev, b, c):
             print(f"[tail edges] ces B={b} C={c}: loss {worst(per_d, per_o):.1e} risk {worst(risk, -sv.double().sum(1)):.1e} "
                   f"d_hazards {worst(hz_d.grad, hz_o.grad):.1e} d_survs {worst(sv_d.grad, sv_o.grad):.1e}")
             torch.testing.assert_close(per_d.double().cpu(), per_o.detach(), **CES_LOSS)
-            torch.testing.assert_close(risk.double().cpu(), -sv.double().sum(1), rtol=1e-6, atol=1e-6)
+            torch.testing.assert_close(risk.double().cpu(), -sv.double().sum(1), **RISK)
             torch.testing.assert_close(hz_d.grad.double().cpu(), hz_o.grad, **CES_GRAD)
             torch.testing.assert_close(sv_d.grad.double().cpu(), sv_o.grad, **CES_GRAD)
 
