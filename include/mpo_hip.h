@@ -94,8 +94,10 @@ int mpo_coattn_mcat_forward(const void* bag, int bag_dtype, const int32_t* cu_ro
  * scores / online softmax / context, and mpo_coattn_mcat_backward takes `saved` and h_bag exactly as after
  * mpo_coattn_mcat_forward.
  *   patches [total_rows, patch_dim] bf16;  patch_weight [embed, patch_dim] fp32 (rounded to bf16 operands inside),
- *   patch_bias [embed] fp32.  Built for patch_dim 1024, embed 256 ('medium'), n_q <= 8: the one-call form stays at the
- *   reference's geometry; other feature widths go through mpo_patch_fc_forward + mpo_coattn_mcat_forward.
+ *   patch_bias [embed] fp32.  Built for patch_dim 1024, embed 256 ('medium'); any other width is refused: the one-call form
+ *   stays at the reference's geometry, other feature widths go through mpo_patch_fc_forward + mpo_coattn_mcat_forward.
+ *   n_q 1..16 as in mpo_coattn_mcat_forward (the co-attention half IS that entry's launch sequence; the Python host sends
+ *   windows of at most 8 queries here, the range of the two-wave backward -- that is its choice, not a limit of this entry).
  * Dropout: counter hash of (seed, offset [+ *rng_epoch << 40]), one draw per 16 elements, 8 random bits each: the realised drop
  * probability is round(256 p) / 256 (exact for the reference's 0.25) and the keep scale follows it; reserve
  * total_rows * embed / 16 + 1 counters. */
