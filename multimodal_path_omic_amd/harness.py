@@ -4,6 +4,7 @@ gradient accumulation over `grad_acc_step` slides, Harrell's C-index.  No per-sl
 (the reference's loss.item() at main.py:49 is exactly what this harness must not do)."""
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import List, Sequence
 
@@ -643,6 +644,122 @@ def concordance_index_device(censorship, time, risk):
     return ops.concordance_index(censorship.detach().reshape(-1).to(torch.float32).contiguous(),
                                  time.detach().reshape(-1).to(torch.float64).contiguous(),
                                  risk.detach().reshape(-1).to(torch.float32).contiguous())
+
+
+@dataclass
+class StratResult:
+    """A cohort cut into a low-risk (0) and a high-risk (1) group at a risk cut-off, as risk_stratification defines it, in
+    numpy arrays: cutoff (1,) fp64; group (n,) int32 (-1: excluded, a NaN risk or time); at_risk, deaths (2, n) int32 and
+    surv (2, n) fp64, both groups' counts and Kaplan-Meier estimates at every subject's time, in subject order; sizes (4,)
+    int64 = low, high, excluded, distinct event times; logrank (5,) fp64 = O1, E1, V, chi2, p; time (n,) fp64, the times as
+    they were read (an input, kept for curves())."""
+    cutoff: np.ndarray
+    group: np.ndarray
+    at_risk: np.ndarray
+    deaths: np.ndarray
+    surv: np.ndarray
+    sizes: np.ndarray
+    logrank: np.ndarray
+    time: np.ndarray
+
+    def _statistic(self, k: int) -> float:
+        if int(self.sizes[0]) == 0 or int(self.sizes[1]) == 0:
+            raise ValueError("one risk group is empty")
+        return float(self.logrank[k])
+
+    def chi2_value(self) -> float:
+        """The log-rank chi-square (one degree of freedom) as a Python float.  Raises ValueError("one risk group is empty")
+        where that is why there is none; NaN where V == 0 (nobody has an event)."""
+        return self._statistic(3)
+
+    def logrank_p_value(self) -> float:
+        """The log-rank p-value, erfc(sqrt(chi2 / 2)), as a Python float: raises and is NaN as chi2_value."""
+        return self._statistic(4)
+
+    def curves(self):
+        """For plotting: per group g (0 low, 1 high) a dict of arrays over the sorted distinct times of the group's subjects:
+        'time', 'surv' (S_g), 'at_risk' and 'deaths' (of the group at that time)."""
+        out = []
+        for g in (0, 1):
+            members = np.flatnonzero(self.group == g)
+            t, first = np.unique(self.time[members], return_index=True)
+            pick = members[first]
+            out.append({"time": t, "surv": self.surv[g][pick], "at_risk": self.at_risk[g][pick], "deaths": self.deaths[g][pick]})
+        return out
+
+
+def risk_stratification(censorship, time, risk, cutoff=None) -> StratResult:
+    """The other half of a survival report beside Harrell's C: the cohort cut into a high- and a low-risk group at a risk
+    cut-off, both groups' Kaplan-Meier curves and the log-rank test of their separation, on the host in numpy.
+    censorship, time, risk: (n,) array-likes (censorship and risk are read as fp32, time as fp64 -- what ResidentCohort and
+    EvalResult hold, after a copy to the host); cutoff: None or a number.  Returns a StratResult.  THE DEFINITION:
+      event_i   = (1 - censorship_i) != 0, as in concordance_index_censored.
+      excluded  a subject whose risk or time is NaN: group -1.  It is counted in no set below; its own at_risk and deaths
+                are 0 and its surv is NaN.
+      r_i       = (double)risk_i + 0.0: -0 and +0 are one value.
+      cutoff    given, or the median of the m non-excluded r: (r_(lo) + r_(hi)) / 2.0 at the order statistics (m - 1) // 2
+                and m // 2 -- numpy.median's arithmetic, the same bits; NaN when m = 0.  E.g. the training cohort's median
+                for the validation cohort, which is the sound protocol.
+      group_i   = 1 (high) if r_i > cutoff, else 0 (low): a risk equal to the cut-off is low.
+      at_risk[g][i] = #{j in g : t_j >= t_i},  deaths[g][i] = #{j in g : t_j == t_i and event_j}, for every i not excluded.
+      surv[g][i] = S_g(t_i): the product of (n_g(u) - d_g(u)) / n_g(u) over the group's distinct event times u <= t_i, each
+                factor one fp64 division of two exact integers, multiplied in ascending time; 1 before the first event,
+                exactly 0 from a factor of 0 on.
+      log-rank  over the m_u distinct event times u of both groups together, n = n_0 + n_1 and d = d_0 + d_1 at u:
+                O1 = sum d_1;  E1 = sum (d * n_1) / n;  V = sum (((d * q) * (1 - q)) * (n - d)) / (n - 1) with q = n_1 / n (a
+                term of 0 where n == 1), both added in ascending time;  x = O1 - E1;  chi2 = (x * x) / V;  p = erfc(sqrt(chi2
+                / 2)) (one degree of freedom).  chi2 and p are NaN where a group is empty or V == 0.
+    By sorting, O(n log n).  The integers and the cut-off are exact; surv is within (2k + 1) 2^-53 of the exact product of its k
+    factors and E1, V within (m_u + 8) 2^-53 of the exact sums (tests/stratify_cases.py counts the roundings)."""
+    c = np.asarray(censorship, dtype=np.float32).reshape(-1)
+    t = np.asarray(time, dtype=np.float64).reshape(-1)
+    r = np.asarray(risk, dtype=np.float32).reshape(-1).astype(np.float64) + 0.0          # (-0 and +0: one value)
+    n = r.size
+    if n == 0 or c.size != n or t.size != n:
+        raise ValueError(f"risk_stratification: {c.size} censorship values, {t.size} times and {n} risks (equal and at least one)")
+    event = (np.float32(1.0) - c) != 0
+    valid = ~(np.isnan(r) | np.isnan(t))
+    if cutoff is None:
+        cut = float(np.median(r[valid])) if valid.any() else float("nan")
+    else:
+        cut = float(np.asarray(cutoff, dtype=np.float64).reshape(-1)[0])
+    with np.errstate(invalid="ignore"):
+        group = np.where(valid, (r > cut).astype(np.int32), np.int32(-1)).astype(np.int32)
+    at_risk, deaths = np.zeros((2, n), dtype=np.int32), np.zeros((2, n), dtype=np.int32)
+    surv = np.full((2, n), np.nan, dtype=np.float64)
+    pooled = np.unique(t[valid & event])                                  # the distinct event times of both groups
+    n_at, d_at = [], []
+    for g in (0, 1):
+        times = np.sort(t[group == g])
+        deaths_at = np.sort(t[(group == g) & event])
+        count_at = lambda u: (times.size - np.searchsorted(times, u, "left"),
+                              np.searchsorted(deaths_at, u, "right") - np.searchsorted(deaths_at, u, "left"))
+        a, d = count_at(t[valid])
+        at_risk[g, valid], deaths[g, valid] = a, d
+        u = np.unique(deaths_at)
+        a, d = count_at(u)
+        s = np.concatenate([[1.0], np.cumprod((a - d).astype(np.float64) / a.astype(np.float64))])
+        surv[g, valid] = s[np.searchsorted(u, t[valid], "right")]          # as many factors as event times <= t_i
+        a, d = count_at(pooled)
+        n_at.append(a.astype(np.float64))
+        d_at.append(d.astype(np.float64))
+    nn, dd, n1 = n_at[0] + n_at[1], d_at[0] + d_at[1], n_at[1]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        q = n1 / nn
+        e_terms = (dd * n1) / nn
+        v_terms = np.where(nn == 1.0, 0.0, (((dd * q) * (1.0 - q)) * (nn - dd)) / (nn - 1.0))
+    o1, e1, v = float(d_at[1].sum()), 0.0, 0.0
+    for e_term, v_term in zip(e_terms.tolist(), v_terms.tolist()):
+        e1 += e_term
+        v += v_term
+    sizes = np.array([int((group == 0).sum()), int((group == 1).sum()), int((~valid).sum()), pooled.size], dtype=np.int64)
+    chi2 = p = float("nan")
+    if sizes[0] and sizes[1] and v != 0.0:
+        x = o1 - e1
+        chi2 = (x * x) / v
+        p = math.erfc(math.sqrt(chi2 / 2.0))
+    return StratResult(np.array([cut], dtype=np.float64), group, at_risk, deaths, surv, sizes,
+                       np.array([o1, e1, v, chi2, p], dtype=np.float64), t)
 
 
 def cut_eval_windows(ids, lengths, slab_index, max_window_rows: int = 1 << 19, max_window_slides: int = 32):
