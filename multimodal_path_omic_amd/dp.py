@@ -5,6 +5,9 @@ buffer per optimiser step (RCCL over xGMI via torch.distributed backend 'nccl'; 
 tests).  Parameter .grad tensors are views into one contiguous buffer, so backward accumulates
 straight into the bucket and the collective needs no packing.  The reference's nn.DataParallel
 (models/mcat/main.py:267-268) is not reproduced: with batch_size=1 it never used more than one GPU.
+
+Whole epochs over a cohort sharded across the ranks: shard_slides, epoch_orders, global_order and gather_ragged below are
+the plan (pure host functions) and the one ragged collective; harness.train_epoch_dp / validate_dp are the loops.
 """
 from __future__ import annotations
 
@@ -429,3 +432,114 @@ def assign_slides(lengths: Sequence[int], world_size: int) -> "List[List[int]]":
     for r in range(world_size):
         out[r].sort()
     return out
+
+
+# ------------------------------------------------------------------------------------ epochs over a sharded resident cohort
+# Every rank keeps its own slides resident for the whole run (harness.ResidentCohort([slides[i] for i in shards[rank]])) and
+# runs the same number of windows per epoch: the one rule that keeps the collectives matched.  Everything below is a pure
+# function of host lists, so every rank computes the whole plan and no size is ever exchanged.
+def shard_slides(lengths: Sequence[int], world_size: int) -> "List[List[int]]":
+    """The cohort's slides dealt to `world_size` ranks for a whole run: global slide ids per rank, each list sorted.  The
+    slides are sorted by (-length, id) and dealt in boustrophedon order (rank 0 .. W-1, then W-1 .. 0, and so on), so the
+    shards are disjoint, cover every slide, differ in SIZE by at most 1 and in ROWS by at most the longest slide (round j
+    moves the difference of two ranks by at most that round's range of lengths, with alternating sign, and the rounds'
+    ranges do not overlap).  Deterministic: every rank computes the same plan.
+    Not assign_slides: that one balances the rows of one window and lets the counts fall where they may.  A sampled step
+    costs k rows per slide whatever the slide's length, so equal counts balance compute; the rows balance memory."""
+    world_size = int(world_size)
+    if world_size < 1:
+        raise ValueError(f"shard_slides: world_size {world_size} below 1")
+    order = sorted(range(len(lengths)), key=lambda i: (-int(lengths[i]), i))
+    out: "List[List[int]]" = [[] for _ in range(world_size)]
+    for j, i in enumerate(order):
+        rnd, pos = divmod(j, world_size)
+        out[pos if rnd % 2 == 0 else world_size - 1 - pos].append(i)
+    for shard in out:
+        shard.sort()
+    return out
+
+
+_MASK64 = (1 << 64) - 1
+
+
+def _splitmix64(x: int) -> int:
+    x = (x + 0x9E3779B97F4A7C15) & _MASK64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _MASK64
+    return x ^ (x >> 31)
+
+
+def _permutation(n: int, seed: int, epoch: int, rank: int) -> "List[int]":
+    """Fisher-Yates over range(n) on a splitmix64 stream keyed by (seed, epoch, rank): integer arithmetic alone, so the
+    order is the same on every host and under every library version."""
+    state = _splitmix64(int(seed) & _MASK64)
+    state = _splitmix64(state ^ (int(epoch) & _MASK64))
+    state = _splitmix64(state ^ (int(rank) & _MASK64))
+    perm = list(range(n))
+    for i in range(n - 1, 0, -1):
+        state = _splitmix64(state)
+        j = state % (i + 1)             # (modulo bias below 2^-40 for any cohort that fits a machine)
+        perm[i], perm[j] = perm[j], perm[i]
+    return perm
+
+
+def epoch_orders(shard_sizes: Sequence[int], n_per_window: int, seed: int, epoch: int):
+    """The shuffled epoch of every rank and the number of windows all of them run: -> (orders, n_windows).  orders[r] is a
+    permutation of range(shard_sizes[r]) -- ids LOCAL to rank r's cohort -- and a pure function of (seed, epoch, r,
+    shard_sizes[r]): every rank can compute every rank's order, and one process can replay the global schedule
+    (global_order).  n_windows = min over r of shard_sizes[r] // n_per_window: what harness.train_epoch_dp runs on EVERY
+    rank, whatever its own shard would allow; the ids behind n_windows * n_per_window are that epoch's leftover.
+    A world whose smallest shard holds fewer than n_per_window slides raises ValueError: it has no window to run."""
+    sizes = [int(s) for s in shard_sizes]
+    n = int(n_per_window)
+    if not sizes or n < 1:
+        raise ValueError(f"epoch_orders: {len(sizes)} shards and {n} slides per window (at least one of each)")
+    if min(sizes) < n:
+        r = sizes.index(min(sizes))
+        raise ValueError(f"epoch_orders: rank {r}'s shard holds {sizes[r]} slides, fewer than one window of {n}: every rank "
+                         "must run the same number of windows, and this world has none to run")
+    return [_permutation(s, seed, epoch, r) for r, s in enumerate(sizes)], min(sizes) // n
+
+
+def global_order(orders, shards, n_per_window: int, n_windows: int) -> "List[int]":
+    """The GLOBAL slide ids one process would run to form the windows the ranks form together under (orders, n_windows) of
+    epoch_orders over shards of shard_slides: global window w is rank 0's window w, then rank 1's, and so on -- n_windows
+    windows of n_per_window * world slides."""
+    n = int(n_per_window)
+    out = []
+    for w in range(int(n_windows)):
+        for order, shard in zip(orders, shards):
+            if len(order) < (w + 1) * n:
+                raise ValueError(f"global_order: an order of {len(order)} ids has no window {w} of {n}")
+            out += [shard[i] for i in order[w * n:(w + 1) * n]]
+    return out
+
+
+def _world(group=None) -> int:
+    return dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+
+
+def _rank(group=None) -> int:
+    return dist.get_rank(group) if dist.is_available() and dist.is_initialized() else 0
+
+
+def gather_ragged(t: torch.Tensor, sizes: Sequence[int], group=None) -> torch.Tensor:
+    """Per-slide results of every rank, concatenated rank-major: `t` is (sizes[rank], ...) on this rank and `sizes` is the
+    shard plan every rank holds already, so no size is exchanged -- pad to max(sizes), ONE all-gather, keep the valid
+    prefixes.  The result is the same tensor, bit for bit, on every rank.  Without an initialised process group, or at world
+    size 1, `t` itself comes back.  Raises ValueError, before the collective, where `sizes` does not name the world or
+    this rank's rows.  (nccl: enqueued on the device, no host synchronisation; gloo stages through the host.)"""
+    world = _world(group)
+    if world == 1:
+        return t
+    sizes = [int(s) for s in sizes]
+    rank = dist.get_rank(group)
+    if len(sizes) != world or min(sizes) < 0 or int(t.shape[0]) != sizes[rank]:
+        raise ValueError(f"gather_ragged: sizes {sizes} for a world of {world}, and {int(t.shape[0])} rows on rank {rank}")
+    most = max(sizes)
+    mine = t.contiguous()
+    if sizes[rank] < most:
+        mine = torch.cat([mine, mine.new_zeros((most - sizes[rank], *t.shape[1:]))])
+    parts = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(parts, mine, group=group)
+    return torch.cat([p[:s] for p, s in zip(parts, sizes)])

@@ -256,8 +256,8 @@ class GraphedWindowStep:
     out (`opt=None`): replay, then all-reduce the bucket and step eagerly.
 
     The gene-expression model takes the window (bags, labels) of make_ge_window: the body is train_ge_window (its one
-    loss, `ce`), the call returns the per-bag loss alone, and split_patch_grad is refused (no data-parallel exchange is
-    built for that model).
+    loss, `ce`), the call returns the per-bag loss alone, and split_patch_grad is refused: that model's data-parallel
+    step (opt=None, train_epoch_dp) reduces its whole bucket in one all-reduce.
 
     sample_rows = k lifts the one-window restriction: the captured body starts (right behind the counter bump, so that a
     replay's sample and masks share its epoch) with the gather of ops.RowSampler -- k rows of every slide into a buffer of
@@ -275,7 +275,8 @@ class GraphedWindowStep:
     slides instead: bind() then takes further SlideSet windows -- slide ids into a cohort that lives on the device, no copy
     and no H2D transfer per window -- and a SlideSet with `cycle` may hold slides shorter than k (lapped).  A step captured
     on one kind of window refuses the other: the two gathers read different descriptors.  train_epoch drives an epoch
-    (the gene-expression model's (SlideSet, labels) windows of a GeResidentCohort: train_ge_epoch).
+    (the gene-expression model's (SlideSet, labels) windows of a GeResidentCohort: train_ge_epoch; one rank's share of a
+    data-parallel epoch over a sharded cohort, either model: train_epoch_dp).
     """
 
     def __init__(self, model, bucket, window, grad_acc_step: int, opt=None, warmup: int = 2, pool=None,
@@ -1363,3 +1364,146 @@ def test_ge(model, cohort: GeResidentCohort, ids, save_dir=None, name: str = "AT
 
 
 test_ge.__test__ = False
+
+
+# ------------------------------------------------------------------------------------ data-parallel epochs (one process per GPU)
+def _check_epoch_order(who: str, step, cohort, order) -> "List[int]":
+    """train_epoch's validation of a whole order -- the cohort's layout against the step's capture, every id in range, every
+    slide at least k rows unless the cohort laps -- before anything runs."""
+    if (int(cohort.rows[0].shape[1]), cohort.rows[0].dtype) != (step.sampler.width, step.sampler.dtype):
+        raise ValueError(f"{who}: the cohort's rows are {int(cohort.rows[0].shape[1])} x {cohort.rows[0].dtype}, the step was "
+                         f"captured for {step.sampler.width} x {step.sampler.dtype}")
+    order, k = [int(i) for i in order], step.sampler.k
+    for i in order:
+        if not 0 <= i < cohort.n_slides:
+            raise ValueError(f"{who}: slide id {i} outside the cohort's {cohort.n_slides} slides")
+        if not cohort.cycle and cohort.lengths[i] < k:
+            raise ValueError(f"{who}: slide {i} has {cohort.lengths[i]} rows, fewer than k = {k}, and the cohort does not lap "
+                             "short slides (cycle=False)")
+    return order
+
+
+def train_epoch_dp(step: "GraphedWindowStep", cohort, order, opt, n_windows: int, group=None):
+    """One rank's share of a data-parallel epoch: train_epoch / train_ge_epoch with the gradient exchange and the optimiser
+    between the replays.  The plan is dp's: shards = shard_slides(lengths, world); this rank's `cohort` is a ResidentCohort
+    (GeResidentCohort) over [slides[i] for i in shards[rank]]; (orders, n_windows) = epoch_orders(shard sizes, n, seed,
+    epoch) and `order` = orders[rank], ids local to this rank's cohort.
+
+    step: a GraphedWindowStep captured with opt=None and sample_rows=k on a window of `cohort`; its grad_acc_step is the
+    PER-RANK window size n (the mean over ranks completes 1 / (n * world)) and its `l1` is passed explicitly (the optimiser
+    is not inside the step) and must be `opt`'s l1_lambda.  Fusion models may be captured with split_patch_grad=True.
+    opt: the flat optimiser over the step's bucket, stepped eagerly here; FlatOptimizer(max_grad_norm=, skip_nonfinite=)
+    works unchanged: it measures the REDUCED gradient, the same on every rank, so every rank clips or skips alike.
+    n_windows: the loop runs exactly that many windows ON EVERY RANK -- a rank that ran one more would wait in its
+    collective for ever.  The whole `order` is validated as train_epoch validates it, and an order of fewer than
+    n_windows * n ids is refused, before the first collective; what lies behind n_windows * n comes back as `leftover`
+    and is not run.
+
+    Per window the loop enqueues: the bind, the selects into the step's static tensors, the replay; with split_patch_grad
+    the all-reduce of flat[head:] while replay_tail() computes the patch layer's weight gradient, then that of flat[:head],
+    otherwise (always for the gene-expression model) one all-reduce of the bucket; opt.step(l1_slides = n * world); the
+    device copies of loss (and risk) into epoch-long buffers.  Under nccl (RCCL) there is no host synchronisation and no H2D
+    copy inside the loop; gloo, which the tests run on one card, stages every collective through the host.  The nccl leg is
+    the same calls and is exercised by multi-GPU bench runs (bench.py --gpus N) alone.  With no process group
+    initialised the world is 1: no collective, the same loop.
+
+    Ranks must not share dropout masks and row samples: the generator's seed is torch.initial_seed() (ops._reserve), read
+    when the step is captured, so call torch.manual_seed(base + rank) BEFORE the capture.
+
+    Returns what train_epoch (loss, risk, ids_run, leftover) or train_ge_epoch (loss, ids_run, leftover) returns, for this
+    rank's slides, ids local to this rank's cohort; epoch_c_index_dp gives the epoch's training C-index over all ranks."""
+    from . import dp
+    who = "train_epoch_dp"
+    if step.sampler is None or step.sampler.source != "slides":
+        raise ValueError(f"{who}: the step must be captured with sample_rows on a window of a resident cohort")
+    if step.opt is not None:
+        raise ValueError(f"{who}: the step was captured with its optimiser inside; a data-parallel step leaves it out "
+                         "(opt=None): the update comes after the exchange")
+    if isinstance(cohort, GeResidentCohort) != step.ge:
+        raise ValueError(f"{who}: a {'gene-expression' if step.ge else 'fusion-model'} step over a {type(cohort).__name__}")
+    if opt.bucket is not step.bucket:
+        raise ValueError(f"{who}: the optimiser steps another gradient bucket than the one the step writes")
+    if float(getattr(opt, "l1_lambda", 0.0)) != step.l1:
+        raise ValueError(f"{who}: the step reports the L1 penalty with l1 = {step.l1}, the optimiser folds its gradient with "
+                         f"l1_lambda = {float(getattr(opt, 'l1_lambda', 0.0))}: pass the optimiser's value to the step")
+    order = _check_epoch_order(who, step, cohort, order)
+    n, n_win = step.sampler.n_slides, int(n_windows)
+    if n_win < 0 or len(order) < n_win * n:
+        raise ValueError(f"{who}: {n_win} windows of {n} slides need {n_win * n} ids, the order holds {len(order)}; n_windows is "
+                         "dp.epoch_orders' -- the same on every rank")
+    world = dp._world(group)
+    bucket = step.bucket
+    head = step.head_numel() if step.split else None
+    leftover = order[n_win * n:]
+    dev = cohort.device
+    order_dev = torch.tensor(order[:n_win * n], dtype=torch.int32).to(dev, non_blocking=True)
+    loss = torch.empty(n_win * n, dtype=torch.float32, device=dev)
+    risk = None if step.ge else torch.empty(n_win * n, dtype=torch.float32, device=dev)
+    static = step.window[1:]
+    folds_l1 = bool(getattr(opt, "l1_lambda", 0.0))
+    for w in range(n_win):
+        lo, hi = w * n, (w + 1) * n
+        step.bind(cohort.window(order_dev[lo:hi], order[lo:hi], out=static))
+        out = step()
+        if step.split:
+            rest = bucket.all_reduce_mean_async(lo=head, group=group)
+            step.replay_tail()
+            first = bucket.all_reduce_mean_async(lo=0, hi=head, group=group)
+            for handle in (rest, first):
+                if handle is not None:
+                    handle.wait()
+        else:
+            bucket.all_reduce_mean(group)
+        if folds_l1:
+            opt.step(l1_slides=n * world)
+        else:
+            opt.step()
+        if step.ge:
+            loss[lo:hi].copy_(out.view(-1), non_blocking=True)
+        else:
+            loss[lo:hi].copy_(out[0].view(-1), non_blocking=True)
+            risk[lo:hi].copy_(out[1].view(-1), non_blocking=True)
+    return (loss, order_dev, leftover) if step.ge else (loss, risk, order_dev, leftover)
+
+
+def epoch_c_index_dp(cohort: ResidentCohort, ids_run, risk, group=None):
+    """The training C-index of a data-parallel epoch over ALL ranks' slides: this rank's risks (train_epoch_dp's `risk`) and
+    the censorship and survival months of the slides it ran (`ids_run`) are gathered rank-major -- three all-gathers of
+    equal sizes, n_windows * n per rank -- and concordance_index_device runs over the union.  -> (c_index (1,) fp64, counts
+    (3,) int64) on the device: integer counts over the same gathered vectors, so every rank holds the same counts and the
+    same C-index bits."""
+    from . import dp
+    sizes = [int(risk.numel())] * dp._world(group)
+    ids = ids_run.to(torch.int64)
+    cens, months, risks = (dp.gather_ragged(t, sizes, group) for t in
+                           (cohort.censorship.index_select(0, ids), cohort.survival_months.index_select(0, ids), risk.detach()))
+    return concordance_index_device(cens, months, risks)
+
+
+def validate_dp(evaluator, sizes, group=None):
+    """A validation epoch over a sharded cohort: every rank calls its own CohortEvaluator (GeCohortEvaluator) -- eager or
+    captured, over the validation slides it holds; nothing in those classes knows about ranks -- and the per-slide results are
+    gathered (dp.gather_ragged; sizes[r] = the number of slides rank r evaluates, from the shard plan; unequal sizes are
+    the normal case).  Returns the evaluator's result type over the UNION of the slides in rank-major order, the same bits
+    on every rank: loss, risk, hazards, survs, Y with mean_loss and the C-index (counts) recomputed on the device over the
+    gathered risks, censorship and survival months; for the gene-expression model loss, Y and, over them and the gathered
+    labels, classification_metrics_device.  Maps and pooling attentions (need_maps / need_paths) stay with their rank: the
+    union's result carries none.  At world size 1 the evaluator's own result comes back."""
+    from . import dp
+    world = dp._world(group)
+    sizes = [int(s) for s in sizes]
+    if len(sizes) != world or sizes[dp._rank(group)] != len(evaluator.ids):
+        raise ValueError(f"validate_dp: sizes {sizes} for a world of {world} whose rank here evaluates {len(evaluator.ids)} slides")
+    r = evaluator()
+    if world == 1:
+        return r
+
+    def gather(t):
+        return dp.gather_ragged(t, sizes, group)
+    if isinstance(evaluator, GeCohortEvaluator):
+        loss, y, labels = gather(r.loss), gather(r.Y), gather(evaluator.labels)
+        pred, confusion, counts, summary = classification_metrics_device(y, labels, loss)
+        return GeEvalResult(loss, y, pred, confusion, counts, summary[2:3], summary[0:1], summary[1:2])
+    loss, risk, hazards, survs, y = (gather(t) for t in (r.loss, r.risk, r.hazards, r.survs, r.Y))
+    c_index, counts = concordance_index_device(gather(evaluator.censorship), gather(evaluator.survival_months), risk)
+    return EvalResult(loss, risk, hazards, survs, y, loss.mean(0, keepdim=True), c_index, counts)
