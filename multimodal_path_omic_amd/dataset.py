@@ -7,7 +7,7 @@
 
 A dataset holds one row per slide it kept, hands harness.ResidentCohort / GeResidentCohort their dicts (`slides()`, `cohort()`)
 and splits by patient into slide ids of that ONE cohort (`split()`: fit.split_patients).  Host code: no kernel, no C entry; the
-rows reach the device through harness._cohort_slabs as every cohort's do.  pandas, scipy, h5py and yaml are the reference's
+rows reach the device through harness._ResidentRows as every cohort's do.  pandas, scipy, h5py and yaml are the reference's
 dependencies and are not imported here.
 
 Numbers are parsed with Python's float(), which rounds correctly; pandas' default C parser does not always, so a cell of
@@ -228,7 +228,7 @@ class SurvivalDataset(_SlideDataset):
 
     def slides(self) -> "List[dict]":
         """The dicts harness.ResidentCohort takes.  Each `wsi` is the memory-mapped file: no row is read until
-        harness._cohort_slabs concatenates a slab, and then one slab's rows (slab_bytes of the bag dtype; twice that in
+        harness._ResidentRows concatenates a slab, and then one slab's rows (slab_bytes of the bag dtype; twice that in
         fp32 for a bf16 cohort) are in host memory at a time, never the cohort's."""
         return [{"wsi": self.patches(i), "omics": [o[i] for o in self.omics], "survival_months": float(self.survival_months[i]),
                  "survival_class": int(self.survival_class[i]), "censorship": self.censorship[i].item()} for i in range(len(self))]

@@ -5,6 +5,7 @@ gradient accumulation over `grad_acc_step` slides, Harrell's C-index.  No per-sl
 from __future__ import annotations
 
 import math
+from contextlib import contextmanager
 from dataclasses import dataclass
 from typing import List, Sequence
 
@@ -240,6 +241,23 @@ def _slide_weights(n: int, grad_acc_step: int, device) -> torch.Tensor:
     return w
 
 
+@contextmanager
+def _device_feature_scale(bags, scale):
+    """For the length of one forward (and backward) over `bags`, the window carries the feature scale of what it holds now,
+    found on the device into `scale` (1,) (ops.feature_scale_device: three tiny launches, enqueued on entry) and read by the
+    fp32 patch layer through a pointer (bags.data._mpo_feature_scale_dev).  scale None -- a window that never reaches the
+    scaled kernel -- carries nothing."""
+    if scale is None:
+        yield
+        return
+    from . import ops
+    bags.data._mpo_feature_scale_dev = ops.feature_scale_device(bags.data, out=scale)
+    try:
+        yield
+    finally:
+        del bags.data._mpo_feature_scale_dev
+
+
 class GraphedWindowStep:
     """One window step (forward, `ces` loss, backward, gradients into the flat bucket, optionally the Adam
     update) captured ONCE into a HIP graph and replayed: ~500 launches per window cost one graph launch on
@@ -386,22 +404,19 @@ class GraphedWindowStep:
         from . import ops
         ops.bump_step_counters(self.epoch, self.opt.t_dev if self.opt is not None else None)   # one launch for both
         bags = self.window[0] if self.sampler is None else self.sampler()
-        if self.scale is not None:
-            # the range pass over the whole window as it is at this replay; the window carries the result for the length of
-            # the body only (an eager step on the same tensor afterwards finds its scale on the host, as ever)
-            bags.data._mpo_feature_scale_dev = ops.feature_scale_device(bags.data, out=self.scale)
-        self.bucket.begin()
-        try:
-            if self.ge:
-                out = train_ge_window(self.model, bags, self.window[1], self.acc, l1=self.l1)
-            else:
-                _, omics, labels, cens = self.window
-                ops.defer_patch_weight_grad = self.split
-                out = train_window(self.model, bags, omics, labels, cens, self.acc, **self.train_kwargs)
-        finally:
-            ops.defer_patch_weight_grad = False
-            if self.scale is not None:
-                del bags.data._mpo_feature_scale_dev
+        # the range pass over the whole window as it is at this replay; the window carries the result for the length of the
+        # forward and backward only (an eager step on the same tensor afterwards finds its scale on the host, as ever)
+        with _device_feature_scale(bags, self.scale):
+            self.bucket.begin()
+            try:
+                if self.ge:
+                    out = train_ge_window(self.model, bags, self.window[1], self.acc, l1=self.l1)
+                else:
+                    _, omics, labels, cens = self.window
+                    ops.defer_patch_weight_grad = self.split
+                    out = train_window(self.model, bags, omics, labels, cens, self.acc, **self.train_kwargs)
+            finally:
+                ops.defer_patch_weight_grad = False
         self.bucket.finish()
         if self.split and flush:
             ops.flush_patch_weight_grads()
@@ -487,46 +502,65 @@ class GraphedWindowStep:
 
 
 # ------------------------------------------------------------------------------------ a cohort resident on the device
-def _cohort_slabs(cohort, who: str, slides: Sequence[dict], bag_dtype, slab_bytes: int):
-    """The row storage of a resident cohort (ResidentCohort, GeResidentCohort; `who` names it in the refusals), on
-    cohort.device: `lengths`, `slabs` (at most slab_bytes each, a slide never split), `rows` (per slide a view of its slab) and
-    where a slide lies, `slab_index` / `row_offset`, set on `cohort`."""
-    if len(slides) == 0:
-        raise ValueError(f"{who}: no slides")
-    cohort.lengths = [int(s["wsi"].shape[0]) for s in slides]
-    width = int(slides[0]["wsi"].shape[1])
-    row_bytes = width * torch.empty(0, dtype=bag_dtype).element_size()
-    if row_bytes % 16:
-        raise ValueError(f"{who}: a row of {row_bytes} bytes is not a multiple of 16 bytes")
-    if any(m < 1 for m in cohort.lengths) or any(int(s["wsi"].shape[1]) != width for s in slides):
-        raise ValueError(f"{who}: every slide needs at least one patch row, and all the same width")
-    cohort.slabs, cohort.rows, group = [], [], []
-    # where a slide lies: its slab and its first row there (slides of one slab lie back to back in id order, so a run of
-    # consecutive ids inside one slab is a contiguous row range: the evaluators' windows are views of it)
-    cohort.slab_index, cohort.row_offset = [], []
+class _ResidentRows:
+    """The row storage of a resident cohort (ResidentCohort, GeResidentCohort; the subclass's name heads the refusals), on
+    `device`: `lengths`, `slabs` (at most slab_bytes each, a slide never split), `rows` (per slide a view of its slab), where
+    a slide lies (`slab_index` / `row_offset`), the pointer / length table csrc/bag_sample.hip's slide gather is addressed
+    through (`table_ptrs`, `table_lens`), and `cycle`.  A subclass adds its per-slide targets and window()'s selects."""
 
-    def flush():
-        if group:
-            slab = torch.cat([slides[i]["wsi"] for i in group]).to(device=cohort.device, dtype=bag_dtype, non_blocking=True)
-            cohort.slabs.append(slab)
-            cohort.rows.extend(slab.split([cohort.lengths[i] for i in group]))
-            first = 0
-            for i in group:
-                cohort.slab_index.append(len(cohort.slabs) - 1)
-                cohort.row_offset.append(first)
-                first += cohort.lengths[i]
-            group.clear()
-    filled = 0
-    for i, m in enumerate(cohort.lengths):
-        if group and filled + m * row_bytes > slab_bytes:
-            flush()
-            filled = 0
-        group.append(i)
-        filled += m * row_bytes
-    flush()
+    def __init__(self, slides: Sequence[dict], device, bag_dtype, cycle: bool, slab_bytes: int):
+        who = type(self).__name__
+        self.device, self.cycle = torch.device(device), bool(cycle)
+        if len(slides) == 0:
+            raise ValueError(f"{who}: no slides")
+        self.lengths = [int(s["wsi"].shape[0]) for s in slides]
+        width = int(slides[0]["wsi"].shape[1])
+        row_bytes = width * torch.empty(0, dtype=bag_dtype).element_size()
+        if row_bytes % 16:
+            raise ValueError(f"{who}: a row of {row_bytes} bytes is not a multiple of 16 bytes")
+        if any(m < 1 for m in self.lengths) or any(int(s["wsi"].shape[1]) != width for s in slides):
+            raise ValueError(f"{who}: every slide needs at least one patch row, and all the same width")
+        self.slabs, self.rows, group = [], [], []
+        # where a slide lies: its slab and its first row there (slides of one slab lie back to back in id order, so a run of
+        # consecutive ids inside one slab is a contiguous row range: the evaluators' windows are views of it)
+        self.slab_index, self.row_offset = [], []
+
+        def flush():
+            if group:
+                slab = torch.cat([slides[i]["wsi"] for i in group]).to(device=self.device, dtype=bag_dtype, non_blocking=True)
+                self.slabs.append(slab)
+                self.rows.extend(slab.split([self.lengths[i] for i in group]))
+                first = 0
+                for i in group:
+                    self.slab_index.append(len(self.slabs) - 1)
+                    self.row_offset.append(first)
+                    first += self.lengths[i]
+                group.clear()
+        filled = 0
+        for i, m in enumerate(self.lengths):
+            if group and filled + m * row_bytes > slab_bytes:
+                flush()
+                filled = 0
+            group.append(i)
+            filled += m * row_bytes
+        flush()
+        self.table_ptrs, self.table_lens = SlideSet.slide_table(self.rows)
+
+    @property
+    def n_slides(self):
+        return len(self.lengths)
+
+    def _slide_set(self, ids_dev, ids_host) -> SlideSet:
+        """The SlideSet a window() starts with: the slides `ids_host` (checked against the cohort) = `ids_dev`."""
+        ids_host = [int(i) for i in ids_host]
+        for i in ids_host:
+            if not 0 <= i < self.n_slides:
+                raise ValueError(f"{type(self).__name__}.window: slide id {i} outside the cohort's {self.n_slides} slides")
+        return SlideSet([self.rows[i] for i in ids_host], [self.lengths[i] for i in ids_host], self.table_ptrs, self.table_lens,
+                        ids_dev, self.cycle)
 
 
-class ResidentCohort:
+class ResidentCohort(_ResidentRows):
     """A cohort that lives on the device once, for shuffled epochs of the sampled, captured step (bag_dtype bf16, fp16 -- bf16's
     bytes, fp32 H_bag behind the patch layer, no feature scale: captured like a bf16 cohort -- or fp32
     for a step captured with device_feature_scale=True): every slide's rows (in
@@ -539,19 +573,13 @@ class ResidentCohort:
     gene-expression cohort ((SlideSet, labels) windows) is not -- GeResidentCohort is that one, over the same storage."""
 
     def __init__(self, slides: Sequence[dict], device, bag_dtype=torch.bfloat16, cycle: bool = False, slab_bytes: int = 1 << 30):
-        self.device, self.cycle = torch.device(device), bool(cycle)
-        _cohort_slabs(self, "ResidentCohort", slides, bag_dtype, slab_bytes)
-        self.table_ptrs, self.table_lens = SlideSet.slide_table(self.rows)
+        super().__init__(slides, device, bag_dtype, cycle, slab_bytes)
         n_groups = len(slides[0]["omics"])
         self.omics = [torch.stack([s["omics"][i] for s in slides]).to(self.device, non_blocking=True) for i in range(n_groups)]
         self.labels = torch.tensor([s["survival_class"] for s in slides], dtype=torch.int64).to(self.device, non_blocking=True)
         self.censorship = torch.tensor([float(s["censorship"]) for s in slides]).to(self.device, non_blocking=True)
         self.survival_months = torch.tensor([float(s["survival_months"]) for s in slides],
                                             dtype=torch.float64).to(self.device, non_blocking=True)
-
-    @property
-    def n_slides(self):
-        return len(self.lengths)
 
     def window(self, ids_dev, ids_host, out=None):
         """(SlideSet, omics, labels, cens) for the slides `ids_host` (host ints) = `ids_dev` (DEVICE int32, the same values; in
@@ -562,17 +590,56 @@ class ResidentCohort:
         any step.bind() has looked at the window: if that bind then refuses, the step is left with the new omics, labels and
         censorship beside the old rows -- validate first, as train_epoch does for the whole order, or leave `out` away and let
         bind() copy."""
-        ids_host = [int(i) for i in ids_host]
-        for i in ids_host:
-            if not 0 <= i < self.n_slides:
-                raise ValueError(f"ResidentCohort.window: slide id {i} outside the cohort's {self.n_slides} slides")
-        bags = SlideSet([self.rows[i] for i in ids_host], [self.lengths[i] for i in ids_host], self.table_ptrs, self.table_lens,
-                        ids_dev, self.cycle)
+        bags = self._slide_set(ids_dev, ids_host)
         o_omics, o_labels, o_cens = out if out is not None else ([None] * len(self.omics), None, None)
         omics = [torch.index_select(x, 0, ids_dev, out=o) for x, o in zip(self.omics, o_omics)]
         labels = torch.index_select(self.labels, 0, ids_dev, out=o_labels)
         cens = torch.index_select(self.censorship, 0, ids_dev, out=o_cens)
         return bags, omics, labels, cens
+
+
+def _check_epoch_order(who: str, step, cohort, order) -> "List[int]":
+    """An epoch's validation of a whole order (train_epoch, train_ge_epoch, train_epoch_dp: `who`) -- the cohort's layout
+    against the step's capture, every id in range, every slide at least k rows unless the cohort laps -- before anything
+    runs.  -> the order as host ints."""
+    if (int(cohort.rows[0].shape[1]), cohort.rows[0].dtype) != (step.sampler.width, step.sampler.dtype):
+        raise ValueError(f"{who}: the cohort's rows are {int(cohort.rows[0].shape[1])} x {cohort.rows[0].dtype}, the step was "
+                         f"captured for {step.sampler.width} x {step.sampler.dtype}")
+    order, k = [int(i) for i in order], step.sampler.k
+    for i in order:
+        if not 0 <= i < cohort.n_slides:
+            raise ValueError(f"{who}: slide id {i} outside the cohort's {cohort.n_slides} slides")
+        if not cohort.cycle and cohort.lengths[i] < k:
+            raise ValueError(f"{who}: slide {i} has {cohort.lengths[i]} rows, fewer than k = {k}, and the cohort does not lap "
+                             "short slides (cycle=False)")
+    return order
+
+
+def _run_epoch(step, cohort, order: "List[int]", n_windows: int, between=None):
+    """The loop of every resident epoch, over a validated `order`: the first n_windows * n ids are uploaded once; per window
+    of the step's n slides it enqueues the bind (one tiny launch), the selects into the step's static tensors, one replay,
+    `between()` where given (a data-parallel epoch's exchange and optimiser step) and the device-to-device copies of loss and
+    risk into epoch-long buffers.  No host synchronisation and no H2D copy of its own inside the loop.
+    -> (loss, risk, ids_run, leftover); risk is None for a gene-expression step, leftover the host ids that did not run."""
+    n = step.sampler.n_slides
+    leftover = order[n_windows * n:]
+    dev = cohort.device
+    order_dev = torch.tensor(order[:n_windows * n], dtype=torch.int32).to(dev, non_blocking=True)
+    loss = torch.empty(n_windows * n, dtype=torch.float32, device=dev)
+    risk = None if step.ge else torch.empty(n_windows * n, dtype=torch.float32, device=dev)
+    static = step.window[1:]
+    for w in range(n_windows):
+        lo, hi = w * n, (w + 1) * n
+        step.bind(cohort.window(order_dev[lo:hi], order[lo:hi], out=static))
+        out = step()
+        if between is not None:
+            between()
+        if risk is None:
+            loss[lo:hi].copy_(out.view(-1), non_blocking=True)
+        else:
+            loss[lo:hi].copy_(out[0].view(-1), non_blocking=True)
+            risk[lo:hi].copy_(out[1].view(-1), non_blocking=True)
+    return loss, risk, order_dev, leftover
 
 
 def train_epoch(step: "GraphedWindowStep", cohort: ResidentCohort, order):
@@ -595,31 +662,8 @@ def train_epoch(step: "GraphedWindowStep", cohort: ResidentCohort, order):
     concordance_index_censored(1 - cens[ids_run], months[ids_run], risk) after one synchronise, gives the same number."""
     if step.sampler is None or step.sampler.source != "slides" or step.ge:
         raise ValueError("train_epoch: the step must be a fusion-model step captured with sample_rows on a ResidentCohort window")
-    n, k = step.sampler.n_slides, step.sampler.k
-    if (int(cohort.rows[0].shape[1]), cohort.rows[0].dtype) != (step.sampler.width, step.sampler.dtype):
-        raise ValueError(f"train_epoch: the cohort's rows are {int(cohort.rows[0].shape[1])} x {cohort.rows[0].dtype}, the step was "
-                         f"captured for {step.sampler.width} x {step.sampler.dtype}")
-    order = [int(i) for i in order]
-    for i in order:
-        if not 0 <= i < cohort.n_slides:
-            raise ValueError(f"train_epoch: slide id {i} outside the cohort's {cohort.n_slides} slides")
-        if not cohort.cycle and cohort.lengths[i] < k:
-            raise ValueError(f"train_epoch: slide {i} has {cohort.lengths[i]} rows, fewer than k = {k}, and the cohort does not lap "
-                             "short slides (cycle=False)")
-    n_win = len(order) // n
-    leftover = order[n_win * n:]
-    dev = cohort.device
-    order_dev = torch.tensor(order[:n_win * n], dtype=torch.int32).to(dev, non_blocking=True)
-    loss = torch.empty(n_win * n, dtype=torch.float32, device=dev)
-    risk = torch.empty(n_win * n, dtype=torch.float32, device=dev)
-    static = step.window[1:]
-    for w in range(n_win):
-        lo, hi = w * n, (w + 1) * n
-        step.bind(cohort.window(order_dev[lo:hi], order[lo:hi], out=static))
-        loss_w, risk_w = step()
-        loss[lo:hi].copy_(loss_w.view(-1), non_blocking=True)
-        risk[lo:hi].copy_(risk_w.view(-1), non_blocking=True)
-    return loss, risk, order_dev, leftover
+    order = _check_epoch_order("train_epoch", step, cohort, order)
+    return _run_epoch(step, cohort, order, len(order) // step.sampler.n_slides)
 
 
 # ------------------------------------------------------------------------------------ validation and test on the device
@@ -846,17 +890,102 @@ def check_eval_loss(kind: str, loss: str, capture: bool = False, need_maps: bool
                          "evaluator keeps no map -- run it eagerly (capture=False)")
 
 
-def _slab_window(slab, first_row: int, lengths) -> BagBatch:
-    """A window over rows [first_row, first_row + sum(lengths)) of `slab`, as a view (BagBatch.from_lengths builds its cu)."""
-    return BagBatch.from_lengths(slab[first_row:first_row + sum(lengths)], lengths)
-
-
 class _EvalWindow:
-    """One window of a CohortEvaluator: a BagBatch over a row range of a slab (a view) and the selects that go with it."""
+    """One window of an evaluator: a BagBatch over a row range of a slab (a view) and the selects that go with it."""
     __slots__ = ("ids", "lo", "hi", "bags", "omics", "labels", "cens", "scale", "graph")
 
 
-class CohortEvaluator:
+class _WindowEvaluator:
+    """What CohortEvaluator and GeCohortEvaluator share: the slides `ids` of a resident cohort cut into windows that are views
+    of its slabs (cut_eval_windows), run once per call -- eagerly, or one captured graph per window -- into run-order buffers,
+    and one device permutation (`perm`; `perm_host` on the host) that puts results into the caller's order.
+    A subclass refuses what it cannot evaluate, then calls this constructor, and supplies
+      _set_up(ids_dev)     (ids_dev: `ids` as int64 on the device) its refusals that need valid ids; `_targets`, the cohort's
+                           tensors the result is computed against, in `ids` order; `_buffers`, the run-order result tensors;
+      _select(w, run_dev)  one window's selects (w.labels, ...);
+      _body(w)             forward + loss of one window, _write()-n into the buffers -> the window's maps, or None;
+      PER_SLIDE and _result(per_slide, targets): the result type's per-slide fields, in the buffers' order, and the result over
+                           them and the targets -- of this evaluator's slides (__call__) or of all ranks' (validate_dp)."""
+
+    def __init__(self, model, cohort, ids, max_window_rows: int, max_window_slides: int, capture: bool, pool):
+        from . import ops
+        self.model, self.cohort, self.capture = model, cohort, bool(capture)
+        self.ids = [int(i) for i in ids]
+        runs, self.perm_host = cut_eval_windows(self.ids, cohort.lengths, cohort.slab_index, max_window_rows, max_window_slides)
+        dev = cohort.device
+        self.perm = torch.tensor(self.perm_host, dtype=torch.int64).to(dev, non_blocking=True)
+        self._set_up(torch.tensor(self.ids, dtype=torch.int64).to(dev, non_blocking=True))
+        weight = model.H[0].weight
+        if weight.device != cohort.labels.device:
+            raise ValueError(f"{type(self).__name__}: the model lies on {weight.device}, the cohort on {dev}")
+        self.windows, lo = [], 0
+        for run in runs:
+            w = _EvalWindow()
+            w.ids, w.lo, w.hi = run, lo, lo + len(run)
+            lo = w.hi
+            first, lengths = cohort.row_offset[run[0]], [cohort.lengths[i] for i in run]
+            # the run's rows as a view of their slab (BagBatch.from_lengths builds its cu)
+            w.bags = BagBatch.from_lengths(cohort.slabs[cohort.slab_index[run[0]]][first:first + sum(lengths)], lengths)
+            w.omics = w.cens = w.scale = w.graph = None
+            self._select(w, torch.tensor(run, dtype=torch.int64).to(dev, non_blocking=True))
+            if dev.type == "cuda":
+                w.bags.plan()                   # (its H2D copy happens here, never inside a call or a capture)
+                if ops.patch_fc_f32_supported(w.bags.data, weight):
+                    w.scale = torch.ones(1, dtype=torch.float32, device=dev)
+            self.windows.append(w)
+        self.pool = pool
+        if self.capture:
+            self._capture(pool)
+
+    def _capture(self, pool):
+        dev = self.cohort.device
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                side = torch.cuda.Stream(device=dev)
+                side.wait_stream(torch.cuda.current_stream(dev))
+                with torch.cuda.stream(side):
+                    for w in self.windows:          # allocator, lazy initialisation, every window's own shapes
+                        self._body(w)
+                torch.cuda.current_stream(dev).wait_stream(side)
+                for w in self.windows:
+                    w.graph = torch.cuda.CUDAGraph()
+                    # thread_local: other threads (RCCL's watchdog under torch.distributed) may issue HIP calls meanwhile
+                    with torch.cuda.graph(w.graph, pool=pool, capture_error_mode="thread_local"):
+                        self._body(w)
+                    pool = w.graph.pool() if pool is None else pool
+            self.pool = pool
+        finally:
+            self.model.train(was_training)
+
+    def _run_windows(self):
+        """Every window once, in run order: one replay each when captured (-> None), otherwise _body in eval mode under
+        torch.no_grad(), the mode it found put back (-> what every window's _body returned)."""
+        if self.capture:
+            for w in self.windows:
+                w.graph.replay()
+            return None
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                return [self._body(w) for w in self.windows]
+        finally:
+            self.model.train(was_training)
+
+    def _write(self, w, *rows):
+        """One window's results into its rows of the run-order buffers (`rows` in the order of PER_SLIDE)."""
+        for dst, src in zip(self._buffers, rows):
+            dst[w.lo:w.hi].copy_(src, non_blocking=True)
+
+    def _in_ids_order(self, per_window):
+        """Per-slide maps as the windows returned them (a list per window) -> one list in the caller's `ids` order."""
+        per_run = [m for window_maps in per_window for m in window_maps]
+        return [per_run[k] for k in self.perm_host]
+
+
+class CohortEvaluator(_WindowEvaluator):
     """A validation epoch over slides of a ResidentCohort with nothing copied and nothing read by the host: the reference's
     validate() (models/mcat/main.py:106-155) -- eval mode, no gradients, per-slide loss and risk, Harrell's C over the set
     -- without its per-slide .item().
@@ -893,68 +1022,37 @@ class CohortEvaluator:
     need_maps (eager only; test() sets it): forward_window(inference=True); the result carries every slide's map and
     ops.map_block_stats of it."""
 
+    PER_SLIDE = ("loss", "risk", "hazards", "survs", "Y")
+
     def __init__(self, model, cohort: ResidentCohort, ids, loss: str = "ces", alpha: float = 0.75, lambda_reg: float = 0.01,
                  l1: float = 0.0, max_window_rows: int = 1 << 19, max_window_slides: int = 32, capture: bool = False,
                  pool=None, need_maps: bool = False):
-        from . import ops
         self.kind = _model_kind(model)
         check_eval_loss(self.kind, loss, bool(capture), bool(need_maps))
-        self.model, self.cohort = model, cohort
         self.loss_name, self.alpha, self.lambda_reg, self.l1 = loss, float(alpha), float(lambda_reg), float(l1)
         self.need_maps = bool(need_maps) or loss == "cesar"
         self.return_maps = bool(need_maps)
-        self.capture = bool(capture)
-        self.ids = [int(i) for i in ids]
-        runs, perm = cut_eval_windows(self.ids, cohort.lengths, cohort.slab_index, max_window_rows, max_window_slides)
-        dev = cohort.device
-        n = len(self.ids)
-        self.perm_host = perm
-        self.perm = torch.tensor(perm, dtype=torch.int64).to(dev, non_blocking=True)
-        ids_dev = torch.tensor(self.ids, dtype=torch.int64).to(dev, non_blocking=True)
+        super().__init__(model, cohort, ids, max_window_rows, max_window_slides, capture, pool)
+
+    def _set_up(self, ids_dev):
+        cohort, dev, n = self.cohort, self.cohort.device, len(self.ids)
         self.censorship = cohort.censorship.index_select(0, ids_dev)
         self.survival_months = cohort.survival_months.index_select(0, ids_dev)
-        weight = model.H[0].weight
-        if weight.device != cohort.censorship.device:
-            raise ValueError(f"CohortEvaluator: the model lies on {weight.device}, the cohort on {dev}")
-        self.windows, lo = [], 0
-        for run in runs:
-            w = _EvalWindow()
-            w.ids, w.lo, w.hi = run, lo, lo + len(run)
-            lo = w.hi
-            first = cohort.row_offset[run[0]]
-            lengths = [cohort.lengths[i] for i in run]
-            w.bags = _slab_window(cohort.slabs[cohort.slab_index[run[0]]], first, lengths)
-            run_dev = torch.tensor(run, dtype=torch.int64).to(dev, non_blocking=True)
-            w.omics = [x.index_select(0, run_dev) for x in cohort.omics]
-            w.labels = cohort.labels.index_select(0, run_dev)
-            w.cens = cohort.censorship.index_select(0, run_dev)
-            w.scale, w.graph = None, None
-            if dev.type == "cuda":
-                w.bags.plan()                   # (its H2D copy happens here, never inside a call or a capture)
-                if ops.patch_fc_f32_supported(w.bags.data, weight):
-                    w.scale = torch.ones(1, dtype=torch.float32, device=dev)
-            self.windows.append(w)
-        n_classes = int(model.classifier.out_features)
-        # results in run order: every window writes its rows, one permutation per tensor puts them into `ids` order
-        self._loss = torch.empty(n, dtype=torch.float32, device=dev)
-        self._risk = torch.empty(n, dtype=torch.float32, device=dev)
-        self._heads = [torch.empty(n, n_classes, dtype=torch.float32, device=dev) for _ in range(3)]
-        self.pool = pool
-        if self.capture:
-            self._capture(pool)
+        self._targets = (self.censorship, self.survival_months)
+        n_classes = int(self.model.classifier.out_features)
+        self._buffers = ([torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2)] +
+                         [torch.empty(n, n_classes, dtype=torch.float32, device=dev) for _ in range(3)])
 
-    # ---- one window
+    def _select(self, w, run_dev):
+        w.omics = [x.index_select(0, run_dev) for x in self.cohort.omics]
+        w.labels = self.cohort.labels.index_select(0, run_dev)
+        w.cens = self.cohort.censorship.index_select(0, run_dev)
+
     def _body(self, w):
         """forward + loss of one window into the run-order buffers -> the window's maps (need_maps) or None."""
         from . import ops
-        bags = w.bags
-        if w.scale is not None:
-            bags.data._mpo_feature_scale_dev = ops.feature_scale_device(bags.data, out=w.scale)
-        try:
-            hazards, survs, y, att = self.model.forward_window(bags, w.omics, inference=self.need_maps)
-        finally:
-            if w.scale is not None:
-                del bags.data._mpo_feature_scale_dev
+        with _device_feature_scale(w.bags, w.scale):
+            hazards, survs, y, att = self.model.forward_window(w.bags, w.omics, inference=self.need_maps)
         if self.loss_name == "sct":
             per_slide, risk = ops.sct_loss(y, w.labels, w.cens), -survs.sum(1)
         else:
@@ -962,58 +1060,40 @@ class CohortEvaluator:
             if self.loss_name == "cesar":
                 per_slide = per_slide + self.lambda_reg * ops.map_block_norm(att["coattn"])
         per_slide = _with_penalty(self.model, per_slide, self.l1)
-        self._loss[w.lo:w.hi].copy_(per_slide.view(-1), non_blocking=True)
-        self._risk[w.lo:w.hi].copy_(risk.view(-1), non_blocking=True)
-        for dst, src in zip(self._heads, (hazards, survs, y)):
-            dst[w.lo:w.hi].copy_(src, non_blocking=True)
+        self._write(w, per_slide.view(-1), risk.view(-1), hazards, survs, y)
         return att["coattn"] if self.need_maps else None
 
-    def _capture(self, pool):
-        dev = self.cohort.device
-        was_training = self.model.training
-        self.model.eval()
-        try:
-            with torch.no_grad():
-                side = torch.cuda.Stream(device=dev)
-                side.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(side):
-                    for w in self.windows:          # allocator, lazy initialisation, every window's own shapes
-                        self._body(w)
-                torch.cuda.current_stream(dev).wait_stream(side)
-                for w in self.windows:
-                    w.graph = torch.cuda.CUDAGraph()
-                    # thread_local: other threads (RCCL's watchdog under torch.distributed) may issue HIP calls meanwhile
-                    with torch.cuda.graph(w.graph, pool=pool, capture_error_mode="thread_local"):
-                        self._body(w)
-                    pool = w.graph.pool() if pool is None else pool
-            self.pool = pool
-        finally:
-            self.model.train(was_training)
+    def _result(self, per_slide, targets) -> EvalResult:
+        loss, risk, hazards, survs, y = per_slide
+        c_index, counts = concordance_index_device(*targets, risk)
+        return EvalResult(loss, risk, hazards, survs, y, loss.mean(0, keepdim=True), c_index, counts)
 
     def __call__(self) -> EvalResult:
         from . import ops
-        maps = None
-        if self.capture:
-            for w in self.windows:
-                w.graph.replay()
-        else:
-            was_training = self.model.training
-            self.model.eval()
-            try:
-                with torch.no_grad():
-                    maps = [self._body(w) for w in self.windows]
-            finally:
-                self.model.train(was_training)
-        loss = self._loss.index_select(0, self.perm)
-        risk = self._risk.index_select(0, self.perm)
-        hazards, survs, y = (t.index_select(0, self.perm) for t in self._heads)
-        c_index, counts = concordance_index_device(self.censorship, self.survival_months, risk)
-        out = EvalResult(loss, risk, hazards, survs, y, loss.mean(0, keepdim=True), c_index, counts)
+        maps = self._run_windows()
+        out = self._result([t.index_select(0, self.perm) for t in self._buffers], self._targets)
         if self.return_maps:
-            per_run = [m for window_maps in maps for m in window_maps]
-            out.maps = [per_run[k] for k in self.perm_host]
+            out.maps = self._in_ids_order(maps)
             out.map_stats = torch.cat([ops.map_block_stats(m) for m in maps]).index_select(0, self.perm)
         return out
+
+
+def _one_shot(evaluator, who: str, model, cohort, ids, options):
+    """validate() / validate_ge(): an eager evaluator of class `evaluator`, built and called once."""
+    if options.get("capture"):
+        raise ValueError(f"{who}: a one-shot evaluation has nothing to replay; build a {evaluator.__name__}(capture=True) and "
+                         "call it every epoch")
+    return evaluator(model, cohort, ids, **options)()
+
+
+def _save_maps(slides, key: str, save_dir, name: str):
+    """test() / test_ge() with save_dir: every slide's slides[.][key] to save_dir/{name}_{id}.pt as a CPU tensor (the copy
+    synchronises), the path into the slide's 'file'."""
+    import os
+    os.makedirs(save_dir, exist_ok=True)
+    for slide in slides:
+        slide["file"] = os.path.join(save_dir, f"{name}_{slide['id']}.pt")
+        torch.save(slide[key].cpu(), slide["file"])
 
 
 def validate(model, cohort: ResidentCohort, ids, **options) -> EvalResult:
@@ -1021,10 +1101,7 @@ def validate(model, cohort: ResidentCohort, ids, **options) -> EvalResult:
     CohortEvaluator(model, cohort, ids, **options) and its call.  No host synchronisation; result.c_index_value() reads
     the C-index.  An epoch loop that validates the same set every epoch keeps one CohortEvaluator instead (its windows,
     and with capture=True its graphs, are built once)."""
-    if options.get("capture"):
-        raise ValueError("validate: a one-shot evaluation has nothing to replay; build a CohortEvaluator(capture=True) and "
-                         "call it every epoch")
-    return CohortEvaluator(model, cohort, ids, **options)()
+    return _one_shot(CohortEvaluator, "validate", model, cohort, ids, options)
 
 
 def test(model, cohort: ResidentCohort, ids, save_dir=None, name: str = "ATTN"):
@@ -1034,17 +1111,14 @@ def test(model, cohort: ResidentCohort, ids, save_dir=None, name: str = "ATTN"):
     and 'coattn' (the (N, M_b) map), all on the device.  Without save_dir nothing is read by the host.  With save_dir
     every slide's map is written with torch.save to save_dir/{name}_{id}.pt (a CPU tensor) and the file's path is the
     dict's 'file': THIS IS THE ONE PLACE THAT SYNCHRONISES -- every map is copied to the host."""
-    import os
-    r = CohortEvaluator(model, cohort, ids, need_maps=True)()
+    ev = CohortEvaluator(model, cohort, ids, need_maps=True)
+    r = ev()
     out = []
-    for k, slide_id in enumerate(ids):
-        out.append({"id": int(slide_id), "hazards": r.hazards[k], "survs": r.survs[k], "Y": r.Y[k], "risk": r.risk[k],
+    for k, slide_id in enumerate(ev.ids):
+        out.append({"id": slide_id, "hazards": r.hazards[k], "survs": r.survs[k], "Y": r.Y[k], "risk": r.risk[k],
                     "attn_stats": r.map_stats[k], "coattn": r.maps[k]})
     if save_dir is not None:
-        os.makedirs(save_dir, exist_ok=True)
-        for slide in out:
-            slide["file"] = os.path.join(save_dir, f"{name}_{slide['id']}.pt")
-            torch.save(slide["coattn"].cpu(), slide["file"])
+        _save_maps(out, "coattn", save_dir, name)
     return out
 
 
@@ -1116,7 +1190,7 @@ def classification_metrics_device(y, label, loss=None, want_pred: bool = True):
                              None if loss is None else loss.detach().reshape(-1).to(torch.float32).contiguous(), want_pred)
 
 
-class GeResidentCohort:
+class GeResidentCohort(_ResidentRows):
     """ResidentCohort for the gene-expression model: every slide's rows on the device once, in the same storage -- slabs of at
     most `slab_bytes`, a slide never split; `rows`, `lengths`, `slab_index`, `row_offset`, the pointer / length table
     (`table_ptrs`, `table_lens`), `cycle`, `n_slides` -- and `labels` (N,) int64 on the device.
@@ -1124,26 +1198,15 @@ class GeResidentCohort:
     (captured like bf16: no feature scale) or fp32 (a step captured with device_feature_scale=True)."""
 
     def __init__(self, slides: Sequence[dict], device, bag_dtype=torch.bfloat16, cycle: bool = False, slab_bytes: int = 1 << 30):
-        self.device, self.cycle = torch.device(device), bool(cycle)
-        _cohort_slabs(self, "GeResidentCohort", slides, bag_dtype, slab_bytes)
-        self.table_ptrs, self.table_lens = SlideSet.slide_table(self.rows)
+        super().__init__(slides, device, bag_dtype, cycle, slab_bytes)
         self.labels = torch.tensor([int(s["gene_expr_class"]) for s in slides], dtype=torch.int64).to(self.device, non_blocking=True)
-
-    @property
-    def n_slides(self):
-        return len(self.lengths)
 
     def window(self, ids_dev, ids_host, out=None):
         """(SlideSet, labels) for the slides `ids_host` (host ints) = `ids_dev` (DEVICE int32, the same values): the tuple a
         gene-expression step takes.  The labels are selected on the device, into `out` = (labels,) where given (a captured
         step's static tensor, step.window[1:]).  No H2D copy and no host synchronisation; what ResidentCohort.window says
         about the two copies of the ids and about `out` holds here."""
-        ids_host = [int(i) for i in ids_host]
-        for i in ids_host:
-            if not 0 <= i < self.n_slides:
-                raise ValueError(f"GeResidentCohort.window: slide id {i} outside the cohort's {self.n_slides} slides")
-        bags = SlideSet([self.rows[i] for i in ids_host], [self.lengths[i] for i in ids_host], self.table_ptrs, self.table_lens,
-                        ids_dev, self.cycle)
+        bags = self._slide_set(ids_dev, ids_host)
         return bags, torch.index_select(self.labels, 0, ids_dev, out=None if out is None else out[0])
 
 
@@ -1165,28 +1228,9 @@ def train_ge_epoch(step: "GraphedWindowStep", cohort: GeResidentCohort, order):
                          "GeResidentCohort window")
     if not isinstance(cohort, GeResidentCohort):
         raise ValueError(f"train_ge_epoch: a GeResidentCohort holds the gene-expression layout, not a {type(cohort).__name__}")
-    n, k = step.sampler.n_slides, step.sampler.k
-    if (int(cohort.rows[0].shape[1]), cohort.rows[0].dtype) != (step.sampler.width, step.sampler.dtype):
-        raise ValueError(f"train_ge_epoch: the cohort's rows are {int(cohort.rows[0].shape[1])} x {cohort.rows[0].dtype}, the step "
-                         f"was captured for {step.sampler.width} x {step.sampler.dtype}")
-    order = [int(i) for i in order]
-    for i in order:
-        if not 0 <= i < cohort.n_slides:
-            raise ValueError(f"train_ge_epoch: slide id {i} outside the cohort's {cohort.n_slides} slides")
-        if not cohort.cycle and cohort.lengths[i] < k:
-            raise ValueError(f"train_ge_epoch: slide {i} has {cohort.lengths[i]} rows, fewer than k = {k}, and the cohort does not "
-                             "lap short slides (cycle=False)")
-    n_win = len(order) // n
-    leftover = order[n_win * n:]
-    dev = cohort.device
-    order_dev = torch.tensor(order[:n_win * n], dtype=torch.int32).to(dev, non_blocking=True)
-    loss = torch.empty(n_win * n, dtype=torch.float32, device=dev)
-    static = step.window[1:]
-    for w in range(n_win):
-        lo, hi = w * n, (w + 1) * n
-        step.bind(cohort.window(order_dev[lo:hi], order[lo:hi], out=static))
-        loss[lo:hi].copy_(step().view(-1), non_blocking=True)
-    return loss, order_dev, leftover
+    order = _check_epoch_order("train_ge_epoch", step, cohort, order)
+    loss, _, ids_run, leftover = _run_epoch(step, cohort, order, len(order) // step.sampler.n_slides)
+    return loss, ids_run, leftover
 
 
 @dataclass
@@ -1213,7 +1257,7 @@ class GeEvalResult:
         return float(self.accuracy)
 
 
-class GeCohortEvaluator:
+class GeCohortEvaluator(_WindowEvaluator):
     """CohortEvaluator for the gene-expression model: the reference's validate() (models/ge_nacagat/main.py:85-119) -- eval
     mode, no gradients, per-slide `ce` loss and Y, accuracy over the set -- over slides of a GeResidentCohort with nothing
     copied and nothing read by the host.
@@ -1235,9 +1279,10 @@ class GeCohortEvaluator:
     need_paths (eager only; test_ge() sets it): the result carries every slide's (1, M_b) pooling attention and
     ops.map_block_stats of it (n_q = 1)."""
 
+    PER_SLIDE = ("loss", "Y")
+
     def __init__(self, model, cohort: GeResidentCohort, ids, l1: float = 0.0, max_window_rows: int = 1 << 19,
                  max_window_slides: int = 32, capture: bool = False, pool=None, need_paths: bool = False):
-        from . import ops
         from .models import GeneExprNarrowContextualAttentionGateTransformer
         if not isinstance(model, GeneExprNarrowContextualAttentionGateTransformer):
             raise ValueError(f"GeCohortEvaluator: {type(model).__name__} is not the gene-expression model; a survival model's "
@@ -1248,82 +1293,42 @@ class GeCohortEvaluator:
             raise ValueError("GeCohortEvaluator(capture=True): need_paths returns the pooling attention map, an output of the "
                              "forward whose size follows the window: the captured evaluator keeps no map -- run it eagerly "
                              "(capture=False)")
-        self.model, self.cohort, self.l1 = model, cohort, float(l1)
-        self.need_paths, self.capture = bool(need_paths), bool(capture)
-        self.ids = [int(i) for i in ids]
-        runs, perm = cut_eval_windows(self.ids, cohort.lengths, cohort.slab_index, max_window_rows, max_window_slides)
+        self.l1, self.need_paths = float(l1), bool(need_paths)
+        super().__init__(model, cohort, ids, max_window_rows, max_window_slides, capture, pool)
+
+    def _set_up(self, ids_dev):
+        cohort, model, dev, n = self.cohort, self.model, self.cohort.device, len(self.ids)
         for i in self.ids:
             if cohort.lengths[i] < model.MIN_WINDOW_ROWS:
                 raise ValueError(f"GeCohortEvaluator: slide {i} has {cohort.lengths[i]} rows, fewer than the {model.MIN_WINDOW_ROWS} "
                                  "the gene-expression model's window forward needs (shorter bags go through forward())")
-        dev = cohort.device
-        n = len(self.ids)
-        self.perm_host = perm
-        self.perm = torch.tensor(perm, dtype=torch.int64).to(dev, non_blocking=True)
-        self.labels = cohort.labels.index_select(0, torch.tensor(self.ids, dtype=torch.int64).to(dev, non_blocking=True))
-        weight = model.H[0].weight
-        if weight.device != cohort.labels.device:
-            raise ValueError(f"GeCohortEvaluator: the model lies on {weight.device}, the cohort on {dev}")
-        self.windows, lo = [], 0
-        for run in runs:
-            w = _EvalWindow()
-            w.ids, w.lo, w.hi = run, lo, lo + len(run)
-            lo = w.hi
-            lengths = [cohort.lengths[i] for i in run]
-            w.bags = _slab_window(cohort.slabs[cohort.slab_index[run[0]]], cohort.row_offset[run[0]], lengths)
-            w.labels = cohort.labels.index_select(0, torch.tensor(run, dtype=torch.int64).to(dev, non_blocking=True))
-            w.omics = w.cens = w.scale = w.graph = None
-            if dev.type == "cuda":
-                w.bags.plan()                   # (its H2D copy happens here, never inside a call or a capture)
-                if ops.patch_fc_f32_supported(w.bags.data, weight):
-                    w.scale = torch.ones(1, dtype=torch.float32, device=dev)
-            self.windows.append(w)
-        # results in run order: every window writes its rows, one permutation per tensor puts them into `ids` order
-        self._loss = torch.empty(n, dtype=torch.float32, device=dev)
-        self._y = torch.empty(n, int(model.classifier.out_features), dtype=torch.float32, device=dev)
-        self.pool = pool
-        if self.capture:
-            self._capture(pool)
+        self.labels = cohort.labels.index_select(0, ids_dev)
+        self._targets = (self.labels,)
+        self._buffers = [torch.empty(n, dtype=torch.float32, device=dev),
+                         torch.empty(n, int(model.classifier.out_features), dtype=torch.float32, device=dev)]
+
+    def _select(self, w, run_dev):
+        w.labels = self.cohort.labels.index_select(0, run_dev)
 
     def _body(self, w):
         """forward + loss of one window into the run-order buffers -> the window's pooling attentions (a list of (1, M_b))."""
-        from . import ops
-        bags = w.bags
-        if w.scale is not None:
-            bags.data._mpo_feature_scale_dev = ops.feature_scale_device(bags.data, out=w.scale)
-        try:
-            targets = (w.labels, _slide_weights(bags.n_slides, 1, w.labels.device))
-            y, att = self.model.forward_window(bags, need_maps=False, ce_targets=targets)
-        finally:
-            if w.scale is not None:
-                del bags.data._mpo_feature_scale_dev
-        self._loss[w.lo:w.hi].copy_(_with_penalty(self.model, att["loss"], self.l1).view(-1), non_blocking=True)
-        self._y[w.lo:w.hi].copy_(y, non_blocking=True)
+        with _device_feature_scale(w.bags, w.scale):
+            targets = (w.labels, _slide_weights(w.bags.n_slides, 1, w.labels.device))
+            y, att = self.model.forward_window(w.bags, need_maps=False, ce_targets=targets)
+        self._write(w, _with_penalty(self.model, att["loss"], self.l1).view(-1), y)
         return att["path"]
 
-    _capture = CohortEvaluator._capture
+    def _result(self, per_slide, targets) -> GeEvalResult:
+        loss, y = per_slide
+        pred, confusion, counts, summary = classification_metrics_device(y, targets[0], loss)
+        return GeEvalResult(loss, y, pred, confusion, counts, summary[2:3], summary[0:1], summary[1:2])
 
     def __call__(self) -> GeEvalResult:
         from . import ops
-        paths = None
-        if self.capture:
-            for w in self.windows:
-                w.graph.replay()
-        else:
-            was_training = self.model.training
-            self.model.eval()
-            try:
-                with torch.no_grad():
-                    paths = [self._body(w) for w in self.windows]
-            finally:
-                self.model.train(was_training)
-        loss = self._loss.index_select(0, self.perm)
-        y = self._y.index_select(0, self.perm)
-        pred, confusion, counts, summary = classification_metrics_device(y, self.labels, loss)
-        out = GeEvalResult(loss, y, pred, confusion, counts, summary[2:3], summary[0:1], summary[1:2])
+        paths = self._run_windows()
+        out = self._result([t.index_select(0, self.perm) for t in self._buffers], self._targets)
         if self.need_paths:
-            per_run = [p for window_paths in paths for p in window_paths]
-            out.paths = [per_run[k] for k in self.perm_host]
+            out.paths = self._in_ids_order(paths)
             stats = [ops.map_block_stats(w.bags.split_map(torch.cat([p.reshape(-1) for p in window_paths]), 1))
                      for w, window_paths in zip(self.windows, paths)]
             out.path_stats = torch.cat(stats).index_select(0, self.perm)
@@ -1335,10 +1340,7 @@ def validate_ge(model, cohort: GeResidentCohort, ids, **options) -> GeEvalResult
     cohort: a one-shot eager GeCohortEvaluator(model, cohort, ids, **options) and its call.  No host synchronisation;
     result.accuracy_value() reads the accuracy.  An epoch loop that validates the same set every epoch keeps one
     GeCohortEvaluator instead."""
-    if options.get("capture"):
-        raise ValueError("validate_ge: a one-shot evaluation has nothing to replay; build a GeCohortEvaluator(capture=True) and "
-                         "call it every epoch")
-    return GeCohortEvaluator(model, cohort, ids, **options)()
+    return _one_shot(GeCohortEvaluator, "validate_ge", model, cohort, ids, options)
 
 
 def test_ge(model, cohort: GeResidentCohort, ids, save_dir=None, name: str = "ATTN"):
@@ -1348,7 +1350,6 @@ def test_ge(model, cohort: GeResidentCohort, ids, save_dir=None, name: str = "AT
     pooling attention), all on the device.  Without save_dir nothing is read by the host.  With save_dir every slide's path
     is written with torch.save to save_dir/{name}_{id}.pt (a CPU tensor) and the file's path is the dict's 'file': THIS IS
     THE ONE PLACE THAT SYNCHRONISES."""
-    import os
     ev = GeCohortEvaluator(model, cohort, ids, need_paths=True)
     r = ev()
     out = []
@@ -1356,10 +1357,7 @@ def test_ge(model, cohort: GeResidentCohort, ids, save_dir=None, name: str = "AT
         out.append({"id": slide_id, "Y": r.Y[k], "pred": r.pred[k], "label": ev.labels[k], "attn_stats": r.path_stats[k],
                     "path": r.paths[k]})
     if save_dir is not None:
-        os.makedirs(save_dir, exist_ok=True)
-        for slide in out:
-            slide["file"] = os.path.join(save_dir, f"{name}_{slide['id']}.pt")
-            torch.save(slide["path"].cpu(), slide["file"])
+        _save_maps(out, "path", save_dir, name)
     return out
 
 
@@ -1367,22 +1365,6 @@ test_ge.__test__ = False
 
 
 # ------------------------------------------------------------------------------------ data-parallel epochs (one process per GPU)
-def _check_epoch_order(who: str, step, cohort, order) -> "List[int]":
-    """train_epoch's validation of a whole order -- the cohort's layout against the step's capture, every id in range, every
-    slide at least k rows unless the cohort laps -- before anything runs."""
-    if (int(cohort.rows[0].shape[1]), cohort.rows[0].dtype) != (step.sampler.width, step.sampler.dtype):
-        raise ValueError(f"{who}: the cohort's rows are {int(cohort.rows[0].shape[1])} x {cohort.rows[0].dtype}, the step was "
-                         f"captured for {step.sampler.width} x {step.sampler.dtype}")
-    order, k = [int(i) for i in order], step.sampler.k
-    for i in order:
-        if not 0 <= i < cohort.n_slides:
-            raise ValueError(f"{who}: slide id {i} outside the cohort's {cohort.n_slides} slides")
-        if not cohort.cycle and cohort.lengths[i] < k:
-            raise ValueError(f"{who}: slide {i} has {cohort.lengths[i]} rows, fewer than k = {k}, and the cohort does not lap "
-                             "short slides (cycle=False)")
-    return order
-
-
 def train_epoch_dp(step: "GraphedWindowStep", cohort, order, opt, n_windows: int, group=None):
     """One rank's share of a data-parallel epoch: train_epoch / train_ge_epoch with the gradient exchange and the optimiser
     between the replays.  The plan is dp's: shards = shard_slides(lengths, world); this rank's `cohort` is a ResidentCohort
@@ -1434,17 +1416,9 @@ def train_epoch_dp(step: "GraphedWindowStep", cohort, order, opt, n_windows: int
     world = dp._world(group)
     bucket = step.bucket
     head = step.head_numel() if step.split else None
-    leftover = order[n_win * n:]
-    dev = cohort.device
-    order_dev = torch.tensor(order[:n_win * n], dtype=torch.int32).to(dev, non_blocking=True)
-    loss = torch.empty(n_win * n, dtype=torch.float32, device=dev)
-    risk = None if step.ge else torch.empty(n_win * n, dtype=torch.float32, device=dev)
-    static = step.window[1:]
     folds_l1 = bool(getattr(opt, "l1_lambda", 0.0))
-    for w in range(n_win):
-        lo, hi = w * n, (w + 1) * n
-        step.bind(cohort.window(order_dev[lo:hi], order[lo:hi], out=static))
-        out = step()
+
+    def exchange_and_step():
         if step.split:
             rest = bucket.all_reduce_mean_async(lo=head, group=group)
             step.replay_tail()
@@ -1458,12 +1432,8 @@ def train_epoch_dp(step: "GraphedWindowStep", cohort, order, opt, n_windows: int
             opt.step(l1_slides=n * world)
         else:
             opt.step()
-        if step.ge:
-            loss[lo:hi].copy_(out.view(-1), non_blocking=True)
-        else:
-            loss[lo:hi].copy_(out[0].view(-1), non_blocking=True)
-            risk[lo:hi].copy_(out[1].view(-1), non_blocking=True)
-    return (loss, order_dev, leftover) if step.ge else (loss, risk, order_dev, leftover)
+    loss, risk, ids_run, leftover = _run_epoch(step, cohort, order, n_win, exchange_and_step)
+    return (loss, ids_run, leftover) if step.ge else (loss, risk, ids_run, leftover)
 
 
 def epoch_c_index_dp(cohort: ResidentCohort, ids_run, risk, group=None):
@@ -1500,10 +1470,5 @@ def validate_dp(evaluator, sizes, group=None):
 
     def gather(t):
         return dp.gather_ragged(t, sizes, group)
-    if isinstance(evaluator, GeCohortEvaluator):
-        loss, y, labels = gather(r.loss), gather(r.Y), gather(evaluator.labels)
-        pred, confusion, counts, summary = classification_metrics_device(y, labels, loss)
-        return GeEvalResult(loss, y, pred, confusion, counts, summary[2:3], summary[0:1], summary[1:2])
-    loss, risk, hazards, survs, y = (gather(t) for t in (r.loss, r.risk, r.hazards, r.survs, r.Y))
-    c_index, counts = concordance_index_device(gather(evaluator.censorship), gather(evaluator.survival_months), risk)
-    return EvalResult(loss, risk, hazards, survs, y, loss.mean(0, keepdim=True), c_index, counts)
+    per_slide = [gather(getattr(r, name)) for name in evaluator.PER_SLIDE]
+    return evaluator._result(per_slide, [gather(t) for t in evaluator._targets])
