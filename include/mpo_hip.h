@@ -125,7 +125,7 @@ int mpo_patch_fc_forward(const void* patches, const int32_t* cu_rows, int n_slid
                          void* workspace, size_t workspace_bytes, mpo_stream_t stream);
 /* The patch layer of an fp32-stored window (models/mcat/mcat.py:24-29,87 with fp32 patch features; ABI v11, x_scale: v13), 1024 -> 256:
  *   forward   H_bag = Dropout(ReLU(X W^T + b)) in fp32 storage; products as three fp16 MFMA terms of hi / lo operand splits with fp32
- *             accumulation (csrc/patch_fc_f32.hip).  Dropout: counter hash, 8 bits per element (realised p = round(256 p) / 256);
+ *             accumulation (csrc/patch_fc_split.hip).  Dropout: counter hash, 8 bits per element (realised p = round(256 p) / 256);
  *             the mask lives in H_bag as zeros.  x_scale: a power of two applied to X before its split and taken off the
  *             accumulator (exact); pass 2^(15 - e) for max |X| = m 2^e, m in [0.5, 1) (ops.patch_fc_f32 derives and caches it
  *             per tensor) so that the features use fp16's range; 1.0 = unscaled (|x| in ~[1e-3, 1.3e5] then).  W_H is scaled
@@ -562,7 +562,7 @@ int mpo_coattn_bwd_bagpass(const void* bag, int bag_dtype, const int32_t* cu_row
 /* ---- patch sampling from a cohort resident on the device (csrc/bag_sample.hip, the same gather): likewise additive to ABI 14. */
 #include "mpo_cohort.h"
 
-/* ---- an fp32 window's feature scale found and read on the device (csrc/feature_range.hip, csrc/patch_fc_f32.hip): likewise
+/* ---- an fp32 window's feature scale found and read on the device (csrc/feature_range.hip, csrc/patch_fc_split.hip): likewise
  * additive to ABI 14. */
 #include "mpo_feature_range.h"
 
@@ -578,7 +578,7 @@ int mpo_coattn_bwd_bagpass(const void* bag, int bag_dtype, const int32_t* cu_row
  * (csrc/class_metrics.hip): likewise additive to ABI 14. */
 #include "mpo_classify.h"
 
-/* ---- the patch layer of an fp16-stored window (csrc/patch_fc_f16.hip): likewise additive to ABI 14. */
+/* ---- the patch layer of an fp16-stored window (csrc/patch_fc_split.hip): likewise additive to ABI 14. */
 #include "mpo_patch_f16.h"
 
 #ifdef __cplusplus

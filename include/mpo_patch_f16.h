@@ -11,7 +11,7 @@ extern "C" {
 #endif
 
 /* mpo_patch_fc_f32_forward / _backward for a window whose patch features are stored in fp16 (models/mcat/mcat.py:24-29,87 with
- * fp16 patch features), 1024 -> 256 (csrc/patch_fc_f16.hip):
+ * fp16 patch features), 1024 -> 256 (csrc/patch_fc_split.hip):
  *   forward   H_bag = Dropout(ReLU(X W^T + b)) in fp32 storage, X [total_rows][1024] fp16.  An fp16 feature is one fp16 MFMA
  *             operand as it is stored, so there is NO feature scale and no split of X: products as two fp16 MFMA terms
  *             W_hi X + W_lo X with fp32 accumulation (W_H scaled by its own maximum inside the call and split, as in the fp32

@@ -267,53 +267,12 @@ int mpo_patch_fc_forward(const void* patches, const int32_t* cu_rows, int n_slid
                                    reinterpret_cast<const unsigned long long*>(rng_epoch), plan, stream);
 }
 
-// fp32-stored window: the patch layer on patch_fc_f32.hip
+// fp32- and fp16-stored windows: the patch layer on patch_fc_split.hip.  One helper per direction behind both windows' entries;
+// the fp16 entries are the fp32 ones without a feature scale, their rate an integer.
 size_t mpo_patch_fc_f32_workspace_bytes(int backward) {
-    return one_block_workspace_bytes(backward ? mpo_patch_wgrad_f32_workspace_floats() : mpo_patch_fc_f32_workspace_floats());
+    return one_block_workspace_bytes(backward ? mpo_patch_wgrad_split_workspace_floats() : mpo_patch_fc_split_workspace_floats());
 }
-// x_scale by value, or (x_scale_dev non-NULL) read on the device when the kernel starts: one kernel, the same bits
-static int patch_fc_f32_forward(const float* patches, int64_t total_rows, int patch_dim, const float* patch_weight,
-                                const float* patch_bias, int embed, float drop_p, uint64_t seed, uint64_t offset,
-                                const uint64_t* rng_epoch, float x_scale, const float* x_scale_dev, float* h_bag, void* workspace,
-                                size_t workspace_bytes, mpo_stream_t stream) {
-    MPO_CHECK(patches && patch_weight && patch_bias && h_bag, "fp32 patch layer: null operand");
-    MPO_CHECK(total_rows >= 1, "fp32 patch layer: total_rows %lld", (long long)total_rows);
-    WsCarve ws(workspace, workspace_bytes);
-    float* wpk = ws.floats(mpo_patch_fc_f32_workspace_floats());
-    MPO_CHECK(ws.ok(), "fp32 patch layer: workspace too small (%zu bytes)", workspace_bytes);
-    return mpo_launch_patch_fc_f32(patches, patch_weight, patch_bias, h_bag, total_rows, embed, patch_dim, drop_p, seed, offset,
-                                   reinterpret_cast<const unsigned long long*>(rng_epoch), x_scale, x_scale_dev, wpk, stream);
-}
-int mpo_patch_fc_f32_forward(const float* patches, int64_t total_rows, int patch_dim, const float* patch_weight,
-                             const float* patch_bias, int embed, float drop_p, uint64_t seed, uint64_t offset,
-                             const uint64_t* rng_epoch, float x_scale, float* h_bag, void* workspace, size_t workspace_bytes,
-                             mpo_stream_t stream) {
-    return patch_fc_f32_forward(patches, total_rows, patch_dim, patch_weight, patch_bias, embed, drop_p, seed, offset, rng_epoch,
-                                x_scale, nullptr, h_bag, workspace, workspace_bytes, stream);
-}
-int mpo_patch_fc_f32_forward_dev(const float* patches, int64_t total_rows, int patch_dim, const float* patch_weight,
-                                 const float* patch_bias, int embed, float drop_p, uint64_t seed, uint64_t offset,
-                                 const uint64_t* rng_epoch, const float* x_scale, float* h_bag, void* workspace,
-                                 size_t workspace_bytes, mpo_stream_t stream) {
-    MPO_CHECK(x_scale, "fp32 patch layer: null device scale (mpo_feature_range_f32 writes it)");
-    return patch_fc_f32_forward(patches, total_rows, patch_dim, patch_weight, patch_bias, embed, drop_p, seed, offset, rng_epoch,
-                                1.0f, x_scale, h_bag, workspace, workspace_bytes, stream);
-}
-int mpo_patch_fc_f32_backward(const float* d_h_bag, const float* h_bag, const float* patches, int64_t total_rows, int embed,
-                              int patch_dim, float gate, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes,
-                              mpo_stream_t stream) {
-    MPO_CHECK(d_h_bag && patches && d_weight, "fp32 patch layer backward: null operand");
-    MPO_CHECK(total_rows >= 1, "fp32 patch layer backward: total_rows %lld", (long long)total_rows);
-    WsCarve ws(workspace, workspace_bytes);
-    float* part = ws.floats(mpo_patch_wgrad_f32_workspace_floats());
-    MPO_CHECK(ws.ok(), "fp32 patch layer backward: workspace too small (%zu bytes)", workspace_bytes);
-    return mpo_launch_patch_wgrad_f32(d_h_bag, h_bag, patches, total_rows, embed, patch_dim, gate, d_weight, d_bias, part, stream);
-}
-
-// fp16-stored window: the patch layer on patch_fc_f16.hip (the fp32 window's entries without a feature scale)
-size_t mpo_patch_fc_f16_workspace_bytes(int backward) {
-    return one_block_workspace_bytes(backward ? mpo_patch_wgrad_f16x_workspace_floats() : mpo_patch_fc_f16_workspace_floats());
-}
+size_t mpo_patch_fc_f16_workspace_bytes(int backward) { return mpo_patch_fc_f32_workspace_bytes(backward); }
 // drop_256 = round(256 p) -> the p the launcher rounds back to that integer (exact: 256ths); refusals in the fp32 entry's words
 static int patch_f16_rate(int drop_256, float* p) {
     *p = (float)drop_256 / 256.0f;
@@ -322,31 +281,71 @@ static int patch_f16_rate(int drop_256, float* p) {
               "nothing would be kept (p must be below 1 - 1/512)", (double)*p, (unsigned)drop_256);
     return 0;
 }
+// x_f16: an fp16 window -- the rate is drop_256 (drop_p is not read) and there is no feature scale.  An fp32 window: drop_p, and
+// x_scale by value or (x_scale_dev non-NULL) read on the device when the kernel starts: one kernel, the same bits.
+static int patch_split_forward(const void* patches, bool x_f16, int64_t total_rows, int patch_dim, const float* patch_weight,
+                               const float* patch_bias, int embed, float drop_p, int drop_256, uint64_t seed, uint64_t offset,
+                               const uint64_t* rng_epoch, float x_scale, const float* x_scale_dev, float* h_bag, void* workspace,
+                               size_t workspace_bytes, mpo_stream_t stream) {
+    const char* window = x_f16 ? "fp16" : "fp32";
+    MPO_CHECK(patches && patch_weight && patch_bias && h_bag, "%s patch layer: null operand", window);
+    if (x_f16) RC(patch_f16_rate(drop_256, &drop_p));
+    MPO_CHECK(total_rows >= 1, "%s patch layer: total_rows %lld", window, (long long)total_rows);
+    WsCarve ws(workspace, workspace_bytes);
+    float* wpk = ws.floats(mpo_patch_fc_split_workspace_floats());
+    MPO_CHECK(ws.ok(), "%s patch layer: workspace too small (%zu bytes)", window, workspace_bytes);
+    return mpo_launch_patch_fc_split(patches, x_f16, patch_weight, patch_bias, h_bag, total_rows, embed, patch_dim, drop_p, seed, offset,
+                                     reinterpret_cast<const unsigned long long*>(rng_epoch), x_scale, x_scale_dev, wpk, stream);
+}
+// x_f16: the gate is formed from drop_256 (gate is not read)
+static int patch_split_backward(const float* d_h_bag, const float* h_bag, const void* patches, bool x_f16, int64_t total_rows,
+                                int embed, int patch_dim, float gate, int drop_256, float* d_weight, float* d_bias,
+                                void* workspace, size_t workspace_bytes, mpo_stream_t stream) {
+    const char* window = x_f16 ? "fp16" : "fp32";
+    MPO_CHECK(d_h_bag && patches && d_weight, "%s patch layer backward: null operand", window);
+    if (x_f16) {
+        float drop_p;
+        RC(patch_f16_rate(drop_256, &drop_p));
+        gate = 256.0f / (256.0f - (float)drop_256);                  // (the forward kernel's inv_keep; 1 at drop_256 = 0)
+    }
+    MPO_CHECK(total_rows >= 1, "%s patch layer backward: total_rows %lld", window, (long long)total_rows);
+    WsCarve ws(workspace, workspace_bytes);
+    float* part = ws.floats(mpo_patch_wgrad_split_workspace_floats());
+    MPO_CHECK(ws.ok(), "%s patch layer backward: workspace too small (%zu bytes)", window, workspace_bytes);
+    return mpo_launch_patch_wgrad_split(d_h_bag, h_bag, patches, x_f16, total_rows, embed, patch_dim, gate, d_weight, d_bias, part, stream);
+}
+int mpo_patch_fc_f32_forward(const float* patches, int64_t total_rows, int patch_dim, const float* patch_weight,
+                             const float* patch_bias, int embed, float drop_p, uint64_t seed, uint64_t offset,
+                             const uint64_t* rng_epoch, float x_scale, float* h_bag, void* workspace, size_t workspace_bytes,
+                             mpo_stream_t stream) {
+    return patch_split_forward(patches, false, total_rows, patch_dim, patch_weight, patch_bias, embed, drop_p, 0, seed, offset, rng_epoch,
+                               x_scale, nullptr, h_bag, workspace, workspace_bytes, stream);
+}
+int mpo_patch_fc_f32_forward_dev(const float* patches, int64_t total_rows, int patch_dim, const float* patch_weight,
+                                 const float* patch_bias, int embed, float drop_p, uint64_t seed, uint64_t offset,
+                                 const uint64_t* rng_epoch, const float* x_scale, float* h_bag, void* workspace,
+                                 size_t workspace_bytes, mpo_stream_t stream) {
+    MPO_CHECK(x_scale, "fp32 patch layer: null device scale (mpo_feature_range_f32 writes it)");
+    return patch_split_forward(patches, false, total_rows, patch_dim, patch_weight, patch_bias, embed, drop_p, 0, seed, offset, rng_epoch,
+                               1.0f, x_scale, h_bag, workspace, workspace_bytes, stream);
+}
+int mpo_patch_fc_f32_backward(const float* d_h_bag, const float* h_bag, const float* patches, int64_t total_rows, int embed,
+                              int patch_dim, float gate, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes,
+                              mpo_stream_t stream) {
+    return patch_split_backward(d_h_bag, h_bag, patches, false, total_rows, embed, patch_dim, gate, 0, d_weight, d_bias, workspace,
+                                workspace_bytes, stream);
+}
 int mpo_patch_fc_f16_forward(const void* patches, int64_t total_rows, int patch_dim, const float* patch_weight,
                              const float* patch_bias, int embed, int drop_256, uint64_t seed, uint64_t offset,
                              const uint64_t* rng_epoch, float* h_bag, void* workspace, size_t workspace_bytes, mpo_stream_t stream) {
-    MPO_CHECK(patches && patch_weight && patch_bias && h_bag, "fp16 patch layer: null operand");
-    float drop_p;
-    RC(patch_f16_rate(drop_256, &drop_p));
-    MPO_CHECK(total_rows >= 1, "fp16 patch layer: total_rows %lld", (long long)total_rows);
-    WsCarve ws(workspace, workspace_bytes);
-    float* wpk = ws.floats(mpo_patch_fc_f16_workspace_floats());
-    MPO_CHECK(ws.ok(), "fp16 patch layer: workspace too small (%zu bytes)", workspace_bytes);
-    return mpo_launch_patch_fc_f16(patches, patch_weight, patch_bias, h_bag, total_rows, embed, patch_dim, drop_p, seed, offset,
-                                   reinterpret_cast<const unsigned long long*>(rng_epoch), wpk, stream);
+    return patch_split_forward(patches, true, total_rows, patch_dim, patch_weight, patch_bias, embed, 0.f, drop_256, seed, offset, rng_epoch,
+                               1.0f, nullptr, h_bag, workspace, workspace_bytes, stream);
 }
 int mpo_patch_fc_f16_backward(const float* d_h_bag, const float* h_bag, const void* patches, int64_t total_rows, int embed,
                               int patch_dim, int drop_256, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes,
                               mpo_stream_t stream) {
-    MPO_CHECK(d_h_bag && patches && d_weight, "fp16 patch layer backward: null operand");
-    float drop_p;
-    RC(patch_f16_rate(drop_256, &drop_p));
-    const float gate = 256.0f / (256.0f - (float)drop_256);          // (the forward kernel's inv_keep; 1 at drop_256 = 0)
-    MPO_CHECK(total_rows >= 1, "fp16 patch layer backward: total_rows %lld", (long long)total_rows);
-    WsCarve ws(workspace, workspace_bytes);
-    float* part = ws.floats(mpo_patch_wgrad_f16x_workspace_floats());
-    MPO_CHECK(ws.ok(), "fp16 patch layer backward: workspace too small (%zu bytes)", workspace_bytes);
-    return mpo_launch_patch_wgrad_f16x(d_h_bag, h_bag, patches, total_rows, embed, patch_dim, gate, d_weight, d_bias, part, stream);
+    return patch_split_backward(d_h_bag, h_bag, patches, true, total_rows, embed, patch_dim, 1.0f, drop_256, d_weight, d_bias, workspace,
+                                workspace_bytes, stream);
 }
 
 // the patch layer's bag pass alone, and with the co-attention's partial pass behind it (bench.py's roofline leg, profiling workloads)

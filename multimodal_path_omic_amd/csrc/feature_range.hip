@@ -1,5 +1,5 @@
 // The feature scale of an fp32 window, found on the device: *scale_out = range_scale(max |x|) (mpo_common.h), the power of two
-// patch_fc_f32.hip multiplies X by before its fp16 operand split.  ops.feature_scale forms the same number on the host
+// patch_fc_split.hip multiplies X by before its fp16 operand split.  ops.feature_scale forms the same number on the host
 // (a full-size |x| temporary, a library reduction, a blocking read) and hands it over by value, which a captured step bakes
 // in; this pass leaves it in device memory, where patch_fc_f32_kernel reads it when it starts -- as it reads W_H's.
 //

@@ -46,7 +46,7 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
 __device__ __forceinline__ float relu_keep_nan(float v) { return __builtin_elementwise_maximum(v, 0.f); }
 __device__ __forceinline__ float clamp_min_keep_nan(float v, float lo) { return v < lo ? lo : v; }
 // The power of two that puts max |v| into [2^14, 2^15) (1 for an all-zero or non-finite maximum): the scale the fp16 operand
-// splits of patch_fc_f32.hip take for W_H and for X (feature_range.hip).
+// splits of patch_fc_split.hip take for W_H and for X (feature_range.hip).
 __device__ __forceinline__ float range_scale(float vmax) {
     if (!(vmax > 0.f) || !(vmax < INFINITY)) return 1.0f;
     int e;

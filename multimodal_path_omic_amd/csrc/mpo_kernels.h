@@ -168,24 +168,17 @@ int mpo_coattn_bwd8_enable(int enabled);   // returns the previous setting
 int mpo_launch_coattn_bwd8(const void* bag, const int* cu, const float* qk2, const float* lse2, const float* dctx,
                            const float* delta, const float* ctx, void* dbag, float* part_dqk, float* part_colsum, int n_q,
                            const BagPlan& plan, float relu_gate, hipStream_t stream);
-// fp32-stored window: the patch layer as three-term bf16 products (patch_fc_f32.hip); ws = the *_workspace_floats() below
-size_t mpo_patch_fc_f32_workspace_floats();
-size_t mpo_patch_wgrad_f32_workspace_floats();
-int mpo_launch_patch_fc_f32(const float* x, const float* w, const float* bias, float* h, long long total_rows, int embed,
-                            int patch_dim, float drop_p, unsigned long long seed, unsigned long long offset,
-                            const unsigned long long* epoch, float x_scale, const float* x_scale_dev /* nullable: DEVICE, read at run time in place of x_scale */,
-                            float* ws, hipStream_t stream);
-int mpo_launch_patch_wgrad_f32(const float* dh, const float* hbag, const float* x, long long total_rows, int embed, int patch_dim,
-                               float gate, float* d_weight, float* d_bias, float* ws, hipStream_t stream);
-// fp16-stored window: the patch layer as two-term fp16 products, its weight gradient as three-term bf16 products
-// (patch_fc_f16.hip); x: fp16 [total_rows][1024]; ws = the *_workspace_floats() below (the fp32 window's sizes)
-size_t mpo_patch_fc_f16_workspace_floats();
-size_t mpo_patch_wgrad_f16x_workspace_floats();
-int mpo_launch_patch_fc_f16(const void* x, const float* w, const float* bias, float* h, long long total_rows, int embed,
-                            int patch_dim, float drop_p, unsigned long long seed, unsigned long long offset,
-                            const unsigned long long* epoch, float* ws, hipStream_t stream);
-int mpo_launch_patch_wgrad_f16x(const float* dh, const float* hbag, const void* x, long long total_rows, int embed, int patch_dim,
-                                float gate, float* d_weight, float* d_bias, float* ws, hipStream_t stream);
+// fp32- or fp16-stored window (x_f16: x is fp16 [total_rows][1024], and takes no feature scale): the patch layer as three- or
+// two-term fp16 products, its weight gradient as three-term bf16 products (patch_fc_split.hip); ws = the *_workspace_floats()
+// below, the same for both windows
+size_t mpo_patch_fc_split_workspace_floats();
+size_t mpo_patch_wgrad_split_workspace_floats();
+int mpo_launch_patch_fc_split(const void* x, bool x_f16, const float* w, const float* bias, float* h, long long total_rows,
+                              int embed, int patch_dim, float drop_p, unsigned long long seed, unsigned long long offset,
+                              const unsigned long long* epoch, float x_scale, const float* x_scale_dev /* nullable: DEVICE, read at run time in place of x_scale */,
+                              float* ws, hipStream_t stream);
+int mpo_launch_patch_wgrad_split(const float* dh, const float* hbag, const void* x, bool x_f16, long long total_rows, int embed,
+                                 int patch_dim, float gate, float* d_weight, float* d_bias, float* ws, hipStream_t stream);
 // K2's patch-side gradient with the product back through the key projection inside the pass (k2_patchgrad.hip)
 int mpo_launch_k2_patch_grad(const int* cu, const void* dk_bf16, const float* w_k, const float* amap, const float* dctx,
                              const void* hbag_bf16, void* out_bf16, float gate, float* part_colsum, int n_q, int embed,

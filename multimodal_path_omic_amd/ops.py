@@ -514,41 +514,50 @@ def patch_weight_grad(g: torch.Tensor, x: torch.Tensor, out: torch.Tensor) -> to
     return out
 
 
+def _patch_fc_split_forward(ctx, window, entry, x, weight, bias, drop_p, rate, *scale):
+    """What PatchFcF32Fn.forward and PatchFcF16Fn.forward share (csrc/patch_fc_split.hip): H_bag, the dropout counters, the
+    workspace, the call -- `rate` as the entry takes it (p, or round(256 p)), `scale` the fp32 window's feature scale -- and
+    what the backward reads off ctx."""
+    h = torch.empty(x.shape[0], weight.shape[0], device=x.device, dtype=torch.float32)
+    seed, off = _reserve(h.numel() // 16 + 2) if drop_p > 0 else (0, 0)
+    ws = _workspace(getattr(L.lib(), f"mpo_patch_fc_{window}_workspace_bytes")(0), x.device)
+    L.call(entry, L.ptr(x), x.shape[0], x.shape[1], L.ptr(weight), L.ptr(bias), weight.shape[0], rate, seed, off, _epoch(), *scale,
+           L.ptr(h), L.ptr(ws), ws.numel(), L.stream_of(x))
+    ctx.save_for_backward(x, h)
+    ctx.param_refs = (weight, bias)
+    return h
+
+
+def _patch_fc_split_backward(ctx, window, dh, rate):
+    """The one backward pass of both windows; `rate` as the entry takes it (the fp32 window's gate, the fp16 window's drop_256)."""
+    x, h = ctx.saved_tensors
+    dh = dh.contiguous()
+    dw, db = (grad_out(p) for p in ctx.param_refs)
+    ws = _workspace(getattr(L.lib(), f"mpo_patch_fc_{window}_workspace_bytes")(1), x.device)
+    L.call(f"mpo_patch_fc_{window}_backward", L.ptr(dh), L.ptr(h), L.ptr(x), x.shape[0], h.shape[1], x.shape[1], rate, L.ptr(dw),
+           L.ptr(db), L.ptr(ws), ws.numel(), L.stream_of(x))
+    return None, dw, db, None
+
+
 class PatchFcF32Fn(torch.autograd.Function):
     """H_bag = dropout_p(relu(X W_H^T + b)) for an fp32-stored window through Linear(1024, 256) (models/mcat/mcat.py:24-29,87),
-    hand-written both ways (csrc/patch_fc_f32.hip): products as three bf16 MFMA terms of hi / lo operand splits (fp32
+    hand-written both ways (csrc/patch_fc_split.hip): products as three bf16 MFMA terms of hi / lo operand splits (fp32
     accumulation, ~4e-6 absolute on H_bag), dropout mask kept in H_bag as zeros; backward = ONE pass that applies the
     ReLU / dropout derivative read off H_bag to the incoming gradient and forms dW_H = g^T X and db_H = colsum(g)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, drop_p: float):
-        lib = L.lib()
-        h = torch.empty(x.shape[0], weight.shape[0], device=x.device, dtype=torch.float32)
         ctx.gate = 1.0 / (1.0 - _realised_drop(drop_p)) if drop_p > 0 else 1.0
-        seed, off = _reserve(h.numel() // 16 + 2) if drop_p > 0 else (0, 0)
-        ws = _workspace(lib.mpo_patch_fc_f32_workspace_bytes(0), x.device)
         # a window that carries a device scale (feature_scale_device: a sampler's output, a captured step's window) is read
         # through it when the kernel starts; any other window's scale is found on the host and passed by value
         scale_dev = getattr(x, "_mpo_feature_scale_dev", None)
         entry, scale = ("mpo_patch_fc_f32_forward", feature_scale(x)) if scale_dev is None else \
                        ("mpo_patch_fc_f32_forward_dev", L.ptr(_check_scale_tensor(scale_dev, x)))
-        L.call(entry, L.ptr(x), x.shape[0], x.shape[1], L.ptr(weight), L.ptr(bias), weight.shape[0],
-               float(drop_p), seed, off, _epoch(), scale, L.ptr(h), L.ptr(ws), ws.numel(),
-               L.stream_of(x))
-        ctx.save_for_backward(x, h)
-        ctx.param_refs = (weight, bias)
-        return h
+        return _patch_fc_split_forward(ctx, "f32", entry, x, weight, bias, drop_p, float(drop_p), scale)
 
     @staticmethod
     def backward(ctx, dh):
-        lib = L.lib()
-        x, h = ctx.saved_tensors
-        dh = dh.contiguous()
-        dw, db = (grad_out(p) for p in ctx.param_refs)
-        ws = _workspace(lib.mpo_patch_fc_f32_workspace_bytes(1), x.device)
-        L.call("mpo_patch_fc_f32_backward", L.ptr(dh), L.ptr(h), L.ptr(x), x.shape[0], h.shape[1], x.shape[1], ctx.gate, L.ptr(dw),
-               L.ptr(db), L.ptr(ws), ws.numel(), L.stream_of(x))
-        return None, dw, db, None
+        return _patch_fc_split_backward(ctx, "f32", dh, ctx.gate)
 
 
 def feature_scale(x) -> float:
@@ -614,7 +623,7 @@ def patch_fc_f32(x, weight, bias, drop_p: float):
 
 class PatchFcF16Fn(torch.autograd.Function):
     """H_bag = dropout_p(relu(X W_H^T + b)) for an fp16-stored window through Linear(1024, 256) (models/mcat/mcat.py:24-29,87),
-    hand-written both ways (csrc/patch_fc_f16.hip), H_bag in fp32: PatchFcF32Fn without a feature scale.  An fp16 feature is
+    hand-written both ways (csrc/patch_fc_split.hip), H_bag in fp32: PatchFcF32Fn without a feature scale.  An fp16 feature is
     one fp16 MFMA operand as stored, so the forward takes two terms W_hi X + W_lo X (fp32 accumulation; against the fp64
     product of the stored operands only W's 2^-22 tail is lost) and the same dropout stream as the fp32 kernel: equal (seed,
     offset, epoch) give equal masks.  Backward = the fp32 window's ONE pass (ReLU / dropout derivative read off H_bag,
@@ -623,33 +632,18 @@ class PatchFcF16Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, drop_p: float):
-        lib = L.lib()
         if not patch_fc_f16_supported(x, weight):
             raise ValueError(f"fp16 patch layer: built for a contiguous fp16 window through Linear(1024, 256) (got {x.dtype} "
                              f"{tuple(x.shape)} through a weight {tuple(weight.shape)})")
-        h = torch.empty(x.shape[0], weight.shape[0], device=x.device, dtype=torch.float32)
         # the entries take the rate as the kernel realises it, in 256ths (one integer for both directions: mpo_patch_f16.h);
         # ctx.gate is the keep scale the backward entry forms from it
         ctx.drop_256 = int(round(_realised_drop(drop_p) * 256)) if drop_p > 0 else 0
         ctx.gate = 256.0 / (256.0 - ctx.drop_256)
-        seed, off = _reserve(h.numel() // 16 + 2) if drop_p > 0 else (0, 0)
-        ws = _workspace(lib.mpo_patch_fc_f16_workspace_bytes(0), x.device)
-        L.call("mpo_patch_fc_f16_forward", L.ptr(x), x.shape[0], x.shape[1], L.ptr(weight), L.ptr(bias), weight.shape[0],
-               ctx.drop_256, seed, off, _epoch(), L.ptr(h), L.ptr(ws), ws.numel(), L.stream_of(x))
-        ctx.save_for_backward(x, h)
-        ctx.param_refs = (weight, bias)
-        return h
+        return _patch_fc_split_forward(ctx, "f16", "mpo_patch_fc_f16_forward", x, weight, bias, drop_p, ctx.drop_256)
 
     @staticmethod
     def backward(ctx, dh):
-        lib = L.lib()
-        x, h = ctx.saved_tensors
-        dh = dh.contiguous()
-        dw, db = (grad_out(p) for p in ctx.param_refs)
-        ws = _workspace(lib.mpo_patch_fc_f16_workspace_bytes(1), x.device)
-        L.call("mpo_patch_fc_f16_backward", L.ptr(dh), L.ptr(h), L.ptr(x), x.shape[0], h.shape[1], x.shape[1], ctx.drop_256,
-               L.ptr(dw), L.ptr(db), L.ptr(ws), ws.numel(), L.stream_of(x))
-        return None, dw, db, None
+        return _patch_fc_split_backward(ctx, "f16", dh, ctx.drop_256)
 
 
 def patch_fc_f16_supported(x, weight) -> bool:

@@ -208,7 +208,7 @@ def test_a_rate_that_rounds_to_256_is_refused_before_anything_is_reserved():
     with pytest.raises(ValueError, match=r"realised as round\(256 p\) / 256 = 256/256"):
         ops._realised_drop(0.999)
     assert ops._realised_drop(0.99) == 253 / 256 and ops._rng_calls == calls
-    # the C entries word it the same way (csrc/patch_fc_fwd.hip, csrc/patch_fc_f32.hip)
-    for name in ("patch_fc_fwd.hip", "patch_fc_f32.hip"):
+    # the C entries word it the same way (csrc/patch_fc_fwd.hip, csrc/patch_fc_split.hip)
+    for name in ("patch_fc_fwd.hip", "patch_fc_split.hip"):
         with open(os.path.join(ROOT, "multimodal_path_omic_amd", "csrc", name)) as f:
             assert "is realised as round(256 p) / 256 = %u/256" in f.read(), name

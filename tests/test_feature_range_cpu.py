@@ -1,5 +1,5 @@
 """CPU-only checks of the device feature scale's entries (include/mpo_feature_range.h, csrc/feature_range.hip, the _dev
-forward of csrc/patch_fc_f32.hip): the header and its exports, the entry points' refusals, the new Python arguments, and
+forward of csrc/patch_fc_split.hip): the header and its exports, the entry points' refusals, the new Python arguments, and
 ops.feature_scale itself, which the device pass must equal bit for bit, pinned on CPU tensors.  Nothing here launches a
 kernel."""
 import ctypes

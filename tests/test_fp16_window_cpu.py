@@ -1,4 +1,4 @@
-"""CPU-only checks of the fp16 window (include/mpo_patch_f16.h, csrc/patch_fc_f16.hip): the header and its exports, the
+"""CPU-only checks of the fp16 window (include/mpo_patch_f16.h, csrc/patch_fc_split.hip): the header and its exports, the
 entries' refusals before any launch, the compiler's resource rows of the two new kernels and of the fp32 window's kernels
 beside them (those must not have moved), and what fp16 storage of the patch matrix costs by the oracle at the benchmarked
 bag length -- the reason the storage mode exists.  Nothing here launches a kernel."""
@@ -96,9 +96,9 @@ def test_python_surface():
 
 
 def test_the_new_kernels_use_no_scratch_and_the_fp32_windows_kernels_have_not_moved():
-    """The fp32 window's kernels now take their shared pieces from csrc/patch_fc_split.h and patch_wgrad_reduce.h: the
-    compiler's resource rows of that file, recorded before the move, are held here (NOTES.md: the ISA text differs in the
-    compilation-unit id alone)."""
+    """Both windows' kernels are instances of one body per direction in csrc/patch_fc_split.hip: the compiler's resource rows
+    of the fp32 window's kernels, recorded when they had a file of their own, are held here (NOTES.md: what the ISA text of
+    each kernel differs in)."""
     _build = importlib.import_module("multimodal_path_omic_amd._build")
     _build.build(verbose=False)
     usage = _build.resource_usage()

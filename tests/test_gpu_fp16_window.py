@@ -1,5 +1,5 @@
 """An fp16-stored window (bag_dtype=torch.float16) through the models and the harness: the patch matrix alone is stored in fp16,
-H_bag and everything behind it is fp32 (ops.patch_fc_f16, csrc/patch_fc_f16.hip).  The oracle is fed the same stored values --
+H_bag and everything behind it is fp32 (ops.patch_fc_f16, csrc/patch_fc_split.hip).  The oracle is fed the same stored values --
 X rounded to fp16, nothing else (bag_storage=torch.float16, storage_points=("x",)) -- and the models are then held to the bars
 the fp32-bag model tests use: the kernels' own arithmetic is the fp32 window's.  Against the fp32 REFERENCE's fixtures at the
 benchmarked bag length what remains is the storage floor of X itself (tests/test_fp16_window_cpu.py).

@@ -223,7 +223,7 @@ def test_full_size_bf16_training_window_equals_per_slide(dev, kind):
 
 def test_whole_model_at_100k_fp32_patches_matches_oracle(dev):
     """BASELINE config 5 as ONE model: a 100 000 x 1024 fp32 slide through MCAT medium -- the fp32 patch
-    layer (fp16-split MFMA products, patch_fc_f32.hip), K1's forward over the fp32 H_bag, the tail, `ces`, K1's vector backward,
+    layer (fp16-split MFMA products, patch_fc_split.hip), K1's forward over the fp32 H_bag, the tail, `ces`, K1's vector backward,
     the one-pass fp32 weight gradient -- against the CPU oracle on the same slide: hazards, the co-attention map (sampled
     columns), a sample of dW_H rows and the patch layer's bias gradient.  (The per-kernel tests hold each of these kernels at
     this size alone; the bench runs the chain unchecked.)"""

@@ -1,4 +1,4 @@
-"""The patch layer of an fp16-stored window on the hand-written kernels (mpo_patch_fc_f16_*, csrc/patch_fc_f16.hip;
+"""The patch layer of an fp16-stored window on the hand-written kernels (mpo_patch_fc_f16_*, csrc/patch_fc_split.hip;
 models/mcat/mcat.py:24-29,87 and its backward): the forward as two fp16 MFMA terms W_hi X + W_lo X against the fp64 product
 of the SAME stored operands (X as fp16 stores it, W_H fp32), the one-pass backward (ReLU / dropout derivative read off H_bag,
 dW_H = g^T X with X split exactly into bf16 hi + lo, db_H = colsum g) against fp64 as well.  The only rounding left is W's

@@ -1,4 +1,4 @@
-"""The patch layer of an fp32-stored window on the hand-written kernels (mpo_patch_fc_f32_*, csrc/patch_fc_f32.hip;
+"""The patch layer of an fp32-stored window on the hand-written kernels (mpo_patch_fc_f32_*, csrc/patch_fc_split.hip;
 models/mcat/mcat.py:24-29,87 and its backward): forward against the fp64 product of the same fp32 operands, the one-pass
 backward (ReLU / dropout derivative read off H_bag, dW_H = g^T X, db_H = colsum g) against fp64 as well.  The products run
 as three half-precision MFMA terms of hi / lo operand splits -- fp16 splits forward (the ReLU mask must not flip against the

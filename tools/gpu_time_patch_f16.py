@@ -1,4 +1,4 @@
-"""Timing: the patch layer of an fp16-stored window (csrc/patch_fc_f16.hip) beside the fp32 window's (csrc/patch_fc_f32.hip) and
+"""Timing: the patch layer of an fp16-stored window beside the fp32 window's (both csrc/patch_fc_split.hip) and
 the bf16 window's (csrc/patch_fc_fwd.hip, csrc/patch_wgrad.hip), forward and weight gradient, at 8 x 100 000 and 32 x 15 000
 rows; then the eager MCAT window step (harness.train_window, dropout on) on an fp32 against an fp16 window of 8 x 15 000 rows.
 HIP events around 10 calls, 3 warm-up calls, 7 repeats with the ways alternated inside each repeat; median and spread
